@@ -13,9 +13,12 @@ included; only the transforms' twiddle / eigenvalue tables (a few KB, functions 
         bench.py --gpus N --steps K --warmup W          # z-slab partition over N GPUs, RCCL halo + all-reduce
 
 Prints ONE JSON line on rank 0.  `value` = grid nodes / s of the whole job (strong scaling: the grid is fixed,
-its z-slabs are spread over the ranks).  `roofline` is for the kernel that dominates the step: Step 1+2 (vector-ALU bound,
+its z-slabs are spread over the ranks); `ms_per_step` = milliseconds of one timed step.  A plain run does only what that line needs: set-up,
+--warmup untimed steps, --steps timed steps, the figures the library sampled inside them.  --full adds what takes runs of its own (the CPU
+baseline, the live PMC traffic of Step 1, the `also` / `also_multi` legs; --no-cpu-baseline / --no-live-traffic / --no-also leave single
+ones out).  --dump-outputs DIR writes phi of the last timed step to DIR (see dump_outputs).  `roofline` is for the kernel that dominates the step: Step 1+2 (vector-ALU bound,
 fp64 vector peak = fp64 matrix peak = 78.6 TFLOP/s on MI355X) when it outlasts the CG loop, else the CG loop's dominant kernel
-against HBM; `roofline_pcg` always carries the latter.  Durations are measured live by HIP events on the solver's stream.  `cpu_baseline` times the C oracle (a port of the
+against HBM; `roofline_pcg` always carries the latter.  Durations are measured live by HIP events on the solver's stream.  `cpu_baseline` (--full) times the C oracle (a port of the
 reference's serial loops, oracle/shm_oracle.c) on this box's host cores over a bounded sample.
 """
 import argparse
@@ -459,6 +462,38 @@ def multi_gpu_legs(shm, HostSolver, dist, torch, args, pre, precision, scrub, ra
     return out
 
 
+DUMP_FULL_NODES = 1 << 22    # up to this many grid nodes --dump-outputs writes the whole of phi (32 MB in fp64) ...
+DUMP_SAMPLE_NODES = 1 << 21  # ... above, a fixed sample of about this many nodes, with their indices (2 x 16 MB)
+
+
+def dump_outputs(solver, out_dir, n, rank, world, dist):
+    """What a caller of the timed path receives, from its last step: phi (GridSolver.get_phi, fp64; each rank holds its z-slab).  Grids up to
+    DUMP_FULL_NODES nodes are written whole as phi.npy (rank-major = the grid's linear node order); larger ones as a sample at node indices
+    drawn with a fixed seed (phi.npy, and phi_index.npy: the linear node indices, as float64).  The inputs come from the data files and the
+    sample depends only on n, so two runs with the same arguments write comparable files.  Collective over the ranks; rank 0 writes."""
+    phi, (k0, k1) = solver.get_phi()
+    N = n ** 3
+    lo = k0 * n * n
+    if N <= DUMP_FULL_NODES:
+        idx = None
+        vals = phi
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, N, size=DUMP_SAMPLE_NODES))
+        idx = idx[(idx >= lo) & (idx < k1 * n * n)]
+        vals = phi[idx - lo]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (idx, vals))
+        if idx is not None:
+            idx = np.concatenate([p[0] for p in parts])
+        vals = np.concatenate([p[1] for p in parts])
+    if rank == 0:
+        os.makedirs(out_dir, exist_ok=True)
+        np.save(os.path.join(out_dir, "phi.npy"), np.ascontiguousarray(vals, dtype=np.float64))
+        if idx is not None:
+            np.save(os.path.join(out_dir, "phi_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -466,6 +501,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="bunny_small_256_f64", choices=sorted(WORKLOADS))
     ap.add_argument("--tol", type=float, default=0.0, help="projected-CG relative residual tolerance (0 = library default)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: the CPU baseline, the live PMC traffic of Step 1 and the "
+                                                        "extra legs (`also` at N=1, `also_multi` at N>1); a plain run times the steps and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write phi of the last timed step to DIR/phi.npy (fp64; above 2^22 nodes a fixed "
+                                                                       "sample, node indices in DIR/phi_index.npy)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-live-traffic", action="store_true", help="take roofline.traffic from the committed PMC record instead of measuring it (two rocprofv3 child runs, ~30 s)")
     ap.add_argument("--no-also", action="store_true", help="skip the extra legs (N=1: all-fp64 Step 1, 512^3 end-to-end, 512^3 stencil-PCG fp64/fp32 on bunny and rocker, "
@@ -546,6 +585,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs:
+        dump_outputs(solver, args.dump_outputs, n, rank, world, dist)
 
     out = None
     if rank == 0:
@@ -635,7 +676,7 @@ def main():
                                        "summed over its launches (3 words per node written; irrelevant to the bound)" % s1["launches_per_step"]}
         else:
             out["roofline"] = dict(out["roofline_pcg"])
-        if not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only (the extra plain-CG solve below is a collective at N>1)
+        if args.full and not args.no_cpu_baseline and world == 1:  # rank 0 at N=1 only (the extra plain-CG solve below is a collective at N>1)
             try:
                 st_plain = solver.solve(tol=args.tol, scrub=scrub, solver="primal", precond="none")  # untimed: iteration count of the port's algorithm
                 out["cpu_baseline"] = cpu_baseline(pre, int(st_plain.iters), out["config"]["tol"])
@@ -648,7 +689,7 @@ def main():
             except Exception as e:  # the baseline is informational; never lose the GPU line over it
                 out["cpu_baseline"] = {"value": None, "unit": "grid-nodes/s", "cores": 1, "kind": "port", "sample": "failed: %r" % (e,)}
         out["roofline"]["traffic_source"] = "committed record %s (rocprofv3 PMC passes of tools/profile_r06.sh)" % os.path.relpath(tfile, ROOT) if out["roofline"].get("traffic") else None
-        if world == 1 and not args.no_also and not args.no_live_traffic and out["roofline"].get("bound") == "valu":
+        if args.full and world == 1 and not args.no_also and not args.no_live_traffic and out["roofline"].get("bound") == "valu":
             live, how = live_step1_traffic(path, hCoef, precision)
             if live is not None:
                 out["roofline"]["traffic_committed_record"] = out["roofline"].get("traffic")
@@ -656,13 +697,13 @@ def main():
                 out["roofline"]["traffic_source"] = how
             else:
                 out["roofline"]["traffic_live_attempt"] = how
-        if world == 1 and not args.no_also and args.workload == "bunny_small_256_f64":
+        if args.full and world == 1 and not args.no_also and args.workload == "bunny_small_256_f64":
             try:
                 solver.close()
                 out["also"] = also_legs(shm, HostSolver, local_rank, args.tol, pre, scrub)
             except Exception as e:  # never lose the headline over an extra leg
                 out["also"] = {"failed": repr(e)}
-    if world > 1 and not args.no_also and args.solver == "auto" and args.precond == "auto" and args.max_iters == 0:
+    if args.full and world > 1 and not args.no_also and args.solver == "auto" and args.precond == "auto" and args.max_iters == 0:
         # The extra multi-rank legs run AFTER the headline record is complete, under a watchdog: should one of them hang on a transport this build has never
         # run on (real multi-rank RCCL: the development pool has one-GPU boxes), every rank gives up after SHM_BENCH_LEGS_TIMEOUT seconds, rank 0 prints the
         # line without them, and the processes exit -- the timed result above is never lost to an extra.

@@ -1,7 +1,11 @@
-"""Worker of tests/test_gpu_parity.py::test_multiprocess_ranks_on_one_gpu: one rank of a `world`-process solve whose RCCL calls go
-through the shared-memory test double (tests/native/rccl_mock.c)."""
+"""Worker of tests/test_gpu_parity.py::test_multiprocess_ranks_on_one_gpu: one or more ranks of a `world`-rank solve whose RCCL calls go
+through the shared-memory test double (tests/native/rccl_mock.c).  The first argument is a rank or a comma-separated list of ranks; each rank
+of a list runs in its own thread with its own solver handle (the library releases the GIL in every call, and the double keeps its group state
+per thread), so that a solve of many ranks needs fewer processes with the GPU open."""
 import os
 import sys
+import threading
+import traceback
 
 import numpy as np
 
@@ -10,8 +14,7 @@ sys.path.insert(0, ROOT)
 import shm_import  # noqa: E402
 
 
-def main():
-    rank, world, uid_hex, case, mode, out_dir = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6]
+def run_rank(rank, world, uid_hex, case, mode, out_dir):
     shm = shm_import.load()
     precision = int(os.environ.get("SHM_WORKER_PRECISION", "64"))
     if case.startswith("file:"):   # file:<data file>:<hCoef> -- pre-processed by the C++ host mirror instead of a golden fixture (no oracle phi in it)
@@ -66,6 +69,31 @@ def main():
     np.save(os.path.join(out_dir, "phi_%d.npy" % rank), phi)
     np.save(os.path.join(out_dir, "meta_%d.npy" % rank), np.array([k0, k1, st.iters, st.shift]))
     s.close()
+
+
+def main():
+    ranks = [int(r) for r in sys.argv[1].split(",")]
+    args = (int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5], sys.argv[6])
+    if len(ranks) == 1:
+        run_rank(ranks[0], *args)
+        return
+    shm_import.load()   # (once, before the threads)
+
+    def body(rank):
+        try:
+            run_rank(rank, *args)
+        except BaseException:
+            # a failed rank leaves its peers waiting in a collective: report it and take the whole process down at once
+            traceback.print_exc()
+            sys.stdout.flush()
+            sys.stderr.flush()
+            os._exit(1)
+
+    threads = [threading.Thread(target=body, args=(r,)) for r in ranks]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
 
 
 if __name__ == "__main__":

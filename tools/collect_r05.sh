@@ -5,7 +5,7 @@ R="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 O="$R/gpurun_out/r05"
 mkdir -p "$O"
 cd "$R" || exit 1
-python bench.py > "$O/bench_default.json" 2> "$O/bench_default.err"
+python bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"
 for w in bunny_small_64_f64 bunny_small_128_f64 bunny_small_512_f64 bunny_pc_512_f64 rocker_512_f32 bunny_small_512_f32; do
   python bench.py --workload $w --no-cpu-baseline --no-also --steps 3 --warmup 1 > "$O/bench_$w.json" 2> "$O/bench_$w.err"
 done
