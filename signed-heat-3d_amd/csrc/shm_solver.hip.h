@@ -19,6 +19,7 @@
 #include "shm_dct.hip.h"
 #include "shm_dct_gemm.hip.h"
 #include "shm_green_fft.hip.h"
+#include "shm_plan.h"
 
 namespace shm {
 
@@ -65,7 +66,6 @@ struct Solver final : SolverBase {
     hipStream_t stream2 = nullptr;  // constraint set-up ((A A^T)^-1), overlapped with the Step-1 kernel
     hipStream_t stream3 = nullptr;  // explicit Schur complement of the dual solver: beside the inversion of G (stream2) and Step 1 (created on first use)
     std::unique_ptr<Event> e_sch_in, e_sch_done, e_gs_done;
-    bool gs_early = false;   // this solve's Green's table was queued before the host built the rows (enqueue_green_table)
     hipStream_t stream_h = nullptr;  // halo exchange of the fused primal CG, overlapped with the interior z chunks of its DIR sweep (created on first use)
     int n = 0, alloc_n = -1;
     size_t N = 0;
@@ -88,7 +88,6 @@ struct Solver final : SolverBase {
     bool conv_tiered32 = false;                                // fp32 handles: Step 1 through the tiered kernel's packed-fp32 body
     bool fold_pq = false;                                      // fused stencil CG on one GPU: the RES sweep sums the DIR sweep's partials of p'.Kp' itself
     int fold_pq_np = 0;
-    int dual_form_req = SHM_DUAL_AUTO;                         // shm_opts.dual_form of the solve in progress
     double step1_budget = 0.;                                  // shm_opts.step1_budget of the solve in progress (<= 0: kTierBudget)
     DevArray<unsigned long long> d_pair_counters;              // [0] fp64 pairs, [1] fp32 pairs evaluated by the last Step 1, [2] pairs evaluated again in fp64 (a-posteriori test)
     DevArray<unsigned> d_unit_counters;                        // tiered Step 1: eight work-queue heads (one per XCD) per launch (zeroed at the start of every Step 1)
@@ -156,12 +155,9 @@ struct Solver final : SolverBase {
     DevArray<Cplx<double>> gs_tw;
     std::vector<int> h_rowX;
     bool have_S = false;
-    bool dual_direct_requested = false, dual_direct = false;   // direct dual solve: S^-1 (Sinv) instead of G^-1; requested by solve(), decided in build_constraints()
     DevArray<double> Sinv, Sinv_ones /* S^-1 1: the border of the direct solve, formed once per set-up behind the inversion */;
-    // s_setprio(3) in the set-up kernels that share the SIMDs with the tiered Step 1: they are short and on the critical path when Step 1 is (64^3 ... 256^3, thin
-    // slabs of a multi-GPU run); where Step 1 outlasts the set-up several times over the raised priority only costs Step 1 issue slots at the wrong moments
-    // (512^3: 198.8 -> 196-197 ms, bunny.pc 512^3: 106.0 -> 104-105 ms without it; 128^3: 6.2 -> 7.7 ms, hence the switch).  Decided per solve in build_constraints().
-    int setup_prio = 1;
+    PlanIn plan_in;   // the inputs and the plan of the set-up in progress (shm_plan.h): given to build_constraints(), read by the stages after it
+    Plan plan;
     double conv_est_total_ms = 1e30;   // estimate of this rank's last Step-1 launch (1e30: none was launched -- stand-alone set-up, test entry points)
     int gs_n = 0;   // grid the Green's table in gs_T was built for (0: none)
     double gs_cell = 0.;
@@ -576,6 +572,20 @@ struct Solver final : SolverBase {
             full_problem_set = true;
         }
     }
+    Step1Kernel step1_kernel() const { return conv_tiered ? kStep1TieredF64 : conv_tiered32 ? kStep1TieredF32 : kStep1Untiered; }
+    // What the plan of a solve (shm_plan.h) is drawn from: this solver's grid and slabs, its last Step 1, the options (null: the defaults) and the form knobs
+    PlanIn plan_inputs(const shm_opts* o) const {
+        PlanIn in;
+        in.f64 = sizeof(T) == 8; in.n = n; in.S = S; in.total_slabs = total_slabs;
+        in.full_wanted = full_wanted(); in.fft_available = fft_available(); in.gemm_dct = gemm_dct(); in.fused_available = fused_available();
+        in.step1 = step1_kernel(); in.conv_est_total_ms = conv_est_total_ms;
+        if (o) {
+            in.solver = o->solver; in.preconditioner = o->preconditioner; in.dual_form = o->dual_form;
+            in.step1_budget = o->step1_budget; in.fast = o->fast_integration != 0;
+        }
+        in.knobs = plan_knobs(knob);
+        return in;
+    }
     void select_step1_arith(int arith) {
         if (arith != SHM_STEP1_AUTO && arith != SHM_STEP1_EXACT_F64) throw Error(SHM_ERR_INVALID, "unknown step1_arith");
         conv_tiered = sizeof(T) == 8 && arith == SHM_STEP1_AUTO && knob("SHM_CONV_EXACT") == nullptr && tier_exponent_span_ok();
@@ -951,7 +961,6 @@ struct Solver final : SolverBase {
         need_problem();
         HIPCHK(hipSetDevice(cfg.device));
         step1_budget = 0.;   // (the stage entry points run with the library's defaults, whatever the last solve's shm_opts asked for)
-        dual_form_req = SHM_DUAL_AUTO;
         select_step1_arith(step1_arith);
         launch_conv();
         HIPCHK(hipStreamSynchronize(stream));
@@ -1103,18 +1112,27 @@ struct Solver final : SolverBase {
         // (per-pair costs of the round-4 kernel; the round-5 one is ~7 % faster, but the 0.38 of the rule that reads this estimate was drawn with these constants)
         return nodes * (double)S * (1.229e-9 * f_near + 1.84e-10 * (f_keep - f_near) + 3.3e-12);
     }
+    // The Step 1 a set-up hides behind (plan_rows): the whole-grid solver of a multi-rank run hides its set-up behind the RANK's share of Step 1, which
+    // conv_est_ms (the rank's nominal estimate) carries in nominal pairs
+    double step1_hidden_ms(double conv_est_ms) const {
+        double nodes_here = 0.;
+        for (const Slab<T>& sl : slabs) nodes_here += (double)sl.nown;
+        const double share = std::min(1.0, conv_est_ms / std::max(1e-30, nodes_here * (double)S / 1.2e9));
+        return estimate_step1_ms_tiered() * share;
+    }
 
     // Per-slab CSR pieces, shift items, G = A A^T (sparse triplets -> dense on device -> inverted) and B = A K A^T.
     // Order: everything the inversion needs first (rows, G), then the Gauss-Jordan kernels are enqueued, and the rest of the host
     // work (per-slab lists, B, active-tile lists) runs while the GPU inverts; uploads come last (a pageable copy waits for the stream).
-    void build_constraints() {
+    // `in`, `p`: the inputs and the plan of this set-up (plan_solve's for a solve, the defaults -- no dual solve requested -- for the test entry points)
+    void build_constraints(const PlanIn& in, const Plan& p) {
         hipStream_t stream = stream2;  // everything below runs beside the Step-1 kernel of the main stream
         const auto th0 = std::chrono::steady_clock::now();
-        static const int prio_env = knob("SHM_SETUP_PRIO") ? atoi(knob("SHM_SETUP_PRIO")) : -1;   // A/B knob: 0 / 1
-        setup_prio = prio_env >= 0 ? prio_env : (conv_tiered && conv_est_total_ms >= 150. && conv_est_total_ms < 1e29 ? 0 : 1);   // (estimate: 256^3 bunny 40, 512^3 320 / 160 ms)
+        plan_in = in;
+        plan = p;
+        plan_setup(plan_in, plan);
         auto lap = [&](const char* what) { log("[shm]   setup %-28s %.2f ms", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count()); };
-        gs_early = green_table_early_ok();
-        if (gs_early) {
+        if (plan.green_early) {
             enqueue_green_table(stream);
             if (!e_gs_done) e_gs_done.reset(new Event());
             e_gs_done->record(stream);
@@ -1122,42 +1140,14 @@ struct Solver final : SolverBase {
         build_rows();
         lap("rows");
         const size_t plane = (size_t)n * n;
-        // Direct dual solve (moderate m, explicit S): S itself is inverted on the set-up stream instead of G, and the dual system is solved with two dense
-        // mat-vecs after Step 1 -- no G, no B, no iteration (see solve_dual), and none of the host tables
-        // below that only they and the sparse sweeps of the iterative dual solver need (entries sorted by node, node -> rows hash, active tiles).
-        // (shm_opts.dual_form -- `dual_form_req` -- overrides the rules below: DIRECT wherever the explicit S fits, or one of the two iterative forms)
-        const bool no_direct = knob("SHM_DUAL_NO_DIRECT") != nullptr || dual_form_req == SHM_DUAL_EXPLICIT_S_CG || dual_form_req == SHM_DUAL_THROUGH_GRID;
-        static const int direct_max_m_env = knob("SHM_DUAL_DIRECT_MAX_M") ? atoi(knob("SHM_DUAL_DIRECT_MAX_M")) : 4096;   // single-level Gauss-Jordan range
-        const int direct_max_m = dual_form_req == SHM_DUAL_DIRECT ? 16384 : direct_max_m_env;
-        dual_direct = dual_direct_requested && !no_direct && m <= direct_max_m;
-        // Round 4: between 4096 and 16384 rows the direct solve pays exactly where this rank's Step 1 outlasts the inversion of S that runs beside it (measured,
-        // tools/r04_ab.py, ms per solve iterative / direct: rocker 128^3 (m = 4 169) 23.9 / 19.8, SprayBottle 128^3 (4 141) 70.2 / 65.3, chair 256^3 (6 340) 58.7 / 57.8,
-        // chair 512^3 (7 748) 373.6 / 367.5 -- and rocker 256^3 (9 110) 97.4 / 106.9, SprayBottle 256^3 (12 620) 174 / 221, knot 128^3 (12 155) 55.6 / 96.5).  The
-        // line is drawn per problem from an estimate of Step 1 that knows what the tiers drop (estimate_step1_ms_tiered: +-25 % over the data files) and of the
-        // set-up on an idle device (assembly 1.4e-7 m^2, inversion 5.5e-11 m^3, the Green's table); beside Step 1 the set-up runs at ~0.4 of that speed.
-        static const bool direct_est_off = knob("SHM_DUAL_DIRECT_EST_OFF") != nullptr;   // A/B knob: the fixed limit alone
-        if (!dual_direct && dual_direct_requested && !no_direct && !direct_est_off && (conv_tiered || conv_tiered32) && precond_available() && !gemm_dct() && n <= 512 &&
-            m > direct_max_m && m <= 16384 && conv_est_total_ms < 1e29) {
-            const double md = (double)m;
-            const double table_ms = 10.0 * std::pow((double)n / 512.0, 4.0);
-            const double setup_alone_ms = 5.5e-11 * md * md * md + 1.4e-7 * md * md + table_ms;
-            // (the whole-grid solver of a multi-rank run hides its set-up behind the RANK's share of Step 1: conv_est_total_ms carries that share in nominal pairs)
-            double nodes_here = 0.;
-            for (const Slab<T>& sl : slabs) nodes_here += (double)sl.nown;
-            const double share = std::min(1.0, conv_est_total_ms / std::max(1e-30, nodes_here * (double)S / 1.2e9));
-            const double step1_ms = estimate_step1_ms_tiered() * share;
-            dual_direct = setup_alone_ms <= 0.38 * step1_ms;
-            log("[shm]   direct solve for m = %d: set-up alone ~%.1f ms, Step 1 ~%.1f ms -> %s", m, setup_alone_ms, step1_ms, dual_direct ? "direct" : "iterative");
-        }
-        // After the fp32 Step 1 -- which leaves the set-up's kernels no room: they run in its gaps and after it -- the direct solve's extra set-up (the
-        // Green's table: three n^4 products, 10 ms at 512^3; the assembly of S) is paid in full, and at 512^3 it costs more than the iterations it replaces
-        // (round 4, tools/r04_ab.py: bunny_small 512^3 fp32 112.8 ms direct / 107.6 iterative, bunny.pc 62.7 / 59.4; at 256^3: 15.8 / 18.5, 128^3: 4.7 / 7.3)
-        const bool direct_always = knob("SHM_DUAL_DIRECT_ALWAYS") != nullptr || dual_form_req == SHM_DUAL_DIRECT;
-        // (the all-fp64 kernel at 512^3: 321 direct / 329 iterative -- fp64 iterations cost twice as much, so only the fp32 solve changes)
-        // Round 5: the fp32 solve's Step 1 is the tiered kernel too (two waves per SIMD): its set-up runs beside it like the fp64 solve's, and the direct solve wins
-        // again (tools/r05_fp32_forms_ab.sh, ms per solve iterative / direct: bunny_small 512^3 110.0 / 102.2, bunny.pc 512^3 60.6 / 54.6, chair 512^3 214.3 / 209.4)
-        if (sizeof(T) == 4 && !conv_tiered32 && n >= 512 && !gemm_dct() && !direct_always) dual_direct = false;
-        dual_direct = dual_direct && schur_wanted();   // (schur_wanted() reads dual_direct: with it set only the structural conditions remain)
+        plan_rows(plan_in, m, [&]() { return step1_hidden_ms(plan_in.conv_est_total_ms); }, plan);
+        log("[shm] plan: %s, m=%d, form %s%s, precond %d, green table %s, G^-1 %s, prio %d; direct weighed: set-up alone ~%.1f ms, Step 1 ~%.1f ms",
+            plan_path_name(plan.path), m, plan.dual_form == SHM_DUAL_DIRECT ? "direct" : plan.dual_form == SHM_DUAL_EXPLICIT_S_CG ? "explicit-S CG" : "through grid",
+            plan.explicit_S ? " (S assembled)" : "", (int)plan.precond, plan.green_early ? "early" : "late", plan.two_level ? "two-level" : "dense", plan.setup_prio,
+            plan.est_setup_ms, plan.est_step1_ms);
+        // Direct dual solve: no G, no B, and none of the host tables below that only they and the sparse sweeps of the iterative dual solver need (entries sorted by
+        // node, node -> rows hash, active tiles)
+        const bool dual_direct = plan.dual_form == SHM_DUAL_DIRECT;
         const bool need_node_tables = !dual_direct;
         // ---- G = A A^T and B = A K A^T from the (node, row, coef) entries sorted by node: rows meet exactly at shared nodes.
         //      Sorted vectors instead of hash maps: the host part of the set-up is on the critical path of small / multi-GPU runs.
@@ -1232,8 +1222,7 @@ struct Solver final : SolverBase {
         lap("G rows");
         DevArray<uint64_t> d_tidx;  // alive until the final synchronisation below
         DevArray<double> d_tval;
-        static const int tl_min_m = knob("SHM_TL_MIN_M") ? atoi(knob("SHM_TL_MIN_M")) : 6144;  // dense inverse up to here (m^2 fp32 = 150 MB: L2 / MALL friendly, 3 launches)
-        tl.on = !dual_direct && m > tl_min_m && build_two_level(gptr, gcol, gval, d_tidx, d_tval);
+        tl.on = plan.two_level && build_two_level(gptr, gcol, gval, d_tidx, d_tval);
         std::vector<uint64_t> tidx;  // alive (like d_tidx / d_tval) until the final synchronisation below
         std::vector<double> tval;
         if (!tl.on && !dual_direct) {
@@ -1603,21 +1592,21 @@ struct Solver final : SolverBase {
             const GjBatch Bt{tl.ptrI.p, tl.offD.p, tl.offW.p, tl.D.p, tl.gjP.p, tl.gjR.p, tl.gjC.p};
             const unsigned nb = (unsigned)tl.nbMax, uP = (unsigned)P;
             for (unsigned kb = 0; kb < nb; kb++) {
-                hipLaunchKernelGGL(gj_pivot_kernel<4>, dim3(1, uP), dim3(256), 0, stream, (double*)nullptr, 0, (int)kb, (double*)nullptr, gjFlag.p + 1, setup_prio, Bt);
+                hipLaunchKernelGGL(gj_pivot_kernel<4>, dim3(1, uP), dim3(256), 0, stream, (double*)nullptr, 0, (int)kb, (double*)nullptr, gjFlag.p + 1, plan.setup_prio, Bt);
                 hipLaunchKernelGGL(gj_panels_kernel, dim3(nb, uP), dim3(kBlock), 0, stream, (const double*)nullptr, 0, (int)kb, (const double*)nullptr, (double*)nullptr, 0,
-                                   (double*)nullptr, kGJ, 0, setup_prio, Bt);
+                                   (double*)nullptr, kGJ, 0, plan.setup_prio, Bt);
                 hipLaunchKernelGGL((gj_update_kernel<GJ_ALL>), dim3(nb * (nb + 1) / 2, uP), dim3(kBlock), 0, stream, (double*)nullptr, 0, 0, (int)kb, 0, 1,
-                                   (const double*)nullptr, 0, (const double*)nullptr, kGJ, 0, kGJ, setup_prio, Bt);
+                                   (const double*)nullptr, 0, (const double*)nullptr, kGJ, 0, kGJ, plan.setup_prio, Bt);
             }
             if (nb > 1) hipLaunchKernelGGL(gj_mirror_kernel, dim3(nb * (nb - 1) / 2, uP), dim3(kBlock), 0, stream, (double*)nullptr, 0, Bt);
         }
         if (tl.nTChunks > 0)
-            hipLaunchKernelGGL(tl_T_kernel, dim3((unsigned)tl.nTChunks), dim3(kBlock), 0, stream, tl.view(), tl.tBox.p, tl.tRow.p, tl.D.p, tl.E.p, tl.Tm.p, setup_prio);
+            hipLaunchKernelGGL(tl_T_kernel, dim3((unsigned)tl.nTChunks), dim3(kBlock), 0, stream, tl.view(), tl.tBox.p, tl.tRow.p, tl.D.p, tl.E.p, tl.Tm.p, plan.setup_prio);
         for (int col = 0; col < 8; col++) {
             const int cntc = tl.schur_ptr[col + 1] - tl.schur_ptr[col];
             if (cntc > 0)
                 hipLaunchKernelGGL(tl_schur_kernel, dim3((unsigned)cntc), dim3(kBlock), 0, stream, tl.view(), tl.sBox.p + tl.schur_ptr[col], tl.sRow.p + tl.schur_ptr[col],
-                                   tl.E.p, tl.Tm.p, Ginv.p, tl.nSp, setup_prio);
+                                   tl.E.p, tl.Tm.p, Ginv.p, tl.nSp, plan.setup_prio);
         }
         // fp32 copies for the dual preconditioner
         tl.D32.alloc(std::max<size_t>(szD, 1));
@@ -1713,9 +1702,9 @@ struct Solver final : SolverBase {
         const bool stepped = outer == 1 && !classic && pivot_env == 0;
         const int pivot_e = pivot_env ? pivot_env : (refined_later ? 16 : 4);   // 16 = block Gauss-Jordan with 4 x 4 pivot blocks (round 3);   // A/B knob: 4 = 256 threads; 2 = 1024 threads (2 % faster on an idle GPU, but four 40-register waves per SIMD do not fit beside Step 1)
         auto launch_pivot = [&](int kb) {
-            if (pivot_e == 16) hipLaunchKernelGGL(gj_pivot_block4_kernel, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, setup_prio);
-            else if (pivot_e == 4) hipLaunchKernelGGL(gj_pivot_kernel<4>, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, setup_prio);
-            else hipLaunchKernelGGL(gj_pivot_kernel<2>, dim3(1), dim3(1024), 0, stream, M, mp, kb, gjP.p, gjFlag.p, setup_prio);
+            if (pivot_e == 16) hipLaunchKernelGGL(gj_pivot_block4_kernel, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
+            else if (pivot_e == 4) hipLaunchKernelGGL(gj_pivot_kernel<4>, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
+            else hipLaunchKernelGGL(gj_pivot_kernel<2>, dim3(1), dim3(1024), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
         };
         if (stepped) {
             // one launch per pivot block: step k-1's update beside step k's pivot and panels (gj_step_kernel)
@@ -1728,14 +1717,14 @@ struct Solver final : SolverBase {
                 double* Cn = gjC.p + (size_t)(k & 1) * mp * kGJ;
                 const double* Rp = gjR.p + (size_t)((k + 1) & 1) * kGJ * mp;
                 const double* Cp = gjC.p + (size_t)((k + 1) & 1) * mp * kGJ;
-                hipLaunchKernelGGL(gj_step_kernel, dim3(grid), dim3(kBlock), 0, stream, M, mp, nb, k, Rp, Cp, Rn, Cn, gjFlag.p, setup_prio);
+                hipLaunchKernelGGL(gj_step_kernel, dim3(grid), dim3(kBlock), 0, stream, M, mp, nb, k, Rp, Cp, Rn, Cn, gjFlag.p, plan.setup_prio);
             }
         } else if (outer == 1) {
             for (int kb = 0; kb < nb; kb++) {
                 launch_pivot(kb);
-                hipLaunchKernelGGL(gj_panels_kernel, dim3(nb), dim3(kBlock), 0, stream, M, mp, kb, gjP.p, gjR.p, 0, gjC.p, c_ld, 0, setup_prio);
+                hipLaunchKernelGGL(gj_panels_kernel, dim3(nb), dim3(kBlock), 0, stream, M, mp, kb, gjP.p, gjR.p, 0, gjC.p, c_ld, 0, plan.setup_prio);
                 hipLaunchKernelGGL((gj_update_kernel<GJ_ALL>), dim3((unsigned)((size_t)nb * (nb + 1) / 2)), dim3(kBlock), 0, stream, M, mp, nb, kb, 0, 1,
-                                   gjR.p, 0, gjC.p, c_ld, 0, kGJ, setup_prio);
+                                   gjR.p, 0, gjC.p, c_ld, 0, kGJ, plan.setup_prio);
             }
         } else {
             for (int k0 = 0; k0 < nb; k0 += outer) {
@@ -1743,14 +1732,14 @@ struct Solver final : SolverBase {
                 for (int t = 0; t < nO; t++) {
                     const int kb = k0 + t;
                     launch_pivot(kb);
-                    hipLaunchKernelGGL(gj_panels_kernel, dim3(nb), dim3(kBlock), 0, stream, M, mp, kb, gjP.p, gjR.p, t * kGJ, gjC.p, c_ld, t * kGJ, setup_prio);
+                    hipLaunchKernelGGL(gj_panels_kernel, dim3(nb), dim3(kBlock), 0, stream, M, mp, kb, gjP.p, gjR.p, t * kGJ, gjC.p, c_ld, t * kGJ, plan.setup_prio);
                     hipLaunchKernelGGL((gj_update_kernel<GJ_CROSS>), dim3((unsigned)(nO * nb + nO * k0)), dim3(kBlock), 0, stream, M, mp, nb, kb, k0, nO,
-                                       gjR.p, t * kGJ, gjC.p, c_ld, t * kGJ, kGJ, setup_prio);
+                                       gjR.p, t * kGJ, gjC.p, c_ld, t * kGJ, kGJ, plan.setup_prio);
                 }
                 const size_t nr = (size_t)(nb - nO);
                 if (nr > 0)
                     hipLaunchKernelGGL((gj_update_kernel<GJ_REST>), dim3((unsigned)(nr * (nr + 1) / 2)), dim3(kBlock), 0, stream, M, mp, nb, -1, k0, nO,
-                                       gjR.p, 0, gjC.p, c_ld, 0, nO * kGJ, setup_prio);
+                                       gjR.p, 0, gjC.p, c_ld, 0, nO * kGJ, plan.setup_prio);
             }
         }
         if (nb > 1) hipLaunchKernelGGL(gj_mirror_kernel, dim3((unsigned)((size_t)nb * (nb - 1) / 2)), dim3(kBlock), 0, stream, M, mp);
@@ -1763,61 +1752,15 @@ struct Solver final : SolverBase {
         hipLaunchKernelGGL((convert_kernel<double, float>), dim3(grid_for((size_t)mp * mp, 4096)), dim3(kBlock), 0, stream2, (size_t)mp * mp, Ginv.p, Ginv32.p);
         HIPCHK(hipGetLastError());
     }
-    // S = A K^+ A^T explicitly (shm_schur.hip.h), on the set-up stream.  For one slab, a DCT-sized grid and a moderate number of rows.
+    // S = A K^+ A^T explicitly (shm_schur.hip.h), on the set-up stream, where the plan asks for it (plan_explicit_S in shm_plan.h).
     //   prepare_schur(): host tables and their uploads -- BEFORE the inversion of G is queued (a pageable copy waits for everything queued on its stream)
     //   enqueue_schur(): the launches -- AFTER it (the inversion is a chain of short dependent kernels; these few throughput-bound ones fill the slots it
     //                    leaves idle)
     // The Green's table T depends on the grid alone (n, h) -- it is to K what the reference's poissonSolver factorisation is to L, built when the grid is
     // built (signed_heat_grid_solver.cpp:8-35, `rebuild`) -- but it is cheap enough to be rebuilt with every solve (see prepare_schur); S depends on the
     // sources and is assembled per solve.
-    bool schur_wanted() const {
-        const bool off = knob("SHM_DUAL_NO_DENSE_S") != nullptr || dual_form_req == SHM_DUAL_THROUGH_GRID;   // apply S through the grid (five sparse sweeps)
-        // (beyond ~8000 rows the assembly costs Step 1 more time than the dense mat-vec saves the CG: rocker 512^3 fp32, m = 12 612: 29 ms of assembly for
-        // 36 x 0.37 ms -- 493-508 against 491-501 ms per solve with S applied through the grid)
-        // (beside the tiered fp64 Step 1 -- where the assembly is co-resident and hidden -- up to 16384 rows since round 4: rocker 512^3 fp64, m = 12 612: solve phase
-        // 71.5 -> 35.9 ms, 631 -> 609 ms per solve; after the fp32 Step 1, which leaves the set-up's kernels no room, the same choice costs 401 -> 423 ms)
-        static const int max_m_env = knob("SHM_DENSE_S_MAX_M") ? atoi(knob("SHM_DENSE_S_MAX_M")) : 0;
-        // (an explicit shm_opts.dual_form request gets the documented 16384 rows whatever Step-1 kernel runs)
-        const bool asked = dual_form_req == SHM_DUAL_DIRECT || dual_form_req == SHM_DUAL_EXPLICIT_S_CG;
-        const int max_m = max_m_env > 0 ? max_m_env : ((conv_tiered || conv_tiered32 || asked) ? 16384 : 8192);
-        // n not a power of two: applying S through the grid costs six dense products per CG iteration (shm_dct_gemm.hip.h: 5 ms at n = 362), so the explicit S
-        // is worth its assembly up to the sizes its memory allows, whatever Step 1 hides
-        if (gemm_dct()) return !off && m > 0 && m <= std::max(max_m, 16384);
-        // Round 6 -- several z-slabs (ranks): S and its inverse are REPLICATED (assembled from the grid's Green's table and the global rows on every rank, beside that
-        // rank's Step 1 like the rest of the set-up), and the solve touches the grid twice -- K^+ b and K^+ (A^T mu - b) on the slabs, two all-to-alls each --
-        // with the whole dual system solved on m-vectors that every rank holds: no gather of D^T Y, no whole-grid solve per rank (solve_dual).  Wherever it fits.
-        if (total_slabs > 1) return !off && fft_available() && m > 0 && m <= 16384 && n <= 512;
-        if (off || total_slabs != 1 || !precond_available() || m <= 0 || m > max_m || n > 512) return false;
-        // the assembly (216 table entries per matrix entry: ~2.2e-7 ms per m^2 on an idle device until round 4 -- 1.8 ms at m = 2842, 29 ms at m = 12 612; 1.1 ms at m = 2842 since the
-        // windows along the last axis are fetched by two loads instead of three; the estimate below keeps the conservative constant) has to hide behind
-        // this rank's Step 1 like the rest of the set-up; where Step 1 is short (<= 128^3, or a thin slab of a multi-GPU run) the sweeps through the grid are
-        // cheap anyway (0.11 ms per iteration at 128^3) and the set-up is the critical path already
-        // (the direct dual solve replaces the inversion of G, the host's B rows and the whole iteration by the assembly and the inversion of S: a gain at
-        // every size it applies to -- 128^3: 12.1 -> 9.6 ms, 64^3: 4.5 -> 2.7 ms per solve -- so it is not subject to this test)
-        const bool force = knob("SHM_DUAL_DENSE_S_ALWAYS") != nullptr || dual_form_req == SHM_DUAL_EXPLICIT_S_CG || dual_form_req == SHM_DUAL_DIRECT;
-        const double schur_est_ms = 2.2e-7 * (double)m * (double)m;
-        if (force || dual_direct) return true;
-        // CG on the explicit S (no inversion): worth it only where an iteration through the grid costs clearly more than the dense mat-vecs -- which grows with
-        // m^2 while the sparse sweeps grow with the grid.  Measured, fp64 (round 4, tools/r04_dense_s_256.py; ms per iteration through the grid / on the explicit
-        // S): 512^3 rocker (m = 12 612) 1.37 / 0.69 -> 631 / 610 ms per solve; 256^3 rocker (9 110) 0.31 / 0.38, SprayBottle (12 620) 0.27 / 0.65, chair (6 340)
-        // 0.23 / 0.245 -> 97 / 104, 174 / 195, 58.3 / 62.5 ms per solve (the assembly also costs Step 1 4-14 ms of shared SIMD time); 128^3: a tie.  Rounds 2-3
-        // chose the explicit S for every m <= 8192 that Step 1 could hide.
-        const double dense_iter_ms = 3.6e-9 * (double)m * (double)m * (sizeof(T) / 8.0) + 0.08;
-        const double grid_iter_ms = std::max(0.15, 1.4 * std::pow((double)n / 512.0, 3.0) * (sizeof(T) / 8.0));
-        // ... and only beside the tiered fp64 Step 1: after the fp32 (or all-fp64) kernel, which leaves the set-up's kernels no room, the assembly is exposed
-        // (chair 512^3 fp32, m = 7 748: 243 ms through the grid, 253 with the explicit S and 17 ms of wait; 256^3 fp32: 38.1 / 43.5)
-        return (conv_tiered || conv_tiered32) && conv_est_total_ms >= 3.0 * schur_est_ms && grid_iter_ms > 1.3 * dense_iter_ms;
-    }
-    // The Green's table of the grid (depends on n and h alone) on `st`.  Round 4: when the number of sources already guarantees the direct dual solve (m <= S <=
-    // its limit), build_constraints() queues this BEFORE the host builds the constraint rows, so the table's kernels (0.9 ms at 256^3, 10 ms at 512^3) run while
-    // the host works (1 ms) instead of after it; otherwise prepare_schur() queues it once m is known.
-    bool green_table_early_ok() const {
-        static const bool off = knob("SHM_GREEN_LATE") != nullptr;   // A/B knob
-        static const int direct_max_m = knob("SHM_DUAL_DIRECT_MAX_M") ? atoi(knob("SHM_DUAL_DIRECT_MAX_M")) : 4096;
-        if (dual_form_req == SHM_DUAL_EXPLICIT_S_CG || dual_form_req == SHM_DUAL_THROUGH_GRID) return false;
-        return !off && dual_direct_requested && knob("SHM_DUAL_NO_DIRECT") == nullptr && knob("SHM_DUAL_NO_DENSE_S") == nullptr && (total_slabs == 1 || fft_available()) && precond_available() &&
-               !gemm_dct() && n <= 512 && S > 0 && S <= direct_max_m && (sizeof(T) == 8 || conv_tiered32 || n < 512 || knob("SHM_DUAL_DIRECT_ALWAYS") != nullptr || dual_form_req == SHM_DUAL_DIRECT);
-    }
+    // The Green's table of the grid (depends on n and h alone) on `st`: queued by build_constraints() before the rows are built where the plan says so (green_early),
+    // otherwise by prepare_schur() once m is known.
     void enqueue_green_table(hipStream_t st) {
         const int P = n + 8;   // leading dimension of the last table index (rows stay 64-byte aligned)
         const size_t n1 = (size_t)n + 1;
@@ -1870,8 +1813,8 @@ struct Solver final : SolverBase {
                     while ((1 << l2) < n) l2++;
 #define SHM_COSI_CASE(L)                                                                                                                              \
     case L:                                                                                                                                            \
-        if (xpass) hipLaunchKernelGGL((cosi_lines_kernel<L, true>), g, dim3(kBlock), 0, st, C, src, dst, tw, om, setup_prio);                         \
-        else hipLaunchKernelGGL((cosi_lines_kernel<L, false>), g, dim3(kBlock), 0, st, C, src, dst, tw, om, setup_prio);                              \
+        if (xpass) hipLaunchKernelGGL((cosi_lines_kernel<L, true>), g, dim3(kBlock), 0, st, C, src, dst, tw, om, plan.setup_prio);                         \
+        else hipLaunchKernelGGL((cosi_lines_kernel<L, false>), g, dim3(kBlock), 0, st, C, src, dst, tw, om, plan.setup_prio);                              \
         break;
                     switch (l2) {
                         SHM_COSI_CASE(4) SHM_COSI_CASE(5) SHM_COSI_CASE(6) SHM_COSI_CASE(7) SHM_COSI_CASE(8) SHM_COSI_CASE(9)
@@ -1902,16 +1845,16 @@ struct Solver final : SolverBase {
             hipLaunchKernelGGL(green_symbol_kernel, dim3((unsigned)std::min(n * n, 8 * num_cus)), dim3(kBlock), 0, st, n, gs_lam.p, W0.p);
             // beside the tiered fp64 Step 1 (two 184-register waves per SIMD) only the narrow shape fits on a SIMD; otherwise the 128 x 128 tiles
             static const bool gemm_wide_env = knob("SHM_GREEN_WIDE") != nullptr;   // A/B knob
-            const bool narrow = (conv_tiered || conv_tiered32 || knob("SHM_GREEN_NARROW") != nullptr) && !gemm_wide_env;
+            const bool narrow = (plan_in.tiered() || knob("SHM_GREEN_NARROW") != nullptr) && !gemm_wide_env;
             auto tiles = [](size_t v) { return (unsigned)((v + kGemmT - 1) / kGemmT); };
             auto gemm = [&](unsigned batches, int M, int N, int K, const double* A, int lda, long long sA, const double* B, int ldb, long long sB, double* C, int ldc, long long sC) {
                 static const int wn_env = knob("SHM_GREEN_WN") ? atoi(knob("SHM_GREEN_WN")) : 0;   // A/B knob (round 5)
                 if (narrow && wn_env == 2)
-                    hipLaunchKernelGGL(dgemm_rm_kernel<2>, dim3((unsigned)((N + 63) / 64), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, setup_prio);
+                    hipLaunchKernelGGL(dgemm_rm_kernel<2>, dim3((unsigned)((N + 63) / 64), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, plan.setup_prio);
                 else if (narrow)
-                    hipLaunchKernelGGL(dgemm_rm_kernel<1>, dim3((unsigned)((N + 31) / 32), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, setup_prio);
+                    hipLaunchKernelGGL(dgemm_rm_kernel<1>, dim3((unsigned)((N + 31) / 32), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, plan.setup_prio);
                 else
-                    hipLaunchKernelGGL(dgemm_rm_kernel<4>, dim3(tiles((size_t)N), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, setup_prio);
+                    hipLaunchKernelGGL(dgemm_rm_kernel<4>, dim3(tiles((size_t)N), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, plan.setup_prio);
             };
             // W1[(k1,k2)][d3] = sum_k3 W0[(k1,k2)][k3] Ct[k3][d3]
             gemm(1, n * n, P, n, W0.p, n, 0LL, gs_Ct.p, P, 0LL, W1.p, P, 0LL);
@@ -1927,10 +1870,10 @@ struct Solver final : SolverBase {
     void prepare_schur() {
         hipStream_t st = stream2;
         have_S = false;
-        if (!schur_wanted()) return;
+        if (!plan.explicit_S) return;
         // T is rebuilt with every solve (0.85 ms at 256^3, 10 ms at 512^3, beside Step 1: +1 % / +2.5 % of a solve), so that a timed solve contains all of
         // its own work; SHM_SCHUR_KEEP_TABLE=1 keeps it while n and h stay the same (it depends on nothing else)
-        if (!gs_early) enqueue_green_table(st);
+        if (!plan.green_early) enqueue_green_table(st);
         // rows in Morton order of their cells: the 16 x 16 tiles of the assembly then read neighbouring table entries
         std::vector<std::pair<uint64_t, int>> key((size_t)m);
         auto spread = [](uint64_t v) {
@@ -1967,18 +1910,19 @@ struct Solver final : SolverBase {
         e_sch_in->record(st);   // the tables are on the device
     }
     void enqueue_schur() {
-        if (!schur_wanted()) return;
+        if (!plan.explicit_S) return;
         // its own stream: the inversion of G on stream2 is a chain of ~135 short launches that each wait for a slot next to Step 1 (39 of Step 1's 40 ms at
         // 256^3); queued behind it the assembly would start when Step 1 is almost over and be exposed, beside it it is done long before.  (Direct dual solve:
         // there is no inversion of G; S is assembled and then inverted itself, all on stream2.)
+        const bool dual_direct = plan.dual_form == SHM_DUAL_DIRECT;
         hipStream_t st = dual_direct ? stream2 : stream3;
         HIPCHK(hipStreamWaitEvent(st, e_sch_in->e, 0));
         const int P = n + 8;
-        if (gs_early) HIPCHK(hipStreamWaitEvent(st, e_gs_done->e, 0));
+        if (plan.green_early) HIPCHK(hipStreamWaitEvent(st, e_gs_done->e, 0));
         HIPCHK(hipMemsetAsync(Sdense.p, 0, (size_t)mp * mp * sizeof(double), st));
         const unsigned mt = (unsigned)((m + 15) / 16);
         if (setup_skip() & 2) hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Sdense.p, mp, 0, m, 1.0);   // (something invertible)
-        else hipLaunchKernelGGL(schur_assemble_kernel, dim3(mt, mt), dim3(kBlock), 0, st, m, mp, n, P, d_rowX.p, d_rowT.p, gs_T.p, Sdense.p, setup_prio);
+        else hipLaunchKernelGGL(schur_assemble_kernel, dim3(mt, mt), dim3(kBlock), 0, st, m, mp, n, P, d_rowX.p, d_rowT.p, gs_T.p, Sdense.p, plan.setup_prio);
         HIPCHK(hipGetLastError());
         if (dual_direct) {
             Sinv.alloc((size_t)mp * mp);
@@ -2760,7 +2704,7 @@ struct Solver final : SolverBase {
         }
         for (Slab<T>& sl : slabs)
             hipLaunchKernelGGL(dual_init_residual_kernel, dim3(1), dim3(kDualBlock), 0, stream, m, mv(sl, V_G), sl.red.p + 1, mv(sl, V_R), sl.sc.p, 1);
-        const bool direct = dual_direct && dense_S;   // S^-1 is resident (build_constraints): no CG, no G^-1, no B
+        const bool direct = plan.dual_form == SHM_DUAL_DIRECT && dense_S;   // S^-1 is resident (build_constraints): no CG, no G^-1, no B
         if (!direct) precondition(1);
         HIPCHK(hipGetLastError());
 
@@ -2926,18 +2870,20 @@ struct Solver final : SolverBase {
     // xGMI) and every rank runs the single-GPU dual solve on the whole grid, whose constraint set-up overlapped Step 1 as usual.
     // Each rank keeps phi for its own planes.  (The dual iteration works on m-vectors and a handful of sparse transforms; it is
     // latency-bound on one GPU already, and its distributed form -- SHM_SOLVER_DUAL_SLABS -- pays two all-to-alls per iteration.)
-    void solve_gathered(const shm_opts& o, shm_stats* st, Event& e_start, Event& e_conv, Event& e_div, std::chrono::steady_clock::time_point wall0) {
+    void solve_gathered(const shm_opts& o, const PlanIn& in, shm_stats* st, Event& e_start, Event& e_conv, Event& e_div, std::chrono::steady_clock::time_point wall0) {
         Solver<T>& F = *full;
         Slab<T>& fs = F.slabs[0];
         Event c_s2a, c_s2b, e_gather, f_start, f_setup;
         c_s2a.record(F.stream2);
-        F.conv_est_total_ms = conv_est_total_ms;   // what the whole-grid solver's set-up can hide behind is this rank's share of Step 1
-        F.conv_tiered = conv_tiered || conv_tiered32;               // ... and beside WHICH Step-1 kernel it runs: the tiered one leaves room only for the narrow GEMM shape (round 4: the
-                                                   // whole-grid solver never learnt this and queued the 256-register shape, which waits for Step 1's persistent waves to end)
-        F.dual_direct_requested = true;
-        F.dual_form_req = dual_form_req;
-        F.build_constraints();
-        F.dual_direct_requested = false;  // on the whole-grid solver's set-up stream: overlaps this rank's Step-1 kernel
+        // The whole-grid solver plans its set-up with this rank's options, knobs and Step 1: what it can hide behind is this rank's share of Step 1 (in.conv_est_total_ms),
+        // and beside WHICH Step-1 kernel it runs -- the tiered one leaves room only for the narrow GEMM shape (round 4: the whole-grid solver never learnt this and queued
+        // the 256-register shape, which waits for Step 1's persistent waves to end).  Either tiered kernel counts as the fp64 one here, whatever the precision.
+        PlanIn fin = in;
+        fin.total_slabs = 1; fin.fft_available = F.fft_available(); fin.gemm_dct = F.gemm_dct();
+        fin.step1 = in.tiered() ? kStep1TieredF64 : kStep1Untiered;
+        Plan fplan;
+        fplan.path = kPathGathered; fplan.dual_requested = true;
+        F.build_constraints(fin, fplan);  // on the whole-grid solver's set-up stream: overlaps this rank's Step-1 kernel
         c_s2b.record(F.stream2);
         F.setup_precond();
         const size_t plane = (size_t)n * n;
@@ -3223,24 +3169,16 @@ struct Solver final : SolverBase {
         need_problem();
         HIPCHK(hipSetDevice(cfg.device));
         shm_opts o = o_in;
-        bool pre = false;
-        if (o.preconditioner == SHM_PRECOND_DCT) {
-            if (!precond_available()) throw Error(SHM_ERR_INVALID, "DCT preconditioner needs n = 2^k in [16,1024] and a power-of-two number of EQUAL z-slabs dividing n (shm_config.slab_plan = SHM_SLAB_PLAN_EQUAL); a single z-slab serves any n in [4,1024]");
-            pre = true;
-        } else if (o.preconditioner == SHM_PRECOND_AUTO) {
-            pre = precond_available();
-        } else if (o.preconditioner != SHM_PRECOND_NONE) {
-            throw Error(SHM_ERR_INVALID, "unknown preconditioner");
-        }
+        PlanIn in = plan_inputs(&o);   // (the options are checked here, before anything is launched)
+        const Plan p = plan_solve(in);
+        if (p.status != SHM_OK) throw Error(p.status, p.error);
+        const bool pre = p.precond;
         if (!(o.tol > 0.)) o.tol = sizeof(T) == 8 ? 1e-8 : 1e-5;
         if (o.max_iters <= 0) o.max_iters = 20 * n;
         if (o.check_every <= 0) o.check_every = pre ? 4 : 32;
 
         Event e_start, e_conv, e_div, e_setup, e_pcg, e_end, e_s2a, e_s2b;
         const auto wall0 = std::chrono::steady_clock::now();
-        if (o.dual_form < SHM_DUAL_AUTO || o.dual_form > SHM_DUAL_THROUGH_GRID) throw Error(SHM_ERR_INVALID, "unknown dual_form");
-        if (o.step1_budget != 0. && !(o.step1_budget >= 1e-12 && o.step1_budget <= 1e-3)) throw Error(SHM_ERR_INVALID, "step1_budget must lie in [1e-12, 1e-3] (0: default 1e-8)");
-        dual_form_req = o.dual_form;
         step1_budget = o.step1_budget;
         select_step1_arith(o.step1_arith);
         e_start.record(stream);
@@ -3254,38 +3192,24 @@ struct Solver final : SolverBase {
         e_conv.record(stream);
         launch_div(o.scrub_nonfinite);
         e_div.record(stream);
-        if (o.fast_integration) {
+        if (p.path == kPathFast) {
+            log("[shm] plan: fast");
             solve_fast(o, st, e_start, e_conv, e_div, wall0);
             return;
         }
-        // Several ranks.  Round 6: where S fits (S <= 16384 sources bound the rows) and the grid is one of the sizes BASELINE.json names (256^3 ... 512^3, four or more equal
-        // power-of-two slabs), AUTO takes the slab-distributed explicit-S forms of solve_dual -- S and its inverse replicated beside every rank's Step 1, K^+ on the slabs: no gather of
-        // D^T Y, no whole-grid solve per rank.  Everything else (larger constraint sets, 1024^3, odd sizes, weighted plans; SHM_SOLVER_DUAL) keeps the gathered solve.
-        // (from four ranks on: with two, each all-to-all crosses ONE xGMI link with a quarter of the grid, four times per solve, where the gather crosses it once with half --
-        // tools/scaling_model.py, link constants assumed: 115 against 107 ms at 512^3 on two ranks, 54 against 58 on four, 30 against 36 on eight)
-        const bool slab_forms_auto = full_wanted() && o.solver == SHM_SOLVER_AUTO && o.preconditioner != SHM_PRECOND_NONE && fft_available() && total_slabs >= 4 && n >= 256 && n <= 512 && S <= 16384 &&
-                                     o.dual_form != SHM_DUAL_THROUGH_GRID && knob("SHM_MULTI_GATHERED") == nullptr;
-        if (full_wanted() && !slab_forms_auto && (o.solver == SHM_SOLVER_AUTO || o.solver == SHM_SOLVER_DUAL) && o.preconditioner != SHM_PRECOND_NONE) {
+        in.step1 = step1_kernel();   // (known once Step 1 is queued)
+        in.conv_est_total_ms = conv_est_total_ms;
+        if (p.path == kPathGathered) {
             ensure_full();
-            solve_gathered(o, st, e_start, e_conv, e_div, wall0);
+            solve_gathered(o, in, st, e_start, e_conv, e_div, wall0);
             return;
         }
         static const bool setup_alone = knob("SHM_SETUP_ALONE") != nullptr;  // measurement knob: wait for Step 1 first, so that shm_stats.ms_setup is
         if (setup_alone) HIPCHK(hipStreamSynchronize(stream));                  // the set-up's time on an otherwise idle GPU (tools/scaling_model.py)
         e_s2a.record(stream2);
-        dual_direct_requested = (o.solver == SHM_SOLVER_DUAL || o.solver == SHM_SOLVER_DUAL_SLABS || (o.solver == SHM_SOLVER_AUTO && o.preconditioner != SHM_PRECOND_NONE)) && precond_available();
-        build_constraints();  // on stream2: overlaps the Step-1 kernel; returns once (A A^T)^-1 (or S^-1, for the direct dual solve) is ready
-        dual_direct_requested = false;
+        build_constraints(in, p);  // on stream2: overlaps the Step-1 kernel; returns once (A A^T)^-1 (or S^-1, for the direct dual solve) is ready
         e_s2b.record(stream2);
-        bool dual = false;
-        if (o.solver == SHM_SOLVER_DUAL || o.solver == SHM_SOLVER_DUAL_SLABS) {
-            if (!precond_available()) throw Error(SHM_ERR_INVALID, "the dual solver needs the DCT: n = 2^k in [16,1024] and a power-of-two number of EQUAL z-slabs dividing n (shm_config.slab_plan = SHM_SLAB_PLAN_EQUAL); a single z-slab serves any n in [4,1024]");
-            dual = true;
-        } else if (o.solver == SHM_SOLVER_AUTO) {
-            dual = precond_available() && o.preconditioner != SHM_PRECOND_NONE;
-        } else if (o.solver != SHM_SOLVER_PRIMAL) {
-            throw Error(SHM_ERR_INVALID, "unknown solver");
-        }
+        const bool dual = p.path == kPathDualSlabs || p.path == kPathDualLocal;
         if (pre || dual) setup_precond();
         e_setup.record(stream);
         if (dual) {
@@ -3293,7 +3217,7 @@ struct Solver final : SolverBase {
             return;
         }
 
-        if (fused_available()) {
+        if (p.path == kPathPrimalFused) {
             solve_primal_fused(o, st, pre, e_start, e_conv, e_div, e_setup, e_s2a, e_s2b, wall0);
             return;
         }
@@ -3551,7 +3475,7 @@ struct Solver final : SolverBase {
         need_problem();
         if (cfg.world != 1) throw Error(SHM_ERR_INVALID, "get_schur is a single-process test entry point");
         HIPCHK(hipSetDevice(cfg.device));
-        build_constraints();
+        build_constraints(plan_inputs(nullptr), Plan());
         *m_out = m;
         if (!have_S) throw Error(SHM_ERR_STATE, "no explicit Schur complement for this problem (several slabs, n not a power of two or > 512, or too many rows)");
         HIPCHK(hipMemcpy2DAsync(out, (size_t)m * sizeof(double), Sdense.p, (size_t)mp * sizeof(double), (size_t)m * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, stream2));
@@ -3562,7 +3486,7 @@ struct Solver final : SolverBase {
         need_problem();
         if (cfg.world != 1) throw Error(SHM_ERR_INVALID, "apply_projector is a single-process test entry point");
         HIPCHK(hipSetDevice(cfg.device));
-        build_constraints();
+        build_constraints(plan_inputs(nullptr), Plan());
         upload_owned(v, 1);
         std::vector<int> nparts(slabs.size(), 0);
         launch_projection(nparts);

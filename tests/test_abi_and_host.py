@@ -181,6 +181,16 @@ def test_fft_core_on_host(tmp_path):
         assert out.returncode == 0 and out.stdout.strip().endswith("OK"), (flags, out.stdout)
 
 
+def test_plan_on_host(tmp_path):
+    """The rules that decide what runs for a solve (csrc/shm_plan.h: path, dual form, set-up choices, option checks) are plain C++: run them on the host
+    against a table of inputs and the plans worked out by hand, with rows on both sides of every threshold."""
+    import subprocess
+    exe = str(tmp_path / "test_plan")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", os.path.join(ROOT, "tests", "native", "test_plan.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stdout
+
+
 def test_kernel_register_schedules():
     """The compiler's resource report of the library build (csrc/Makefile keeps it beside the .so).  Two things have cost measured time silently
     and are pinned here: a register spill in a transform kernel (n = 512 packed layout: 9 % of the sweep), and the fp64 Step-1 kernel falling out
