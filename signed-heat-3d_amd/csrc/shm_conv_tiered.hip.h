@@ -458,7 +458,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         // scan (clusters in storage order, a cluster's candidates together -- Y stays bit-identical from run to run), and a candidate (b_s <= tau = eps_soft / K, K a per-problem
         // estimate of the ring's population: Solver::drop_rule_plan) is dropped while R + (the cluster's candidates) <= eps_soft = 7/8 eps.  K only decides how well the budget is
         // used; the sum is what makes the rule sound.  A source with b_s <= tau_hard = (eps / 8) / S is dropped whatever R (the old rule on an eighth of the budget: it bounds how
-        // far an evaluated source can lie from the block -- the exponent span of yukawa_near -- and keeps the new rule from ever doing much worse than the old one).
+        // far an evaluated source can lie from the block -- the exponent span of yukawa_near -- and keeps the new rule from ever doing much worse than the old one).  That test
+        // reads lb = log2 b_s WITHOUT the factor r_hi / d_s, so it is a bound only where d_s >= r_hi: a source nearer to the block is never dropped by it (inside the block,
+        // d_s = 0, b_s is inf and no sum admits it either -- a weight 1e-16 of s*'s 1e-9 cells from a node is 1e-6 of the dominant term there; tests/test_step1_edges.py).
         // Whole clusters go the same way with their bounding sphere, largest weight (candidate test) and weight sum (bound).
         // fp64 solve: R enters the a-posteriori test (R |term_s*(x)| against budget |X(x)|, beside the packed-fp32 tier's L1 sums), and the second pass evaluates the dropped
         // sources too: where the sheets of the geometry cancel (|X| << dominant term) the rule of rounds 3-5 had no such guard.
@@ -553,7 +555,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         };
         // The fetch runs one KEPT cluster ahead (round 5 in the fp64 solve; the fp32 solve kept the plain order then because the scalar scan for the next kept cluster sat between
         // a cluster's fetch and its use -- with the scan a few scalar instructions on a mask, round 6, both solves look ahead).
-        R_soft = 0.f;   // (the second pass repeats the first one's scan and with it its sums and decisions)
+        // (each pass starts its sums from zero, but pass 1 does NOT repeat pass 0's decisions: its look-ahead walks every cluster, so load_batch runs at other points of the
+        // scan, R_soft accumulates in another order and a soft / hard decision can differ.  Harmless: pass 1 evaluates every valid source, the dropped ones where span_ok.)
+        R_soft = 0.f;
         R_hard = 0.f;
         bool cdrop_cur = false, cdrop_next = false;
         int c = next_kept(0, cdrop_cur);
@@ -590,7 +594,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                 const float lw = 0.5f * __log2f(w2);                                       // log2(|w_s| / w_max) <= 0 (w = 0: -inf)
                 const float rel = lw + 1e-5f - lnear_w;                                    // log2(|w_s| / |w_near|), rounded up
                 const float lhs = (dist * 0.999999f - r_hi_w) * lam_l2;                    // lower bound of lambda (r(x, s) - r_near(x)) / ln 2
-                const bool valid = w2 > 0.f;                                              // the zero-weight padding is never evaluated
+                // the zero-weight padding is never evaluated.  Read from the fp64 weight: a tiny one whose fp32 square underflows is still a source (on a node: NaN there,
+                // like the reference); lw = -inf keeps it out of the packed-fp32 tier
+                const bool valid = q[3] != 0. || q[4] != 0. || q[5] != 0.;
                 const bool in_range = fmaf(dist, lam_l2, range_c) <= lw;                   // every term of the source stays a normal fp32 number over the block
                 float lhs_far = lhs, lhs_drop = lhs;
                 {
@@ -620,7 +626,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                         if (use_diff) lhs_far = lhs_drop;
                     }
                 }
-                const bool far = lhs_far > g_l2 + rel && in_range;
+                // (fp64 solve: only sources at least r_hi from the block -- the bound leaves out the factor r_hi / d_s, and a packed-fp32 distance next to a node has no
+                // relative accuracy left, which the a-posteriori test cannot see)
+                const bool far = lhs_far > g_l2 + rel && in_range && (!CHECK || dist >= r_hi_w);
                 // the drop rule by accumulated bound (see the block's header above): candidates of this cluster together, or only the ones below the hard threshold
                 bool drop = valid && cdrop_cur;   // (pass 1 walks a cluster that pass 0 dropped as a whole)
                 if (drop_on && !cdrop_cur) {
@@ -638,8 +646,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                         if (__builtin_amdgcn_readfirstlane((int)(r_new <= P.drop_eps_soft))) {   // (inf / NaN: false)
                             R_soft = r_new;
                             drop = cand;
-                        } else {
-                            drop = cand && lb <= P.drop_ltau_hard;
+                        } else {   // (the hard threshold leaves out the factor r_hi / d_s: it bounds b_s only where d_s >= r_hi)
+                            drop = cand && lb <= P.drop_ltau_hard && dist >= r_hi_w;
                             R_hard = uniform_f32(R_hard + (float)__builtin_popcountll(__ballot(drop)) * P.drop_tau_hard);
                         }
                     }
