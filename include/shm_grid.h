@@ -253,6 +253,35 @@ shm_status shm_grid_isosurface(shm_solver* s, double isovalue, int64_t* n_vertic
 shm_status shm_grid_isosurface_ex(shm_solver* s, double isovalue, int32_t method, int64_t* n_vertices, int64_t* n_triangles);
 shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices /* [3*nv] */, int64_t* triangles /* [3*nt] */);
 
+/* --- point queries of the resident phi (the reference's SignedHeatGridSolver::evaluateFunction, signed_heat_grid_solver.cpp:405-431) --------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * Value: the reference's trilinear interpolation of the phi shm_grid_get_phi returns (the shifted phi), in its order of operations:
+ *   cell  i = floor((q - bbox_min) / cell) per axis;  weights  t = (q - p000) / cell  with  p000 = i * cell + bbox_min;
+ *   lerp along x first (v00, v01, v10, v11), then y (v0, v1), then z (v).
+ * Gradient (optional): the exact gradient of that trilinear interpolant inside the chosen cell, nested the same way:
+ *   d/dx = ((v100-v000)(1-ty) + (v110-v010) ty)(1-tz) + ((v101-v001)(1-ty) + (v111-v011) ty) tz) / cell,
+ *   d/dy = ((v10-v00)(1-tz) + (v11-v01) tz) / cell,  d/dz = (v1-v0) / cell.
+ *   It is not smoothed and is discontinuous across cell faces: the cell floor() picks decides, so a point on an interior face takes the cell above it.
+ * Box: a point with every coordinate in [bbox_min, bbox_min + (n-1)*cell] (the upper bound computed as (n-1)*cell + bbox_min, no tolerance band) is
+ *   in the box.  On an upper face of an axis it uses cell n-2 of that axis with t = 1.  Any other point, and any point with a NaN coordinate, gets NaN
+ *   for phi and for its gradient.  (The reference reads out of bounds there; wherever it is defined the arithmetic is the same.)
+ * Ownership: like shm_grid_isosurface, a process answers the points whose cell has its lower z-plane among the planes its slabs own; the cell of a
+ *   slab's top plane reads the plane above from the ghost layer (exchanged inside the call).  Every output entry is written; points this process
+ *   does not answer get NaN, and *n_answered counts the points it did answer.  Each in-box point is answered by exactly one rank: combine the ranks'
+ *   outputs with a NaN mask.  With world > 1 both calls are COLLECTIVE (the ghost exchange is): every rank calls, with its own points or Q = 0.
+ * Valid whenever shm_grid_get_phi would succeed (any solve that returned phi, SHM_ERR_NOCONV included); SHM_ERR_STATE before a solve or after a
+ *   test entry point that overwrote phi.  phi and the solver's state are left as they were; sampling twice gives bit-identical results.
+ * Precision: an SHM_F64 handle reads fp64 nodes, an SHM_F32 handle fp32 nodes; cell, weights and sums are always fp64 from the point as given
+ *   (float points are promoted first), so the fp32 handle returns the exact trilinear value of its fp32 nodes (rounded to the output type).
+ * shm_grid_sample: host buffers; pts [3Q] xyz-interleaved fp64, phi_out [Q] fp64, grad_out [3Q] fp64 or NULL.  The points stream through the
+ *   device in chunks (2^20 points) through pinned staging buffers the handle keeps, so device memory stays bounded for any Q.  Q = 0 is valid;
+ *   Q < 0, or NULL pts / phi_out with Q > 0, is SHM_ERR_INVALID.
+ * shm_grid_sample_device: device buffers of the handle's precision (float for SHM_F32, double for SHM_F64) on the handle's device, same layouts;
+ *   synchronous: the outputs are ready on return.  Each pointer is checked (hipPointerGetAttributes / hipMemGetAddressRange) before anything is
+ *   launched: host memory, another device's memory or an allocation smaller than Q points is SHM_ERR_INVALID. */
+shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered);
+shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered);
+
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */
 shm_status shm_comm_unique_id(void* out128);

@@ -211,6 +211,13 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices, int64_t* tri
     return guard(s, [&] { s->impl->get_isosurface(vertices, triangles); });
 }
 
+shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered) {
+    return guard(s, [&] { s->impl->sample(Q, pts, phi_out, grad_out, n_answered); });
+}
+shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered) {
+    return guard(s, [&] { s->impl->sample_device(Q, d_pts, d_phi, d_grad, n_answered); });
+}
+
 shm_status shm_comm_unique_id(void* out128) {
     if (!out128) return SHM_ERR_INVALID;
     try {

@@ -564,6 +564,8 @@ struct SolverBase {
     virtual void get_schur(double*, int32_t*) = 0;
     virtual void isosurface(double, int, int64_t*, int64_t*) = 0;
     virtual void get_isosurface(double*, int64_t*) = 0;
+    virtual void sample(int64_t, const double*, double*, double*, int64_t*) = 0;
+    virtual void sample_device(int64_t, const void*, void*, void*, int64_t*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

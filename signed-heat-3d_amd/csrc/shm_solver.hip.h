@@ -19,6 +19,7 @@
 #include "shm_dct.hip.h"
 #include "shm_dct_gemm.hip.h"
 #include "shm_green_fft.hip.h"
+#include "shm_sample.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -211,6 +212,8 @@ struct Solver final : SolverBase {
         (void)hipSetDevice(cfg.device);
         if (comm) (void)Rccl::get().CommDestroy(comm);
         if (h_pinned) (void)hipHostFree(h_pinned);
+        for (void* b : smp_pinned)
+            if (b) (void)hipHostFree(b);
         slabs.clear();
         if (stream) (void)hipStreamDestroy(stream);
         if (stream2) (void)hipStreamDestroy(stream2);
@@ -3555,6 +3558,131 @@ struct Solver final : SolverBase {
         }
         if (nv) *nv = (int64_t)(iso_vertices.size() / 3);
         if (nt) *nt = (int64_t)(iso_triangles.size() / 3);
+    }
+
+    // ---- point queries of the resident phi (shm_sample.hip.h) ------------------------------------------------------------------------------------------
+    static constexpr int64_t kSampleChunk = (int64_t)1 << 20;   // points per chunk of the host entry: 56 MiB of pinned staging and as much device memory (two slots)
+    DevArray<unsigned long long> d_sample_count;
+    DevArray<double> smp_dev[2];                 // per slot: points [3C], phi [C], gradient [3C]
+    void* smp_pinned[2] = {nullptr, nullptr};    // the same layout in pinned host memory
+    int64_t smp_cap = 0;
+    std::unique_ptr<Event> smp_done[2];
+
+    void sample_begin() {
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        HIPCHK(hipSetDevice(cfg.device));
+        halo_exchange(ARR_Q);  // phi lives in q; cells of the top owned plane read the plane above (collective with world > 1)
+        d_sample_count.alloc(1);
+        HIPCHK(hipMemsetAsync(d_sample_count.p, 0, sizeof(unsigned long long), stream));
+    }
+    int64_t sample_end() {
+        unsigned long long c = 0;
+        HIPCHK(hipMemcpyAsync(&c, d_sample_count.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return (int64_t)c;
+    }
+    // one launch per slab; the first also writes NaN for the points no slab of this process answers
+    template <typename TIO> void launch_sample(int64_t Q, const TIO* pts, TIO* out, TIO* grad) {
+        if (Q <= 0) return;
+        SampleParams P;
+        P.n = n;
+        P.kp0 = slabs.front().k0;
+        P.kp1 = slabs.back().k1;
+        P.cell = cell;
+        for (int a = 0; a < 3; a++) {
+            P.bbox_min[a] = bbox_min[a];
+            P.hi[a] = (n - 1) * cell + bbox_min[a];
+        }
+        const int grid = grid_for((size_t)Q, 16384);
+        for (size_t s = 0; s < slabs.size(); s++) {
+            P.k0 = slabs[s].k0;
+            P.k1 = slabs[s].k1;
+            P.nan_unowned = s == 0;
+            if (grad) hipLaunchKernelGGL((sample_kernel<T, TIO, true>), dim3(grid), dim3(kBlock), 0, stream, P, Q, pts, slabs[s].q.p, out, grad, d_sample_count.p);
+            else hipLaunchKernelGGL((sample_kernel<T, TIO, false>), dim3(grid), dim3(kBlock), 0, stream, P, Q, pts, slabs[s].q.p, out, grad, d_sample_count.p);
+        }
+        HIPCHK(hipGetLastError());
+    }
+
+    // host buffers: the points stream through two pinned staging slots, so that the host copies of one chunk overlap the device work of the other
+    void sample(int64_t Q, const double* pts, double* out, double* grad, int64_t* n_answered) override {
+        if (Q < 0) throw Error(SHM_ERR_INVALID, "sample: Q < 0");
+        if (Q > 0 && (!pts || !out)) throw Error(SHM_ERR_INVALID, "sample: null points or output");
+        sample_begin();
+        const int64_t C = std::min(Q, kSampleChunk);
+        if (C > smp_cap) {
+            for (int b = 0; b < 2; b++) {
+                if (smp_pinned[b]) HIPCHK(hipHostFree(smp_pinned[b]));
+                smp_pinned[b] = nullptr;
+                smp_dev[b].release();
+            }
+            smp_cap = 0;
+            for (int b = 0; b < 2; b++) {
+                HIPCHK(hipHostMalloc(&smp_pinned[b], (size_t)C * 7 * sizeof(double)));
+                smp_dev[b].alloc((size_t)C * 7);
+                if (!smp_done[b]) smp_done[b].reset(new Event());
+            }
+            smp_cap = C;
+        }
+        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
+        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
+            const int b = (int)(c & 1);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            HIPCHK(hipEventSynchronize(smp_done[b]->e));
+            const double* hb = (const double*)smp_pinned[b];
+            memcpy(out + q0, hb + 3 * C, (size_t)m * sizeof(double));
+            if (grad) memcpy(grad + 3 * q0, hb + 4 * C, (size_t)m * 3 * sizeof(double));
+        };
+        for (int64_t c = 0; c < nchunks; c++) {
+            const int b = (int)(c & 1);
+            if (c >= 2) finish(c - 2);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            double* hb = (double*)smp_pinned[b];
+            double* db = smp_dev[b].p;
+            memcpy(hb, pts + 3 * q0, (size_t)m * 3 * sizeof(double));
+            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+            launch_sample<double>(m, db, db + 3 * C, grad ? db + 4 * C : nullptr);
+            HIPCHK(hipMemcpyAsync(hb + 3 * C, db + 3 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (grad) HIPCHK(hipMemcpyAsync(hb + 4 * C, db + 4 * C, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipEventRecord(smp_done[b]->e, stream));
+        }
+        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        const int64_t a = sample_end();
+        if (n_answered) *n_answered = a;
+    }
+
+    // device buffers of type T, checked to lie in device memory of this handle's device and to hold Q points before anything is launched
+    void check_device_buffer(const void* p, size_t bytes, const char* what) {
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof at);
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != cfg.device)
+            throw Error(SHM_ERR_INVALID, fmt("sample_device: %s is not device memory of device %d", what, cfg.device));
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+            (void)hipGetLastError();
+            throw Error(SHM_ERR_INVALID, fmt("sample_device: %s is not a device allocation", what));
+        }
+        if ((const char*)p + bytes > (const char*)base + size) throw Error(SHM_ERR_INVALID, fmt("sample_device: %s holds fewer than the Q points asked for", what));
+    }
+    void sample_device(int64_t Q, const void* pts, void* out, void* grad, int64_t* n_answered) override {
+        if (Q < 0) throw Error(SHM_ERR_INVALID, "sample_device: Q < 0");
+        if (Q > 0 && (!pts || !out)) throw Error(SHM_ERR_INVALID, "sample_device: null points or output");
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        HIPCHK(hipSetDevice(cfg.device));
+        if (Q > 0) {
+            check_device_buffer(pts, (size_t)Q * 3 * sizeof(T), "the point buffer");
+            check_device_buffer(out, (size_t)Q * sizeof(T), "the phi buffer");
+            if (grad) check_device_buffer(grad, (size_t)Q * 3 * sizeof(T), "the gradient buffer");
+        }
+        sample_begin();
+        launch_sample<T>(Q, (const T*)pts, (T*)out, (T*)grad);
+        const int64_t a = sample_end();
+        if (n_answered) *n_answered = a;
     }
 
     void get_isosurface(double* vertices, int64_t* triangles) override {

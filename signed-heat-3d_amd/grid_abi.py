@@ -20,7 +20,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
-               "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
+               "shm_grid_sample", "shm_grid_sample_device", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
 class ShmError(RuntimeError):
@@ -100,6 +100,8 @@ def load_library():
     lib.shm_grid_isosurface.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.shm_grid_isosurface_ex.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.shm_grid_get_isosurface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.shm_grid_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.shm_grid_sample_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -169,6 +171,7 @@ class GridSolver:
             raise ShmError(rc, self._lib.shm_grid_last_error(None).decode())
         self.n = 0
         self.world, self.rank, self.local_slabs = world, rank, local_slabs
+        self.device, self.precision = device, precision
         self._keep = None
 
     def close(self):
@@ -296,6 +299,38 @@ class GridSolver:
         F = np.empty((nt.value, 3), dtype=np.int64)
         self._chk(self._lib.shm_grid_get_isosurface(self._h, V.ctypes.data, F.ctypes.data))
         return V, F
+
+    def sample(self, points, grad=False):
+        """phi of the resident (shifted) phi at points [Q, 3] by the reference's trilinear evaluateFunction (shm_grid_sample): returns (phi [Q],
+        n_answered) or, with grad=True, (phi [Q], grad [Q, 3], n_answered), float64.  NaN outside the box and at points another rank answers."""
+        pts = _f64(points).reshape(-1, 3)
+        Q = pts.shape[0]
+        phi = np.empty(Q, dtype=np.float64)
+        g = np.empty((Q, 3), dtype=np.float64) if grad else None
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_sample(self._h, Q, pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None, C.byref(na)))
+        return (phi, g, na.value) if grad else (phi, na.value)
+
+    def sample_device(self, points, grad=False):
+        """The same on device memory (shm_grid_sample_device): points is a contiguous [Q, 3] torch tensor on this handle's device with its dtype
+        (float64 for SHM_F64, float32 for SHM_F32); returns torch tensors (phi [Q], [grad [Q, 3],] n_answered) of that dtype on that device.
+        Import torch before this library is loaded: torch's HIP libraries ask for libamdhip64.so, this library for libamdhip64.so.7, and torch loaded
+        second brings its own copy of the HIP runtime, which sees no device."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("sample_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if points.dtype != dt or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise ValueError("sample_device: points must be a contiguous [Q, 3] %s tensor" % dt)
+        Q = points.shape[0]
+        phi = torch.empty(Q, dtype=dt, device=points.device)
+        g = torch.empty((Q, 3), dtype=dt, device=points.device) if grad else None
+        if points.is_cuda:
+            torch.cuda.current_stream(points.device).synchronize()   # the points may still be in flight on torch's stream
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_sample_device(self._h, Q, points.data_ptr() if Q else None, phi.data_ptr() if Q else None,
+                                                   g.data_ptr() if grad and Q else None, C.byref(na)))
+        return (phi, g, na.value) if grad else (phi, na.value)
 
     def compute_distance(self, pos, wnormal, area, lam, n, bbox_min, cell, **kw):
         """One-shot convenience mirroring shm_grid_compute_distance (set_problem + solve + get_phi)."""

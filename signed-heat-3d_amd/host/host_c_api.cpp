@@ -159,6 +159,21 @@ int shmh_compute_distance(void* hv, double tCoef, double hCoef, double scale, in
     });
 }
 
+// evaluateFunction through the C++ class: phi of the last compute_distance at pts [3Q] (xyz) -> phi_out [Q], grad_out [3Q] or NULL.
+int shmh_sample(void* hv, int64_t Q, const double* pts, double* phi_out, double* grad_out) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> q((size_t)Q);
+        for (int64_t a = 0; a < Q; a++) q[(size_t)a] = Vector3{pts[3 * a], pts[3 * a + 1], pts[3 * a + 2]};
+        std::vector<Vector3> g;
+        const std::vector<double> phi = h->solver.evaluateFunction(q, grad_out ? &g : nullptr);
+        if (Q > 0) std::memcpy(phi_out, phi.data(), phi.size() * sizeof(double));
+        if (grad_out)
+            for (int64_t a = 0; a < Q; a++)
+                for (int b = 0; b < 3; b++) grad_out[3 * a + b] = g[(size_t)a][b];
+    });
+}
+
 // Wall time of the C++ drop-in call alone -- computeDistance() returning its VectorXd, as the reference's main.cpp:90-91 consumes it --
 // without this flat wrapper's extra copy into a caller buffer (tools/pcie_inclusive.py).
 int shmh_time_compute_distance(void* hv, double tCoef, double hCoef, double scale, int rebuild, int fast, double* seconds_out, shm_stats* stats) {

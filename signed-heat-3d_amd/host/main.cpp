@@ -25,11 +25,13 @@ static void usage() {
                  "      --tol <x>         Projected-CG relative residual tolerance\n      --device <i>      HIP device ordinal\n"
                  "      --out <file>      Write phi as raw little-endian float64 (n^3 values, x fastest)\n"
                  "      --iso <value>     Contour phi at this value (default 0) and export the isosurface\n"
-                 "      --export <file>   OBJ file of the isosurface (the demo writes ../export/isosurface.obj)\n";
+                 "      --export <file>   OBJ file of the isosurface (the demo writes ../export/isosurface.obj)\n"
+                 "      --query <file>    Points to evaluate phi at: raw little-endian float64 xyz triples\n"
+                 "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n";
 }
 
 int main(int argc, char** argv) {
-    std::string path, out, exportPath;
+    std::string path, out, exportPath, queryPath, queryOut;
     double isoval = 0.;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
@@ -56,8 +58,14 @@ int main(int argc, char** argv) {
         else if (s == "--out") out = need("--out");
         else if (s == "--iso") isoval = atof(need("--iso"));
         else if (s == "--export") exportPath = need("--export");
+        else if (s == "--query") queryPath = need("--query");
+        else if (s == "--query-out") queryOut = need("--query-out");
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
         else path = s;
+    }
+    if (queryPath.empty() != queryOut.empty()) {
+        std::cerr << "--query and --query-out go together." << std::endl;
+        return EXIT_FAILURE;
     }
     if (path.empty()) {
         std::cerr << "Please specify a mesh file as argument." << std::endl;
@@ -91,6 +99,27 @@ int main(int argc, char** argv) {
             solver.isosurface(isoval, iv, jf);
             writeSurfaceMesh(iv, jf, exportPath);
             std::cerr << "Isosurface written to " << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
+        }
+        if (!queryPath.empty()) {
+            std::ifstream f(queryPath, std::ios::binary | std::ios::ate);
+            if (!f) throw std::runtime_error("cannot read " + queryPath);
+            const std::streamsize bytes = f.tellg();
+            if (bytes % (std::streamsize)(3 * sizeof(double)) != 0) throw std::runtime_error(queryPath + ": size is not a multiple of 24 bytes (float64 xyz triples)");
+            std::vector<double> raw((size_t)bytes / sizeof(double));
+            f.seekg(0);
+            f.read((char*)raw.data(), bytes);
+            std::vector<Vector3> q(raw.size() / 3);
+            for (size_t a = 0; a < q.size(); a++) q[a] = Vector3{raw[3 * a], raw[3 * a + 1], raw[3 * a + 2]};
+            std::vector<Vector3> g;
+            const std::vector<double> v = solver.evaluateFunction(q, &g);
+            std::vector<double> res(4 * q.size());
+            for (size_t a = 0; a < q.size(); a++) {
+                res[4 * a] = v[a];
+                for (int b = 0; b < 3; b++) res[4 * a + 1 + b] = g[a][b];
+            }
+            std::ofstream o(queryOut, std::ios::binary);
+            o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
+            std::cerr << "phi and its gradient at " << q.size() << " points written to " << queryOut << std::endl;
         }
     } catch (const std::exception& e) {
         std::cerr << "error: " << e.what() << std::endl;

@@ -87,6 +87,21 @@ void SignedHeatGridSolver::isosurface(double isoval, std::vector<Vector3>& verti
     for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
 }
 
+std::vector<double> SignedHeatGridSolver::evaluateFunction(const std::vector<Vector3>& q, std::vector<Vector3>* gradients) {
+    if (!handle) throw std::runtime_error("evaluateFunction: computeDistance has not been called");
+    std::vector<double> pts(3 * q.size()), phi(q.size()), g(gradients ? 3 * q.size() : 0);
+    for (size_t a = 0; a < q.size(); a++)
+        for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+    int64_t answered = 0;
+    if (shm_grid_sample(handle, (int64_t)q.size(), pts.data(), phi.data(), gradients ? g.data() : nullptr, &answered) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_sample: ") + shm_grid_last_error(handle));
+    if (gradients) {
+        gradients->resize(q.size());
+        for (size_t a = 0; a < q.size(); a++) (*gradients)[a] = Vector3{g[3 * a], g[3 * a + 1], g[3 * a + 2]};
+    }
+    return phi;
+}
+
 VectorXd SignedHeatGridSolver::computeDistance(VertexPositionGeometry& geometry, const SignedHeat3DOptions& options) {
     if (options.rebuild || !gridBuilt) {
         const Vector3 c = centroid(geometry);

@@ -40,6 +40,11 @@ class SignedHeatGridSolver {
     // cubes): isosurface of the phi of the LAST computeDistance() call, extracted on the device (marching cubes: shm_grid_isosurface).
     void isosurface(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces);
 
+    // Stands for the reference's private evaluateFunction(u, q) (signed_heat_grid_solver.cpp:405-431), here public and batched: the trilinear value of the phi of
+    // the LAST computeDistance() call at every point of q, evaluated on the device (shm_grid_sample; box, NaN and gradient rules in include/shm_grid.h).
+    // With gradients != nullptr it is resized to q.size() and receives the gradient of the trilinear interpolant in each point's cell.
+    std::vector<double> evaluateFunction(const std::vector<Vector3>& q, std::vector<Vector3>* gradients = nullptr);
+
     // Read-only views of the grid block the reference keeps private (used by the CLI / tests / the Polyscope
     // side effect `registerVolumeGrid("domain", {nx,ny,nz}, bboxMin, bboxMax)`, :35 / :143).
     size_t gridSize() const { return nx; }

@@ -37,6 +37,7 @@ def load_host_library():
     lib.shmh_preprocess.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_int64)]
     lib.shmh_compute_distance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(ShmStats)]
+    lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.argtypes = [C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.restype = None
     _LIB = lib
@@ -109,3 +110,12 @@ class HostSolver:
         st = ShmStats()
         self._chk(self._lib.shmh_compute_distance(self._h, tCoef, hCoef, scale, int(rebuild), int(fast), phi.ctypes.data, C.byref(st)))
         return phi[:self.grid_info()["n"] ** 3], st
+
+    def sample(self, points, grad=False):
+        """evaluateFunction of the C++ mirror at points [Q, 3]: the phi of the last compute_distance, trilinear (shm_grid_sample).
+        Returns phi [Q] or, with grad=True, (phi [Q], grad [Q, 3]), float64; NaN outside the box."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        phi = np.empty(pts.shape[0], dtype=np.float64)
+        g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
+        self._chk(self._lib.shmh_sample(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None))
+        return (phi, g) if grad else phi

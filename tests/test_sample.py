@@ -1,0 +1,451 @@
+"""Point queries of the resident phi (shm_grid_sample / shm_grid_sample_device, include/shm_grid.h): the reference's trilinear evaluateFunction
+(signed_heat_grid_solver.cpp:405-431) and the gradient of that interpolant, through the kernel, the C ABI, the Python bindings, the C++ host mirror
+and the CLI.  The numpy restatement below is held to the C oracle on the host; the GPU tests hold the library to the restatement."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+# torch's HIP libraries ask for the HIP runtime as libamdhip64.so, libshm_grid.so as libamdhip64.so.7: loaded after the library, torch would bring a second
+# runtime into the process that sees no device.  Importing torch first (at collection, before any test loads the library) makes both share torch's.
+try:
+    import torch  # noqa: F401
+except ImportError:
+    torch = None
+
+from conftest import ROOT, c_, load_golden
+
+
+# ---- the numpy restatement of evaluateFunction and its gradient, with the box rules of include/shm_grid.h -------------------------------------------------
+def eval_ref(phi, n, bbox_min, cell, pts, grad=False):
+    """phi: n^3 values (x fastest).  Value, and the exact gradient of the trilinear interpolant in the cell floor() picks; cell n-2 with t = 1 on an upper
+    face; NaN outside [bbox_min, (n-1)*cell + bbox_min] on any axis and for NaN coordinates."""
+    u = np.asarray(phi, dtype=np.float64).reshape(n, n, n)   # [k, j, i]
+    pts = np.asarray(pts, dtype=np.float64).reshape(-1, 3)
+    b = np.asarray(bbox_min, dtype=np.float64)
+    hi = (n - 1) * cell + b
+    with np.errstate(invalid="ignore"):
+        inside = np.all((pts >= b) & (pts <= hi), axis=1)
+    v = np.full(len(pts), np.nan)
+    g = np.full((len(pts), 3), np.nan)
+    p = pts[inside]
+    idx = np.floor((p - b) / cell).astype(np.int64)
+    top = idx > n - 2
+    idx = np.minimum(idx, n - 2)
+    t = (p - (idx * cell + b)) / cell
+    t[top] = 1.0
+    i, j, k = idx[:, 0], idx[:, 1], idx[:, 2]
+    tx, ty, tz = t[:, 0], t[:, 1], t[:, 2]
+    v000, v100, v010, v110 = u[k, j, i], u[k, j, i + 1], u[k, j + 1, i], u[k, j + 1, i + 1]
+    v001, v101, v011, v111 = u[k + 1, j, i], u[k + 1, j, i + 1], u[k + 1, j + 1, i], u[k + 1, j + 1, i + 1]
+    v00 = v000 * (1. - tx) + v100 * tx
+    v01 = v001 * (1. - tx) + v101 * tx
+    v10 = v010 * (1. - tx) + v110 * tx
+    v11 = v011 * (1. - tx) + v111 * tx
+    v0 = v00 * (1. - ty) + v10 * ty
+    v1 = v01 * (1. - ty) + v11 * ty
+    v[inside] = v0 * (1. - tz) + v1 * tz
+    if not grad:
+        return v
+    d0 = (v100 - v000) * (1. - ty) + (v110 - v010) * ty
+    d1 = (v101 - v001) * (1. - ty) + (v111 - v011) * ty
+    g[inside, 0] = (d0 * (1. - tz) + d1 * tz) / cell
+    g[inside, 1] = ((v10 - v00) * (1. - tz) + (v11 - v01) * tz) / cell
+    g[inside, 2] = (v1 - v0) / cell
+    return v, g
+
+
+def _grid(rng, n):
+    return rng.uniform(-2, 1, 3), rng.uniform(0.05, 0.5)
+
+
+# ---- CPU ------------------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n", [4, 11, 16])
+def test_restatement_matches_the_oracle(oracle_c, n):
+    """The restatement equals the C oracle's evaluateFunction (shmo_source_average with one source of unit area at the query point) bit for bit, at
+    random points and at nodes, wherever the oracle is defined (cell index at most n-2 on every axis)."""
+    rng = np.random.default_rng(100 + n)
+    b, h = _grid(rng, n)
+    u = rng.standard_normal(n ** 3)
+    pts = b + rng.uniform(0, (n - 1) * h * (1 - 1e-9), (400, 3))
+    nodes = rng.integers(0, n - 1, (100, 3)) * h + b
+    pts = np.concatenate([pts, nodes])
+    ref = eval_ref(u, n, b, h, pts)
+    idx = np.floor((pts - b) / h)
+    assert idx.max() <= n - 2 and idx.min() >= 0
+    one = np.ones(1)
+    for q, r in zip(pts, ref):
+        o = oracle_c.shmo_source_average(n, c_(b), h, c_(u), 1, c_(q), one)
+        assert o == r, (q, o, r)
+
+
+def test_restatement_gradient_is_the_interpolants():
+    """Inside a cell the gradient is the derivative of the interpolated value: central differences of the restatement agree, and the gradient of a
+    linear field is its slope everywhere, faces and nodes included."""
+    rng = np.random.default_rng(7)
+    n = 11
+    b, h = _grid(rng, n)
+    u = rng.standard_normal(n ** 3)
+    cells = rng.integers(0, n - 1, (300, 3))
+    pts = b + (cells + rng.uniform(0.1, 0.9, (300, 3))) * h
+    v, g = eval_ref(u, n, b, h, pts, grad=True)
+    eps = 1e-6 * h
+    for a in range(3):
+        e = np.zeros(3)
+        e[a] = eps
+        fd = (eval_ref(u, n, b, h, pts + e) - eval_ref(u, n, b, h, pts - e)) / (2 * eps)
+        assert np.abs(fd - g[:, a]).max() < 1e-6 * np.abs(g).max()
+    slope = np.array([0.3, -1.7, 2.2])
+    node = b + np.stack(np.meshgrid(*[np.arange(n)] * 3, indexing="ij")[::-1], -1).reshape(-1, 3) * h
+    lin = node @ slope
+    q = np.concatenate([pts, node[rng.integers(0, n ** 3, 200)], b + (n - 1) * h * np.ones((1, 3))])
+    _, gl = eval_ref(lin, n, b, h, q, grad=True)
+    assert np.abs(gl - slope).max() < 1e-9
+
+
+def test_restatement_box_rules():
+    """Upper faces use cell n-2 with t = 1 (so a node on an upper face returns its own value); anything outside the closed box, or NaN, is NaN."""
+    rng = np.random.default_rng(3)
+    n = 9
+    b, h = _grid(rng, n)
+    u = rng.standard_normal(n ** 3)
+    U = u.reshape(n, n, n)
+    hi = (n - 1) * h + b
+    ijk = rng.integers(0, n, (200, 3))
+    ijk[:60, 0] = n - 1
+    ijk[60:120, 1] = n - 1
+    ijk[120:180, 2] = n - 1
+    pts = ijk * h + b
+    v = eval_ref(u, n, b, h, pts)
+    assert np.array_equal(v, U[ijk[:, 2], ijk[:, 1], ijk[:, 0]])
+    assert eval_ref(u, n, b, h, hi[None])[0] == U[-1, -1, -1]
+    out = []
+    for a in range(3):
+        for side in (np.nextafter(b[a], -np.inf), np.nextafter(hi[a], np.inf)):
+            q = (b + hi) / 2
+            q[a] = side
+            out.append(q.copy())
+    out += [np.array([np.nan, b[1], b[2]]), np.array([b[0], b[1], np.inf])]
+    v, g = eval_ref(u, n, b, h, np.array(out), grad=True)
+    assert np.isnan(v).all() and np.isnan(g).all()
+    v = eval_ref(u, n, b, h, np.array([b, hi]))
+    assert np.isfinite(v).all()
+
+
+def test_sample_entry_points_are_exported(shm):
+    lib = shm.load_library()
+    from signed_heat_3d_amd.grid_abi import ABI_SYMBOLS
+    header = open(os.path.join(ROOT, "include", "shm_grid.h")).read()
+    for name in ("shm_grid_sample", "shm_grid_sample_device"):
+        assert name in ABI_SYMBOLS and hasattr(lib, name) and (name + "(") in header
+    assert lib.shm_grid_abi_version() == 5
+
+
+def test_cli_help_lists_the_query_flags():
+    exe = os.path.join(ROOT, "signed-heat-3d_amd", "bin", "shm_grid_cli")
+    p = subprocess.run([exe, "--help"], capture_output=True, text=True)
+    assert p.returncode == 0 and "--query <file>" in p.stdout and "--query-out <file>" in p.stdout
+
+
+# ---- GPU ------------------------------------------------------------------------------------------------------------------------------------------------------
+def _problem(size):
+    if size == 32:
+        d = load_golden("bunny_small_n32")
+        return dict(pos=d["pos"], wnormal=d["wnormal"], area=d["area"], lam=float(d["lam"]), n=int(d["n"]), bbox_min=d["bbox_min"], cell=float(d["cell"]))
+    from signed_heat_3d_amd.host_abi import HostSolver
+    pre = HostSolver(os.path.join(ROOT, "data", "bunny_small.obj")).preprocess(hCoef=3.0)
+    assert pre["n"] == 128
+    return dict(pos=pre["pos"], wnormal=pre["wnormal"], area=pre["area"], lam=pre["lam"], n=pre["n"], bbox_min=pre["bbox_min"], cell=pre["cell"])
+
+
+def _solved(shm, d, precision=64, **kw):
+    s = shm.GridSolver(precision=precision, **kw)
+    s.set_problem(d["pos"], d["wnormal"], d["area"], d["lam"], d["n"], d["bbox_min"], d["cell"])
+    s.solve(tol=1e-10 if precision == 64 else 0.0)
+    return s
+
+
+def _points(d, Q=100000, seed=0):
+    """Uniform points, source positions plus a small jitter, exact node positions, the six faces and the upper corner."""
+    rng = np.random.default_rng(seed)
+    n, b, h = d["n"], np.asarray(d["bbox_min"]), d["cell"]
+    hi = (n - 1) * h + b
+    q4 = Q // 4
+    uni = rng.uniform(b, hi, (q4, 3))
+    src = d["pos"][rng.integers(0, len(d["pos"]), q4)] + rng.normal(0, 0.2 * h, (q4, 3))
+    nodes = rng.integers(0, n, (q4, 3)) * h + b
+    faces = rng.uniform(b, hi, (Q - 3 * q4 - 1, 3))
+    ax = rng.integers(0, 3, len(faces))
+    up = rng.integers(0, 2, len(faces)).astype(bool)
+    faces[np.arange(len(faces)), ax] = np.where(up, hi[ax], b[ax])
+    return np.concatenate([uni, src, nodes, faces, hi[None]])
+
+
+_CACHE = {}
+
+
+def _case(shm, size, precision):
+    key = (size, precision)
+    if key not in _CACHE:
+        d = _problem(size)
+        s = _solved(shm, d, precision)
+        _CACHE[key] = (d, s, s.get_phi()[0])
+    return _CACHE[key]
+
+
+def _close(a, b, scale, rel=1e-13):
+    assert np.array_equal(np.isnan(a), np.isnan(b))
+    m = ~np.isnan(a)
+    err = np.abs(a[m] - b[m]).max() if m.any() else 0.
+    assert err <= rel * scale, (err, rel * scale)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", [64, 32])
+@pytest.mark.parametrize("size", [32, 128])
+def test_sample_matches_the_restatement(shm, size, precision):
+    d, s, phi = _case(shm, size, precision)
+    pts = _points(d, seed=size + precision)
+    v, g, na = s.sample(pts, grad=True)
+    rv, rg = eval_ref(phi, d["n"], d["bbox_min"], d["cell"], pts, grad=True)
+    scale = np.abs(phi).max()
+    assert na == len(pts)
+    _close(v, rv, scale)
+    _close(g, rg, scale)
+    v2, na2 = s.sample(pts)   # without the gradient: the same values
+    assert na2 == na and np.array_equal(v2, v)
+
+
+@pytest.mark.gpu
+def test_sample_outside_points_are_nan(shm):
+    d, s, phi = _case(shm, 32, 64)
+    n, b, h = d["n"], np.asarray(d["bbox_min"]), d["cell"]
+    hi = (n - 1) * h + b
+    rng = np.random.default_rng(11)
+    inside = rng.uniform(b, hi, (500, 3))
+    out = rng.uniform(b, hi, (600, 3))
+    a = np.arange(600) % 3
+    out[np.arange(600), a] = np.where(np.arange(600) % 2, np.nextafter(hi[a], np.inf) + rng.uniform(0, 3, 600) * h,
+                                      np.nextafter(b[a], -np.inf) - rng.uniform(0, 3, 600) * h)
+    bad = rng.uniform(b, hi, (30, 3))
+    bad[:10, 0] = np.nan
+    bad[10:20, 1] = np.inf
+    bad[20:, 2] = -np.inf
+    pts = np.concatenate([inside, out, bad])[rng.permutation(1130)]
+    v, g, na = s.sample(pts, grad=True)
+    rv, rg = eval_ref(phi, n, b, h, pts, grad=True)
+    assert na == 500 and np.isnan(v).sum() == 630 and np.isnan(g).any(axis=1).sum() == 630
+    _close(v, rv, np.abs(phi).max())
+    _close(g, rg, np.abs(phi).max())
+    v0, na0 = s.sample(np.zeros((0, 3)))
+    assert na0 == 0 and v0.shape == (0,)
+
+
+@pytest.mark.gpu
+def test_sample_at_the_sources_averages_to_zero(shm):
+    """The shift makes the area-weighted mean of phi over the sources zero (signed_heat_grid_solver.cpp:110-111): the sample there agrees."""
+    d, s, phi = _case(shm, 128, 64)
+    v, na = s.sample(d["pos"])
+    assert na == len(d["pos"])
+    mean = np.sum(d["area"] * v) / np.sum(d["area"])
+    assert abs(mean) <= 1e-10 * np.abs(phi).max(), mean
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("slabs,plan", [(2, 0), (3, 0), (3, 1)])
+def test_sample_on_slabs(shm, slabs, plan):
+    d, s1, phi1 = _case(shm, 32, 64)
+    s = _solved(shm, d, 64, local_slabs=slabs, slab_plan=plan)
+    phi, (k0, k1) = s.get_phi()
+    assert (k0, k1) == (0, d["n"])
+    n, b, h = d["n"], np.asarray(d["bbox_min"]), d["cell"]
+    pts = _points(d, Q=20000, seed=slabs + 10 * plan)
+    # points exactly on every slab boundary plane (and on the planes just below, whose cells read the ghost plane)
+    rng = np.random.default_rng(5)
+    if plan == 0:
+        bounds = [shm.plan_slab(n, slabs, sl)[0] for sl in range(slabs)]
+    else:
+        w = shm.step1_plane_weights(d["pos"], d["wnormal"], d["lam"], n, b, h, 64)
+        bounds = [shm.plan_slab_weighted(n, slabs, sl, w, 4)[0] for sl in range(slabs)]
+    extra = []
+    for kb in bounds[1:]:
+        for kk in (kb, kb - 1):
+            q = rng.uniform(b, (n - 1) * h + b, (200, 3))
+            q[:, 2] = kk * h + b[2]
+            extra.append(q)
+    pts = np.concatenate([pts] + extra)
+    v, g, na = s.sample(pts, grad=True)
+    assert na == len(pts) and not np.isnan(v).any()
+    rv, rg = eval_ref(phi, n, b, h, pts, grad=True)
+    scale = np.abs(phi).max()
+    _close(v, rv, scale)
+    _close(g, rg, scale)
+    # against the single-slab handle: equal up to what the two solves' phi differ by
+    v1 = s1.sample(pts)[0]
+    dphi = np.abs(phi - phi1).max()
+    assert np.abs(v - v1).max() <= 1e-13 * scale + dphi
+
+
+@pytest.mark.gpu
+def test_sample_two_ranks(shm, tmp_path):
+    """world = 2 on one GPU through the shared-memory double of librccl, both ranks as threads of one worker process: every in-box point is answered
+    by exactly one rank, and the NaN-mask union of the two equals the restatement on the whole phi, and the world-1 handle."""
+    so = str(tmp_path / "librccl_mock.so")
+    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", os.path.join(ROOT, "tests", "native", "rccl_mock.c"), "-o", so, "-I/opt/rocm/include",
+                           "-D__HIP_PLATFORM_AMD__", "-L/opt/rocm/lib", "-lamdhip64", "-lrt", "-lpthread"])
+    d, s1, phi1 = _case(shm, 32, 64)
+    n, b, h = d["n"], np.asarray(d["bbox_min"]), d["cell"]
+    pts = _points(d, Q=20000, seed=2)
+    rng = np.random.default_rng(9)
+    outside = rng.uniform(b - 2 * h, b - h, (100, 3))
+    pts = np.concatenate([pts, outside])
+    np.save(tmp_path / "pts.npy", pts)
+    uid = ("/shmmock_%d_sample_2" % os.getpid()).encode().ljust(128, b"\x00")
+    log = open(tmp_path / "worker.log", "w+")
+    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "tests", "sample_worker.py"), "2", uid.hex(), "bunny_small_n32", str(tmp_path / "pts.npy"),
+                          str(tmp_path)], env=dict(os.environ, SHM_RCCL_LIB=so), stdout=log, stderr=subprocess.STDOUT)
+    try:
+        p.wait(timeout=300)
+    except subprocess.TimeoutExpired:
+        p.kill()
+        p.wait()
+    log.seek(0)
+    assert p.returncode == 0, log.read()
+    phis, vs, gs, nas = [], [], [], []
+    for r in range(2):
+        k0, k1, na = np.load(tmp_path / ("meta_%d.npy" % r))
+        phis.append(np.load(tmp_path / ("phi_%d.npy" % r)))
+        vs.append(np.load(tmp_path / ("sample_%d.npy" % r)))
+        gs.append(np.load(tmp_path / ("grad_%d.npy" % r)))
+        nas.append(int(na))
+    phi = np.concatenate(phis)
+    assert phi.size == n ** 3
+    m0, m1 = ~np.isnan(vs[0]), ~np.isnan(vs[1])
+    assert not (m0 & m1).any()
+    assert nas[0] == m0.sum() and nas[1] == m1.sum() and nas[0] + nas[1] == len(pts) - 100 and nas[0] > 0 and nas[1] > 0
+    v = np.where(m0, vs[0], vs[1])
+    g = np.where(m0[:, None], gs[0], gs[1])
+    rv, rg = eval_ref(phi, n, b, h, pts, grad=True)
+    scale = np.abs(phi).max()
+    _close(v, rv, scale)
+    _close(g, rg, scale)
+    v1 = s1.sample(pts)[0]
+    assert np.array_equal(np.isnan(v), np.isnan(v1))
+    m = ~np.isnan(v)
+    assert np.abs(v[m] - v1[m]).max() <= 1e-13 * scale + np.abs(phi - phi1).max()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", [64, 32])
+def test_sample_device_equals_the_host_path(shm, precision):
+    d, s, phi = _case(shm, 128, precision)
+    pts = _points(d, seed=21)
+    pts = np.concatenate([pts, np.array([[np.nan, 0., 0.], [1e9, 0., 0.]])])
+    dt = np.float64 if precision == 64 else np.float32
+    pio = pts.astype(dt)
+    t = torch.from_numpy(pio).to("cuda:0")
+    tv, tg, tna = s.sample_device(t, grad=True)
+    hv, hg, hna = s.sample(pio.astype(np.float64), grad=True)
+    assert tv.dtype == t.dtype and tv.device == t.device and tg.shape == (len(pts), 3)
+    # (fp32 points on an upper face or node can round out of the box: count what the restatement finds inside)
+    assert tna == hna == np.count_nonzero(~np.isnan(eval_ref(phi, d["n"], d["bbox_min"], d["cell"], pio.astype(np.float64)))) >= len(pts) // 2
+    assert np.array_equal(tv.cpu().numpy(), hv.astype(dt), equal_nan=True)
+    assert np.array_equal(tg.cpu().numpy(), hg.astype(dt), equal_nan=True)
+    tv2, tna2 = s.sample_device(t)
+    assert tna2 == tna and np.array_equal(tv2.cpu().numpy(), tv.cpu().numpy(), equal_nan=True)
+    # host memory handed to the device entry point is refused before anything is launched; the handle goes on working
+    out = np.empty(len(pts), dtype=dt)
+    na = C.c_int64()
+    rc = s._lib.shm_grid_sample_device(s._h, len(pts), pio.ctypes.data, out.ctypes.data, None, C.byref(na))
+    assert rc == 1 and b"device memory" in s._lib.shm_grid_last_error(s._h)
+    # a Q beyond the allocation holding the points is refused too (the check bounds by the allocation: a caching allocator's segment may be larger than the tensor)
+    rc = s._lib.shm_grid_sample_device(s._h, 1 << 40, t.data_ptr(), tv.data_ptr(), None, C.byref(na))
+    assert rc == 1
+    assert np.array_equal(s.sample(pio.astype(np.float64))[0], hv, equal_nan=True)
+
+
+@pytest.mark.gpu
+def test_sample_state_rules(shm):
+    d = _problem(32)
+    s = shm.GridSolver()
+    with pytest.raises(shm.ShmError) as e:
+        s.sample(np.zeros((1, 3)))
+    assert e.value.status == 7
+    s.set_problem(d["pos"], d["wnormal"], d["area"], d["lam"], d["n"], d["bbox_min"], d["cell"])
+    with pytest.raises(shm.ShmError) as e:
+        s.sample(np.zeros((1, 3)))
+    assert e.value.status == 7
+    st = s.solve(fast=True)
+    phi = s.get_phi()[0]
+    pts = _points(d, Q=20000, seed=4)
+    v, g, na = s.sample(pts, grad=True)
+    rv, rg = eval_ref(phi, d["n"], d["bbox_min"], d["cell"], pts, grad=True)
+    _close(v, rv, np.abs(phi).max())
+    _close(g, rg, np.abs(phi).max())
+    v2, g2, na2 = s.sample(pts, grad=True)
+    assert na2 == na and np.array_equal(v2, v) and np.array_equal(g2, g)
+    assert np.array_equal(s.get_phi()[0], phi)
+    # a test entry point that overwrites phi ends the sampling, as it ends get_phi
+    s.apply_laplacian(np.zeros(d["n"] ** 3))
+    with pytest.raises(shm.ShmError) as e:
+        s.sample(pts[:10])
+    assert e.value.status == 7
+    na = C.c_int64()
+    assert s._lib.shm_grid_sample(s._h, -1, None, None, None, C.byref(na)) == 1          # Q < 0
+    assert s._lib.shm_grid_sample(s._h, 3, None, None, None, C.byref(na)) == 1           # NULL points with Q > 0
+    assert st.iters >= 0
+
+
+@pytest.mark.gpu
+def test_sample_gradient_on_a_real_field(shm):
+    """Away from the sources |grad phi| is about 1 and |phi| grows away from the nearest source: catches sign and scale mistakes the restatement would
+    share with the kernel."""
+    d, s, phi = _case(shm, 128, 64)
+    n, b, h = d["n"], np.asarray(d["bbox_min"]), d["cell"]
+    rng = np.random.default_rng(17)
+    cand = rng.uniform(b, (n - 1) * h + b, (60000, 3))
+    src = d["pos"]
+    dist = np.empty(len(cand))
+    near = np.empty(len(cand), dtype=np.int64)
+    for a in range(0, len(cand), 2000):
+        dd = ((cand[a:a + 2000, None, :] - src[None]) ** 2).sum(-1)
+        near[a:a + 2000] = dd.argmin(1)
+        dist[a:a + 2000] = np.sqrt(dd.min(1))
+    keep = (dist >= 3 * h) & (dist <= 10 * h)
+    q, c = cand[keep], src[near[keep]]
+    assert len(q) > 1000
+    v, g, na = s.sample(q, grad=True)
+    assert na == len(q)
+    mag = np.linalg.norm(g, axis=1)
+    assert 0.9 <= np.median(mag) <= 1.1, np.median(mag)
+    # phi < 0 inside: there the gradient points towards the surface, so it is sign(phi) grad phi that points away from it
+    away = np.sign(v) * np.einsum("ij,ij->i", g, q - c) > 0
+    assert away.mean() >= 0.95, away.mean()
+
+
+@pytest.mark.gpu
+def test_cli_query_matches_the_host_solver(shm, tmp_path):
+    from signed_heat_3d_amd.host_abi import HostSolver
+    host = HostSolver(os.path.join(ROOT, "data", "bunny_small.obj"))
+    phi, _ = host.compute_distance(hCoef=2.0)
+    n = host.grid_info()["n"]
+    gi = host.grid_info()
+    d = dict(n=n, bbox_min=gi["bbox_min"], cell=gi["cell"], pos=host.preprocess(hCoef=2.0)["pos"])
+    pts = np.concatenate([_points(d, Q=4000, seed=8), gi["bbox_min"][None] - 1.0])
+    pts.astype("<f8").tofile(tmp_path / "q.f64")
+    exe = os.path.join(ROOT, "signed-heat-3d_amd", "bin", "shm_grid_cli")
+    p = subprocess.run([exe, os.path.join(ROOT, "data", "bunny_small.obj"), "--h", "2", "--query", str(tmp_path / "q.f64"), "--query-out",
+                        str(tmp_path / "r.f64")], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    r = np.fromfile(tmp_path / "r.f64", dtype="<f8").reshape(-1, 4)
+    v, g = host.sample(pts, grad=True)
+    assert r.shape == (len(pts), 4) and np.isnan(r[-1]).all()
+    scale = np.abs(phi).max()
+    _close(r[:, 0], v, scale)
+    _close(r[:, 1:], g, scale)
+    rv, rg = eval_ref(phi, n, gi["bbox_min"], gi["cell"], pts, grad=True)
+    _close(v, rv, scale)
+    _close(g, rg, scale)
