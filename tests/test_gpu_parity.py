@@ -540,7 +540,8 @@ def test_constraint_rows_bit_exact(shm, case):
 
 @pytest.mark.parametrize("case", ["bunny_small_n16", "bunny_small_n32"])
 def test_projector(shm, case):
-    """P = I - A^T (A A^T)^-1 A: idempotent, annihilates range(A^T), A P v = 0."""
+    """P = I - A^T (A A^T)^-1 A: idempotent, annihilates range(A^T), A P v = 0.  These three properties also hold for P = 0: the comparison of P v with
+    v - A^T (A A^T)^-1 A v formed on the host, in both precisions, lives in tests/test_stage_edges.py (test_projector_matches_the_host_projector)."""
     d = load_golden(case)
     s = make_solver(shm, d)
     n = int(d["n"])
