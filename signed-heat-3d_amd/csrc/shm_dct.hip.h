@@ -66,7 +66,7 @@
 
 namespace shm {
 
-#if defined(SHM_EXPERIMENT_KNOBS) || SHM_DCT_RUNTIME_GATE
+#if SHM_DCT_RUNTIME_GATE
 #define SHM_DCT_DBG(P, bit) ((P).debug_skip & (bit))
 #else
 #define SHM_DCT_DBG(P, bit) 0
@@ -98,8 +98,8 @@ struct DctAddr {
 struct DctParams {
     int ntiles;             // tiles of this sweep; the workgroups stride over them (persistent: a workgroup costs more to start than a tile to set up)
     int tiles_a;
-    int debug_skip;         // always 0 in product builds (see SHM_DCT_RUNTIME_GATE); -DSHM_EXPERIMENT_KNOBS builds take it from env SHM_DCT_SKIP for
-                            // timing experiments: 1 = no FFT passes, 2 = no spectral step, 4 = no global loads, 8 = no global stores
+    int debug_skip;         // always 0: what makes the phase conditions opaque to the compiler (see SHM_DCT_RUNTIME_GATE).  Bits: 1 = no FFT passes, 2 = no spectral
+                            // step, 4 = no global loads, 8 = no global stores
     DctAddr in, out;
     // FUSED only: spectral coordinates of line l of tile t: kx = (t % tiles_a)*16 + l ; ky = ky0 + t / tiles_a
     int ky0;
@@ -218,7 +218,7 @@ template <int LOG2N, int CPLX_BYTES> constexpr int dct_waves_per_simd() {
 // cannot write).  One more LDS pass per tile (1/7 of the fused sweep's), 2 x the tile in LDS (73.5 KB at n = 512 fp64: two workgroups per CU, each with a tile in flight
 // all the time).  Dense sweeps only (no tile list, no element mask, plain layout, unit stride between the lines of a y / z tile).
 // MEASURED SLOWER (profiles/r06_dct_dma_rejected.txt: 512^3 fp64 0.46 -> 0.43 of the HBM peak, fp32 0.44 -> 0.36): the sweeps are bound by their LDS passes and barriers at the
-// occupancy the LDS allows, not by bytes in flight.  Kept as a verified A/B variant (-DSHM_DCT_PF), not shipped.
+// occupancy the LDS allows, not by bytes in flight.  No launcher instantiates PF = true (launch_dct_pf).
 template <typename TP, typename TIn, typename TOut, int MODE, bool DOT, int LOG2N, bool XPASS, bool SEG, bool PF = false>
 __global__ __launch_bounds__(kBlock, ((LOG2N >= SHM_DCT_WAVES_HINT || SHM_DCT_WAVES_256 > 0) && !(SHM_DCT_SEG9_ONE_WAVE && SEG && LOG2N == 9 && sizeof(TP) == 8) ? dct_waves_per_simd<LOG2N, (int)sizeof(Cplx<TP>)>() : 1)) void dct_lines_kernel(DctParams P, const TIn* __restrict__ in, TOut* __restrict__ out,
                                                            const Cplx<TP>* __restrict__ tw_g, const Cplx<TP>* __restrict__ om_g,

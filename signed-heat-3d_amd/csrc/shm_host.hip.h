@@ -280,7 +280,7 @@ static double drop_rule_K(int64_t S, const double* wn, double lambda) {
 }
 
 // K of the drop rule chosen per problem on a sample of blocks (round 6, late): the formula above is within a factor of three of the best K and that factor is worth 3 % of Step 1
-// on the culled configurations (measured, SHM_CONV_DROP_K: rocker 512^3 fp32 254 ms at K = 350 against 262 at the formula's 1066; SprayBottle.pc 512^3 fp32 283 at 700 ... 1400
+// on the culled configurations (measured with K set by hand: rocker 512^3 fp32 254 ms at K = 350 against 262 at the formula's 1066; SprayBottle.pc 512^3 fp32 283 at 700 ... 1400
 // against 307 at 350).  The host walks up to 48 blocks spread over the grid through the kernel's own scan -- clusters in storage order, 64 at a time, then the sources of the kept
 // ones, candidates of a batch / cluster together or only the ones below the hard threshold -- for a ladder of K and keeps the K that drops most.  Deterministic (every rank
 // derives the same K from the same sources); (samples x sources) <= 1.5e6: a few ms, only for S >= 4096.  src6: the sources as the kernel gets them (Morton order, grid-centred

@@ -98,7 +98,7 @@ struct Solver final : SolverBase {
     int n_clusters = 0;
     int conv_grid_cap = 1 << 30;
     bool o_fast_hint = false;  // the running solve is a fast-integration one: no constraint set-up beside Step 1
-    int num_cus = 256, dct_grid_x16 = 16;
+    int num_cus = 256;
     DevArray<T> d_src;          // [Spad][6] Morton-sorted, padded to whole clusters
     DevArray<float> d_src32;    // same in fp32 (far clusters of the fp64 path)
     DevArray<float> d_clusters; // [n_clusters][4] bounding spheres
@@ -160,8 +160,6 @@ struct Solver final : SolverBase {
     PlanIn plan_in;   // the inputs and the plan of the set-up in progress (shm_plan.h): given to build_constraints(), read by the stages after it
     Plan plan;
     double conv_est_total_ms = 1e30;   // estimate of this rank's last Step-1 launch (1e30: none was launched -- stand-alone set-up, test entry points)
-    int gs_n = 0;   // grid the Green's table in gs_T was built for (0: none)
-    double gs_cell = 0.;
     int log2n = 0;
     bool precond_ready = false;
     double* h_pinned = nullptr;
@@ -185,12 +183,8 @@ struct Solver final : SolverBase {
         {
             hipDeviceProp_t prop;
             HIPCHK(hipGetDeviceProperties(&prop, cfg.device));
-            const char* e = knob("SHM_CONV_SLOTS_PER_CU_X16");  // tuning knob: conv workgroups per CU, in 1/16ths (default 64 = 4, the LDS-limited residency: one persistent wave of workgroups)
-            const int x16 = e ? atoi(e) : 64;
-            conv_grid_cap = std::max(1, prop.multiProcessorCount * x16 / 16);
+            conv_grid_cap = std::max(1, prop.multiProcessorCount * 4);  // conv workgroups: 4 per CU, the LDS-limited residency (one persistent wave of workgroups)
             num_cus = prop.multiProcessorCount;
-            const char* d = knob("SHM_DCT_GRID_X16");  // tuning knob: DCT workgroups per resident slot, in 1/16ths (16 = one persistent wave of workgroups)
-            dct_grid_x16 = d ? std::max(1, atoi(d)) : (1 << 20);
         }
         {   // the set-up stream outranks the main stream so that its short kernels are not starved by the Step-1 kernel
             int least = 0, greatest = 0;
@@ -363,8 +357,7 @@ struct Solver final : SolverBase {
             // far when lambda * (d_lo - r_hi) > 25 + ln(Amax/Amin): the cluster's terms are below e^-25 ~ 1.4e-11 of the
             // tile's dominant term, so their fp32 rounding (~1e-5 incl. the exponent) stays below 2e-16 of it
             {
-                const char* e = knob("SHM_CONV_FAR_LOG");  // experiment knob: -ln of the relative size below which a cluster goes to fp32
-                const double far_log = e ? atof(e) : 25.0;
+                const double far_log = 25.0;  // -ln of the relative size below which a cluster goes to fp32
                 conv_far_gap = (far_log + std::log(std::max(1.0, amax / std::max(amin, 1e-300)))) / lambda;
                 // skipped clusters: a source further than r_hi + gap from the tile contributes less than (A_s / A_near) e^{-lambda gap} of
                 // the tile's dominant term (its nearest source: weight A_near, at most r_hi away).  A cluster with largest weight A_c is
@@ -375,26 +368,24 @@ struct Solver final : SolverBase {
                 const char* sk = knob("SHM_CONV_NO_SKIP");
                 // sources whose terms, all S of them together, stay below one rounding unit of a tile's dominant term are dropped (round 3: the bound is
                 // S e^-skip, loose by orders of magnitude -- rocker 512^3 fp32 reads the same L_inf against fp64, 5.6e-6, with a budget of 1e-6; until round 3
-                // a further safety factor of 64 sat in it: 470 -> 440 ms on that workload).  SHM_CONV_DROP_BUDGET32: A/B knob for the fp32 solve.
-                const char* db32 = knob("SHM_CONV_DROP_BUDGET32");
-                conv_skip_base = sk ? 3.0e38 : std::log((double)S / (db32 && sizeof(T) == 4 ? atof(db32) : eps));
+                // a further safety factor of 64 sat in it: 470 -> 440 ms on that workload).
+                conv_skip_base = sk ? 3.0e38 : std::log((double)S / eps);
                 // Tiered fp64 Step 1 (shm_conv_tiered.hip.h; default for SHM_F64): per (wave sub-tile, source), terms below e^-G of the sub-tile's dominant
                 // terms go through packed fp32.  G from the error budget on Y (1e-8, the stage test's bound and a decade inside the
                 // 1e-7 gate on phi): the packed-fp32 tier is measured at <= 5.6e-9 over every data file and grid size; sources whose terms all together stay
-                // below 2e-9 of the dominant term are dropped (SHM_CONV_DROP_BUDGET; max|dY| does not move between 1.6e-13 and 2e-9: tools/tier_robustness.py).
+                // below 2e-9 of the dominant term are dropped (max|dY| does not move between 1.6e-13 and 2e-9: tools/tier_robustness.py).
                 // SHM_CONV_EXACT=1: every pair in the reference's fp64 arithmetic (conv_normalize_kernel<double>; Y to 1e-11 of the C oracle).
                 const char* tl = knob("SHM_CONV_TIER_LOG");
                 conv_tier_log = tl ? atof(tl) : 8.0;
-                const char* db = knob("SHM_CONV_DROP_BUDGET");
-                conv_tier_skip_base = sk ? 3.0e38 : std::log((double)S / (db ? atof(db) : 2e-9));
+                conv_tier_skip_base = sk ? 3.0e38 : std::log((double)S / 2e-9);
                 // Round 6 -- the tiered kernels drop by ACCUMULATED bound (shm_conv_tiered.hip.h): budgets eps (same values as above: 2e-9 of the dominant term in the fp64
                 // solve, one fp32 rounding unit in the fp32 solve; 0: nothing is dropped), and K, the number of sources a block is expected to find near the threshold -- the
                 // candidate threshold is eps_soft / K, the running sum keeps the rule sound whatever K is.  Sources near the threshold lie in a ring of radius D ~ 25 / lambda
                 // around the block on a surface with one source per mean source area a: ~ 2 pi D / (a lambda) of them within one e-fold, i.e. 157 / (a lambda^2); three times
                 // that leaves the sum room (tools/r06_drop_sim.py: rocker 512^3 keeps 0.52-0.53 of its pairs for K = 512 ... 1024, 0.62 for K = 256, where the sum binds).
-                conv_drop_eps64 = sk ? 0. : (db ? atof(db) : 2e-9);
-                conv_drop_eps32 = sk ? 0. : (db32 ? atof(db32) : 6.0e-8);
-                conv_drop_K = knob("SHM_CONV_DROP_K") ? atof(knob("SHM_CONV_DROP_K")) : drop_rule_K(S, h_wn.data(), lambda);   // (the formula; refined on a sample of blocks below)
+                conv_drop_eps64 = sk ? 0. : 2e-9;
+                conv_drop_eps32 = sk ? 0. : 6.0e-8;
+                conv_drop_K = drop_rule_K(S, h_wn.data(), lambda);   // (the formula; refined on a sample of blocks below)
                 select_step1_arith(SHM_STEP1_AUTO);
             }
             d_src.upload(packed, stream);
@@ -427,7 +418,7 @@ struct Solver final : SolverBase {
             }
             d_clusters.upload(cl, stream);
             if constexpr (sizeof(T) == 8) {   // (fp64 solve: the tiered kernel reads these very records -- clusters of 64, unscaled weights)
-                if (!solve_only && knob("SHM_CONV_DROP_K") == nullptr && knob("SHM_CONV_DROP_K_FORMULA") == nullptr)
+                if (!solve_only)
                     conv_drop_K = choose_drop_K(reinterpret_cast<const double*>(packed.data()), n_clusters, cl.data(), kConvClusterRec, lambda, n, cell, conv_drop_eps64, S, conv_drop_K);
             }
             if constexpr (sizeof(T) == 4) {
@@ -463,7 +454,7 @@ struct Solver final : SolverBase {
                     clt[kConvClusterRec * (size_t)c + 4] = wmax2 > 0. ? (float)(0.5 * std::log(wmax2) + 1e-5) : -1.0e30f;
                     clt[kConvClusterRec * (size_t)c + 5] = wsum > 0. ? (float)(std::log(wsum) + 1e-5) : -1.0e30f;
                 }
-                if (!solve_only && knob("SHM_CONV_DROP_K") == nullptr && knob("SHM_CONV_DROP_K_FORMULA") == nullptr)
+                if (!solve_only)
                     conv_drop_K = choose_drop_K(pk.data(), n_clusters_t, clt.data(), kConvClusterRec, lambda, n, cell, conv_drop_eps32, S, conv_drop_K);
                 d_src_t.upload(pk, stream);
                 d_clusters_t.upload(clt, stream);
@@ -661,7 +652,7 @@ struct Solver final : SolverBase {
     // starts with ONE sample layer (differential rule; spread over the planes), goes on with one of the eight most central remaining layers under the box rule -- work that
     // needs no verdict, long enough for every sample block to finish meanwhile --, and then runs its share of the rest, centre to faces, under the rule the sample earned.
     bool far_rule_plan(Slab<T>& sl, int planes, int npt) {
-        if (sizeof(T) != 8 || !conv_tiered || conv_tier_exact || slabs.size() != 1 || total_slabs != 1 || knob("SHM_TIER_FAR_RULE") != nullptr || knob("SHM_TIER_NO_SAMPLE") != nullptr) return false;
+        if (sizeof(T) != 8 || !conv_tiered || conv_tier_exact || slabs.size() != 1 || total_slabs != 1 || knob("SHM_TIER_FAR_RULE") != nullptr) return false;
         if (step1_budget > 0. && step1_budget != kTierBudget) return false;
         const int layers = (planes + npt - 1) / npt;
         if (layers < 64 || layers % 8 != 0 || planes % npt != 0) return false;
@@ -753,8 +744,7 @@ struct Solver final : SolverBase {
             P.tier_log = conv_tier_exact ? 3.0e38f : conv_tiered32 ? -1.0e30f : (float)std::max(2.0, conv_tier_log - g_shift);   // (fp32 solve: every kept source that stays in the fp32 exponent range is "far")
             P.wscale = conv_wscale;
             {   // a-posteriori test of the packed-fp32 tier (shm_conv_tiered.hip.h): budget on Y / calibrated relative error of a far term as it shows up in X
-                static const double redo_env = knob("SHM_CONV_REDO_RATIO") ? atof(knob("SHM_CONV_REDO_RATIO")) : -1.;   // A/B knob (0: never)
-                const double ratio = redo_env >= 0. ? redo_env : budget / kTierEpsFar;
+                const double ratio = budget / kTierEpsFar;
                 P.far_redo_ratio = ratio > 0. ? (float)ratio : 3.0e38f;
             }
             P.skip_base = conv_tier_exact ? 3.0e38f : (float)std::min(conv_tiered ? conv_tier_skip_base - g_shift : conv_skip_base, 3.0e38);
@@ -766,18 +756,15 @@ struct Solver final : SolverBase {
                 P.drop_ltau_hard = eps > 0. ? (float)std::log2(tau_hard) : -3.0e38f;
                 P.drop_tau_hard = (float)(tau_hard * 1.0001);
                 P.drop_check = P.far_redo_ratio < 1.0e30f ? (float)((double)P.far_redo_ratio / budget) : (float)(1.0 / kTierEpsFar);   // 1 / eps_far
-                static const double u0_env = knob("SHM_TIER_U0") ? atof(knob("SHM_TIER_U0")) : -1.;          // experiment knobs (defaults: kTierU0, kTierFlush)
-                static const int flush_env = knob("SHM_TIER_FLUSH") ? atoi(knob("SHM_TIER_FLUSH")) : -1;
-                P.tier_u0 = (float)(u0_env >= 0. ? u0_env : kTierU0);
-                P.tier_flush = flush_env >= 0 ? flush_env : kTierFlush;
+                P.tier_u0 = (float)kTierU0;
+                P.tier_flush = kTierFlush;
             }
             P.inv_lambda = (float)(1.0 / lambda);
             P.tiles_x = (n + kConvTile - 1) / kConvTile;
             P.tiles_y = P.tiles_x;
             // nodes per lane (a z-column sharing dx^2 + dy^2): 4 when the grid still yields a full wave of workgroups, else 2
             const int planes = P.kk_end - P.kk_begin;
-            static const int npt_env = knob("SHM_TIER_NPT") ? atoi(knob("SHM_TIER_NPT")) : 0;   // A/B knob (round 5): 2 / 4 nodes per lane whatever the grid
-            const bool npt4 = npt_env ? npt_env == 4 : (long long)P.tiles_x * P.tiles_y * ((planes + 15) / 16) >= conv_grid_cap;
+            const bool npt4 = (long long)P.tiles_x * P.tiles_y * ((planes + 15) / 16) >= conv_grid_cap;
             // fp32: 8 nodes per lane on grids large enough, culled as two 16-plane halves (see the kernel); fp64 stays at 4 (8 needs 256 VGPRs: 57 against
             // 44 ms at 256^3).  SHM_CONV_NPT4: A/B knob, and the reference for the bit-identity check of the two shapes (tools/skip_check.py)
             const bool npt4_env = knob("SHM_CONV_NPT4") != nullptr;   // (read per launch: the check flips it inside one process)
@@ -807,9 +794,8 @@ struct Solver final : SolverBase {
                 const double conv_est_ms = pairs / (sizeof(T) == 8 ? 1.2e9 : 3.5e9);
                 conv_est_total_ms = (&sl == &slabs[0] ? 0. : conv_est_total_ms) + conv_est_ms;
                 const double setup_est_ms = 2.2e-3 * (double)std::min<int64_t>(S, (int64_t)8 * n * n);
-                static const bool no_reserve = knob("SHM_CONV_NO_RESERVE") != nullptr;  // A/B knob
                 if (conv_tiered || conv_tiered32) grid = std::min(grid, resident);   // its waves pull work from a queue: exactly the resident workgroups, nothing left to hand out
-                if (!no_reserve && !o_fast_hint && conv_est_ms < 4.0 * setup_est_ms && grid > resident - resident / 8) grid = resident - resident / 8;
+                if (!o_fast_hint && conv_est_ms < 4.0 * setup_est_ms && grid > resident - resident / 8) grid = resident - resident / 8;
             }
             // Several launches over z chunks instead of one: the set-up stream's kernels are dispatched only where a Step-1 launch has no workgroups left to
             // hand out -- its tail -- so one long launch makes the ~135 dependent launches of the constraint set-up finish with Step 1 whatever their own
@@ -817,11 +803,10 @@ struct Solver final : SolverBase {
             // Only where the tiles cost about the same (the kernel spans the grid: lambda * side < 100, nothing is culled) -- with culling the persistent
             // workgroups of ONE launch balance the uneven tiles, and every extra launch adds an uneven tail (rocker 512^3 fp32, 16 launches: +10 %) -- and
             // where Step 1 is long enough to matter (>= 10 ms); at most 16 chunks (256^3: set-up done at 38 instead of 42.7 ms with 8, Step 1 unchanged).
-            static const int split_env = knob("SHM_CONV_SPLIT") ? atoi(knob("SHM_CONV_SPLIT")) : 0;   // A/B knob (1: one launch)
             const bool uniform_tiles = lambda * cell * n < 100.;
             // (The tiered fp64 kernel needs none of this: its grid is exactly the resident workgroups -- nothing left to hand out -- and its 176 registers leave room on
             // every SIMD for a wave of the set-up kernels, which therefore run WHILE Step 1 runs; one launch, balanced by its work queue.)
-            const int want_chunks = split_env > 0 ? split_env : (conv_tiered || conv_tiered32) ? 1 : (uniform_tiles && conv_est_total_ms >= 10. ? std::min(16, (int)std::lround(conv_est_total_ms / 2.5)) : 1);
+            const int want_chunks = (conv_tiered || conv_tiered32) ? 1 : (uniform_tiles && conv_est_total_ms >= 10. ? std::min(16, (int)std::lround(conv_est_total_ms / 2.5)) : 1);
             const int nchunks = std::max(1, std::min(tiles_z, want_chunks));
             const int chunk_planes = ((tiles_z + nchunks - 1) / nchunks) * tile_z;
             if (!d_pair_counters.p) d_pair_counters.alloc(3);
@@ -870,10 +855,9 @@ struct Solver final : SolverBase {
                     }
                     return;
                 }
-                // the tiles of a launch are handed out by a queue head (culled workloads: their costs differ severalfold); SHM_CONV_STATIC: static stride (A/B knob)
-                static const bool static_tiles = knob("SHM_CONV_STATIC") != nullptr;
+                // the tiles of a launch are handed out by a queue head (culled workloads: their costs differ severalfold)
                 unsigned* head = nullptr;
-                if (!static_tiles && conv_launch_index < kMaxConvLaunches) head = d_unit_counters.p + 8 * conv_launch_index++;
+                if (conv_launch_index < kMaxConvLaunches) head = d_unit_counters.p + 8 * conv_launch_index++;
                 if constexpr (sizeof(T) == 4) {
                     if (sel == 8) {
                         hipLaunchKernelGGL((conv_normalize_kernel<float, 8>), g, dim3(kBlock), 0, stream, Pc, d_src.p, d_src32.p, d_clusters.p, d_exptab.p, sl.Y0.p, sl.Y1.p,
@@ -932,9 +916,8 @@ struct Solver final : SolverBase {
     }
 
     void launch_div(int scrub) {
-        static const bool classic = knob("SHM_DIV_CLASSIC") != nullptr;   // A/B knob: the one-node-per-thread kernel of rounds 1-3
         for (Slab<T>& sl : slabs) {
-            if (classic || vec == 1) {   // (n not a multiple of the vector width: scalar kernel)
+            if (vec == 1) {   // (n not a multiple of the vector width: the one-node-per-thread kernel)
                 hipLaunchKernelGGL((divergence_kernel<T>), dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)n, (unsigned)sl.nzl), dim3(kBlock), 0, stream, sl.gp,
                                    sl.Y0.p, sl.Y1.p, sl.Y2.p, sl.r.p, scrub);
                 sl.div_sum_blocks = 0;
@@ -947,9 +930,7 @@ struct Solver final : SolverBase {
             const int xchunks = (lanes + LX - 1) / LX, RB = kBlock / LX, rowgroups = (n + RB - 1) / RB;
             // planes per workgroup: 4 measured best at 256^3 and 512^3 in both precisions (512^3 fp64: 0.79 ms against 0.84 with 32 and 0.80 with 2 --
             // many short marches keep more loads in flight than few deep ones; the first plane's extra load is a fifth of a march)
-            int ZC = 4;
-            static const int zc_env = knob("SHM_DIV_ZC") ? atoi(knob("SHM_DIV_ZC")) : 0;   // A/B knob
-            if (zc_env > 0) ZC = zc_env;
+            const int ZC = 4;
             const unsigned nblk = (unsigned)((long long)xchunks * rowgroups * ((sl.nzl + ZC - 1) / ZC));
             sl.div_partials.alloc(nblk);
             sl.div_sum_blocks = (int)nblk;
@@ -1639,29 +1620,8 @@ struct Solver final : SolverBase {
         // Round 5 measured two shorter chains against the five launches below (rocker.obj 512^3, plain stencil CG, one box, profiles/r05_projection.txt):
         //   [t | y = T^T w | v_S by the last workgroup to arrive], S^-1, finish:  0.081 -> 0.266 ms per projection (the device-scope fence every workgroup needs before
         //                                                                          it takes its ticket writes the L2 back each time);
-        //   [t | y = T^T w], S^-1 mat-vec gathering v_S itself (8 rows per workgroup), finish (SHM_TL_MERGED3=1):  0.079 -> 0.095 ms, loop 0.693 -> 0.680 of the roofline.
+        //   [t | y = T^T w], S^-1 mat-vec gathering v_S itself (8 rows per workgroup), finish:  0.079 -> 0.095 ms, loop 0.693 -> 0.680 of the roofline.
         // The launches are short because they are narrow, not because they are many: fewer of them did not pay.  Five it stays.
-        static const bool merged3 = knob("SHM_TL_MERGED3") != nullptr;
-        if (merged3 && (size_t)tl.nSp * sizeof(double) <= 60 * 1024) {
-            // three launches: [t = D^-1 w_I | y = T^T w_I], u_S = S^-1 (w_S - gathered y), u_I = t - T u_S
-            const unsigned g1 = grows + (unsigned)tl.nChunks;
-            if (f32)
-                hipLaunchKernelGGL((tl_rows_cols_kernel<float>), dim3(g1), dim3(kBlock), 0, st, V, tl.rowBox.p, tl.nI, (int)grows, tl.D32.p, tl.chunkBox.p, tl.chunkCol.p, tl.T32.p, w,
-                                   tl.tbuf.p, tl.ybuf.p);
-            else
-                hipLaunchKernelGGL((tl_rows_cols_kernel<double>), dim3(g1), dim3(kBlock), 0, st, V, tl.rowBox.p, tl.nI, (int)grows, tl.D.p, tl.chunkBox.p, tl.chunkCol.p, tl.Tm.p, w,
-                                   tl.tbuf.p, tl.ybuf.p);
-            const unsigned g2 = (unsigned)((tl.nS + kTlSepRows - 1) / kTlSepRows);
-            const size_t lds = (size_t)tl.nSp * sizeof(double);
-            if (f32)
-                hipLaunchKernelGGL((tl_sep_matvec_kernel<float>), dim3(g2), dim3(kBlock), lds, st, tl.nS, tl.nSp, Ginv32.p, tl.sepRow.p, tl.adj_ptr.p, tl.adj_idx.p, w, tl.ybuf.p, tl.uS.p);
-            else
-                hipLaunchKernelGGL((tl_sep_matvec_kernel<double>), dim3(g2), dim3(kBlock), lds, st, tl.nS, tl.nSp, Ginv.p, tl.sepRow.p, tl.adj_ptr.p, tl.adj_idx.p, w, tl.ybuf.p, tl.uS.p);
-            const unsigned gfin = grows + (unsigned)((tl.nS + kBlock - 1) / kBlock);
-            if (f32) hipLaunchKernelGGL((tl_finish_kernel<float>), dim3(gfin), dim3(kBlock), 0, st, V, tl.rowBox.p, tl.nI, tl.nS, tl.sepRow.p, tl.T32.p, tl.tbuf.p, tl.uS.p, u);
-            else hipLaunchKernelGGL((tl_finish_kernel<double>), dim3(gfin), dim3(kBlock), 0, st, V, tl.rowBox.p, tl.nI, tl.nS, tl.sepRow.p, tl.Tm.p, tl.tbuf.p, tl.uS.p, u);
-            return;
-        }
         if (f32) hipLaunchKernelGGL((tl_rows_kernel<float>), dim3(grows), dim3(kBlock), 0, st, V, tl.rowBox.p, tl.nI, tl.D32.p, w, tl.tbuf.p);
         else hipLaunchKernelGGL((tl_rows_kernel<double>), dim3(grows), dim3(kBlock), 0, st, V, tl.rowBox.p, tl.nI, tl.D.p, w, tl.tbuf.p);
         if (tl.nChunks > 0) {
@@ -1681,33 +1641,24 @@ struct Solver final : SolverBase {
     // `refined_later`: the caller checks the inverse by a residual and refines (the direct dual solve with S^-1): the pivot blocks may then be inverted by the
     // 16-step block kernel, whose result differs from the scalar 64-step one at the 1e-11 level on ill-conditioned matrices (A A^T: near-dependent rows of
     // neighbouring cells; the projector test holds A P v to 1e-11 without refinement, so G keeps the scalar kernel)
-    // SHM_SETUP_SKIP (experiment knob, bit mask): leave out the set-up's device work piece by piece -- 2: the assembly of S, 4: the Gauss-Jordan launches (1 = the Green's
-    // table: SHM_SCHUR_KEEP_TABLE).  The solve's RESULT is then wrong; only Step 1's duration beside what is left means anything (tools/ab.py prints it).
-    static int setup_skip() {
-        static const int v = knob("SHM_SETUP_SKIP") ? atoi(knob("SHM_SETUP_SKIP")) : 0;
-        return v;
-    }
     void enqueue_gj_invert(double* M, int mp, bool refined_later = false) {
         hipStream_t stream = stream2;
         const int nb = mp / kGJ;
-        static const int outer_env = knob("SHM_GJ_OUTER") ? atoi(knob("SHM_GJ_OUTER")) : 0;   // experiment knob: pivot blocks per outer block
-        const int outer = outer_env > 0 ? std::min(outer_env, 8) : (nb >= 64 ? 4 : 1);
+        const int outer = nb >= 64 ? 4 : 1;   // pivot blocks per outer block
         gjP.alloc(kGJ * kGJ);
         gjR.alloc((size_t)outer * kGJ * mp);   // [outer * 64][mp]
         gjC.alloc((size_t)mp * outer * kGJ);   // [mp][outer * 64]
         gjFlag.alloc(2);
         HIPCHK(hipMemsetAsync(gjFlag.p, 0, sizeof(int), stream));
-        if (setup_skip() & 4) return;   // (timing experiments: see setup_skip)
         const int c_ld = outer * kGJ;
-        static const int pivot_env = knob("SHM_GJ_PIVOT_E") ? atoi(knob("SHM_GJ_PIVOT_E")) : 0;
         const bool classic = knob("SHM_GJ_CLASSIC") != nullptr;   // A/B knob, read per inversion (a test flips it inside one process): three dependent launches per pivot block (rounds 1-3)
-        // one launch per pivot block (gj_step_kernel; it inverts the pivot tiles by the scalar elimination) unless a pivot kernel is asked for explicitly
-        const bool stepped = outer == 1 && !classic && pivot_env == 0;
-        const int pivot_e = pivot_env ? pivot_env : (refined_later ? 16 : 4);   // 16 = block Gauss-Jordan with 4 x 4 pivot blocks (round 3);   // A/B knob: 4 = 256 threads; 2 = 1024 threads (2 % faster on an idle GPU, but four 40-register waves per SIMD do not fit beside Step 1)
+        // one launch per pivot block (gj_step_kernel; it inverts the pivot tiles by the scalar elimination)
+        const bool stepped = outer == 1 && !classic;
+        // pivot kernel of the other two forms: block Gauss-Jordan with 4 x 4 pivot blocks where the caller refines (round 3), else the scalar one on 256 threads
+        // (1024 threads: 2 % faster on an idle GPU, but four 40-register waves per SIMD do not fit beside Step 1)
         auto launch_pivot = [&](int kb) {
-            if (pivot_e == 16) hipLaunchKernelGGL(gj_pivot_block4_kernel, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
-            else if (pivot_e == 4) hipLaunchKernelGGL(gj_pivot_kernel<4>, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
-            else hipLaunchKernelGGL(gj_pivot_kernel<2>, dim3(1), dim3(1024), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
+            if (refined_later) hipLaunchKernelGGL(gj_pivot_block4_kernel, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
+            else hipLaunchKernelGGL(gj_pivot_kernel<4>, dim3(1), dim3(256), 0, stream, M, mp, kb, gjP.p, gjFlag.p, plan.setup_prio);
         };
         if (stepped) {
             // one launch per pivot block: step k-1's update beside step k's pivot and panels (gj_step_kernel)
@@ -1767,9 +1718,6 @@ struct Solver final : SolverBase {
     void enqueue_green_table(hipStream_t st) {
         const int P = n + 8;   // leading dimension of the last table index (rows stay 64-byte aligned)
         const size_t n1 = (size_t)n + 1;
-        static const bool keep_table = knob("SHM_SCHUR_KEEP_TABLE") != nullptr;
-        if (!keep_table) gs_n = 0;
-        if (gs_n == n && gs_cell == cell) return;
         {
             const double pi = 3.14159265358979323846;
             h_gs_lam.resize(n);
@@ -1790,8 +1738,8 @@ struct Solver final : SolverBase {
             W1.alloc((size_t)n * n * P);
             // Round 5: n = 2^k -- the three cosine contractions as FFT passes (shm_green_fft.hip.h: O(n^3 log n), 0.8 GB of traffic at 256^3) instead of dense
             // products on the fp64 matrix cores (6 n^4 flop: 1.2 ms at 256^3, 10 ms at 512^3 -- machine time taken from the Step-1 kernel they run beside).
-            // SHM_GREEN_GEMM=1: the products (A/B; they also serve every n that is not a power of two)
-            const bool by_fft = (n & (n - 1)) == 0 && n >= 16 && n <= 512 && knob("SHM_GREEN_GEMM") == nullptr;
+            // The products serve every n that is not a power of two.
+            const bool by_fft = (n & (n - 1)) == 0 && n >= 16 && n <= 512;
             if (by_fft) {
                 const double pi = 3.14159265358979323846;
                 h_gs_tw.resize(2 * (size_t)n);   // [0, n): e^{-2 pi i t / n} ; [n, 2n): e^{-i pi k / n}
@@ -1839,22 +1787,16 @@ struct Solver final : SolverBase {
                 // T[d1][(d2,d3)] from W2[k1][(d2,d3)]: tiles of L consecutive (d2,d3)
                 pass(false, (int)(n1l * Pl / L), (int)(n1l * Pl / L), addr(L, 0, 1, n1l * Pl), addr(L, 0, 1, n1l * Pl), W2.p, gs_T.p);
                 HIPCHK(hipGetLastError());
-                gs_n = n;
-                gs_cell = cell;
                 return;
             }
             HIPCHK(hipMemsetAsync(gs_Ct.p, 0, (size_t)n * P * sizeof(double), st));
             hipLaunchKernelGGL(cosine_tables_kernel, dim3(grid_for(n1 * n, 1024)), dim3(kBlock), 0, st, n, P, gs_ctab.p, gs_Cm.p, gs_Ct.p);
             hipLaunchKernelGGL(green_symbol_kernel, dim3((unsigned)std::min(n * n, 8 * num_cus)), dim3(kBlock), 0, st, n, gs_lam.p, W0.p);
             // beside the tiered fp64 Step 1 (two 184-register waves per SIMD) only the narrow shape fits on a SIMD; otherwise the 128 x 128 tiles
-            static const bool gemm_wide_env = knob("SHM_GREEN_WIDE") != nullptr;   // A/B knob
-            const bool narrow = (plan_in.tiered() || knob("SHM_GREEN_NARROW") != nullptr) && !gemm_wide_env;
+            const bool narrow = plan_in.tiered();
             auto tiles = [](size_t v) { return (unsigned)((v + kGemmT - 1) / kGemmT); };
             auto gemm = [&](unsigned batches, int M, int N, int K, const double* A, int lda, long long sA, const double* B, int ldb, long long sB, double* C, int ldc, long long sC) {
-                static const int wn_env = knob("SHM_GREEN_WN") ? atoi(knob("SHM_GREEN_WN")) : 0;   // A/B knob (round 5)
-                if (narrow && wn_env == 2)
-                    hipLaunchKernelGGL(dgemm_rm_kernel<2>, dim3((unsigned)((N + 63) / 64), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, plan.setup_prio);
-                else if (narrow)
+                if (narrow)
                     hipLaunchKernelGGL(dgemm_rm_kernel<1>, dim3((unsigned)((N + 31) / 32), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, plan.setup_prio);
                 else
                     hipLaunchKernelGGL(dgemm_rm_kernel<4>, dim3(tiles((size_t)N), tiles((size_t)M), batches), dim3(kBlock), 0, st, M, N, K, A, lda, sA, B, ldb, sB, C, ldc, sC, plan.setup_prio);
@@ -1866,8 +1808,6 @@ struct Solver final : SolverBase {
             // T[d1][(d2,d3)] = sum_k1 Cm[d1][k1] W2[k1][(d2,d3)]
             gemm(1, (int)n1, (int)(n1 * P), n, gs_Cm.p, n, 0LL, W2.p, (int)(n1 * P), 0LL, gs_T.p, (int)(n1 * P), 0LL);
             HIPCHK(hipGetLastError());
-            gs_n = n;
-            gs_cell = cell;
         }
     }
     void prepare_schur() {
@@ -1875,7 +1815,7 @@ struct Solver final : SolverBase {
         have_S = false;
         if (!plan.explicit_S) return;
         // T is rebuilt with every solve (0.85 ms at 256^3, 10 ms at 512^3, beside Step 1: +1 % / +2.5 % of a solve), so that a timed solve contains all of
-        // its own work; SHM_SCHUR_KEEP_TABLE=1 keeps it while n and h stay the same (it depends on nothing else)
+        // its own work
         if (!plan.green_early) enqueue_green_table(st);
         // rows in Morton order of their cells: the 16 x 16 tiles of the assembly then read neighbouring table entries
         std::vector<std::pair<uint64_t, int>> key((size_t)m);
@@ -1924,8 +1864,7 @@ struct Solver final : SolverBase {
         if (plan.green_early) HIPCHK(hipStreamWaitEvent(st, e_gs_done->e, 0));
         HIPCHK(hipMemsetAsync(Sdense.p, 0, (size_t)mp * mp * sizeof(double), st));
         const unsigned mt = (unsigned)((m + 15) / 16);
-        if (setup_skip() & 2) hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Sdense.p, mp, 0, m, 1.0);   // (something invertible)
-        else hipLaunchKernelGGL(schur_assemble_kernel, dim3(mt, mt), dim3(kBlock), 0, st, m, mp, n, P, d_rowX.p, d_rowT.p, gs_T.p, Sdense.p, plan.setup_prio);
+        hipLaunchKernelGGL(schur_assemble_kernel, dim3(mt, mt), dim3(kBlock), 0, st, m, mp, n, P, d_rowX.p, d_rowT.p, gs_T.p, Sdense.p, plan.setup_prio);
         HIPCHK(hipGetLastError());
         if (dual_direct) {
             Sinv.alloc((size_t)mp * mp);
@@ -2007,10 +1946,8 @@ struct Solver final : SolverBase {
         const int xchunks = (per_row + tx - 1) / tx;
         const int yblocks = (n + tyb * kStRY - 1) / (tyb * kStRY);
         // planes per workgroup: as many as possible (less z-halo re-reading) while the grid still has >= ~4 workgroups per CU
-        static const int zc_env = knob("SHM_STENCIL_ZC") ? atoi(knob("SHM_STENCIL_ZC")) : 0;
         int zc = 16;
         while (zc > 4 && (long long)xchunks * yblocks * ((sl.nzl + zc - 1) / zc) < 1024) zc >>= 1;
-        if (zc_env > 0) zc = zc_env;
         const int zchunks = (sl.nzl + zc - 1) / zc;
         return {dim3((unsigned)(xchunks * yblocks * zchunks)), dim3((unsigned)tx, (unsigned)tyb), xchunks, yblocks, zc};
     }
@@ -2048,7 +1985,7 @@ struct Solver final : SolverBase {
         int wx = 0, ry = 8, zc = 16, yblocks = 0, zchunks = 0, nw = 8, part = 0;
     };
     bool fused_available() const {
-        static const bool off = knob("SHM_CG_CLASSIC") != nullptr;  // A/B knob: the round-1 four-kernel loop
+        static const bool off = knob("SHM_CG_CLASSIC") != nullptr;  // the four-kernel loop at any size (it is the shipped path where a row does not fit: tests reach it this way)
         return !off && (n + vec - 1) / vec <= 8 * 64;
     }
     FusedCfg fused_cfg(const Slab<T>& sl) const {
@@ -2059,17 +1996,9 @@ struct Solver final : SolverBase {
         // waves per workgroup: 8 (two 512-thread workgroups per CU, out of phase), 16 where a row needs 4 or more waves side by side -- with 8 the
         // workgroup would own only 4 rows (wx = 4) or 2 (wx = 8) and re-read as many border rows from L2 as it owns: 512^3 fp64 (wx = 4), 8 -> 16 waves:
         // DIR 5.33 -> 5.60 TB/s, RES 5.57 -> 5.88, 1.558 -> 1.50 ms per iteration; where wy is already >= 4 (256^3, 512^3 fp32) 16 waves are no better
-        static const int nw_env = knob("SHM_FUSED_WAVES") ? atoi(knob("SHM_FUSED_WAVES")) : 0;  // A/B knob: 4, 8 or 16 waves per workgroup
-        static const int ry_env = knob("SHM_FUSED_RY") ? atoi(knob("SHM_FUSED_RY")) : 0;
-        c.ry = (vec == 1) ? 4 : 2;
-#ifdef SHM_AB_SHAPES
-        if (ry_env == 4 || (ry_env == 2 && vec != 1)) c.ry = ry_env;   // (1 row per lane measured no better than 2)
-        const bool four_waves = nw_env == 4 && c.wx <= 4;
-#else
-        (void)ry_env;
-        const bool four_waves = false;
-#endif
-        c.nw = four_waves ? 4 : (c.ry <= 2 && (nw_env == 16 || (nw_env == 0 && c.wx >= 4))) ? 16 : 8;   // (16-wave kernels exist for <= 2 rows per lane)
+        static const int nw_env = knob("SHM_FUSED_WAVES") ? atoi(knob("SHM_FUSED_WAVES")) : 0;  // A/B knob: 8 or 16 waves per workgroup
+        c.ry = (vec == 1) ? 4 : 2;   // rows per lane (1 measured no better than 2)
+        c.nw = (c.ry <= 2 && (nw_env == 16 || (nw_env == 0 && c.wx >= 4))) ? 16 : 8;   // (16-wave kernels exist for <= 2 rows per lane)
         const int wy = c.nw / c.wx;
         static const int zc_env = knob("SHM_FUSED_ZC") ? atoi(knob("SHM_FUSED_ZC")) : 0;
         // rows per workgroup wy * ry: 8 rows per lane unless that leaves too few workgroups along y to fill the chip with deep z chunks
@@ -2106,16 +2035,6 @@ struct Solver final : SolverBase {
         if (fold_pq && !sl.pq_partials.p) sl.pq_partials.alloc(sl.partials.count);
         if (c.part == FUSED_INTERIOR) { F.zc_first = 1; c.zchunks -= 2; }
         else if (c.part == FUSED_BOUNDARY) { F.zc_stride = c.zchunks - 1; c.zchunks = 2; }
-#ifdef SHM_AB_SHAPES   // (round 6: the 4-wave shapes and, for vector widths > 1, the 4-rows-per-lane shapes exist for A/B runs only -- 52 of the ~120 instantiations of
-                       // cg_fused_kernel, compiled in with -DSHM_AB_SHAPES; the launcher below never selects them otherwise)
-        if constexpr (WX <= 4) {
-            if (c.nw == 4) {
-                hipLaunchKernelGGL((cg_fused_kernel<T, VEC, RY, WX, 4 / WX, MODE>), dim3((unsigned)(c.yblocks * c.zchunks)), dim3(256), 0, stream, F, sl.sc.p, slot_old,
-                                   slot_new, sl.red.p, sl.pq.p, init, use_uw, alpha_slot, zsrc, pin, pout, sl.r.p, dir_to_own ? sl.pq_partials.p : sl.partials.p, sl.pq_partials.p, pq_np);
-                return;
-            }
-        }
-#endif
         if constexpr (RY <= 2) {
             if (c.nw == 16) {   // 16-wave workgroups: twice the rows per workgroup, half the re-read border rows (see fused_cfg)
                 hipLaunchKernelGGL((cg_fused_kernel<T, VEC, RY, WX, 16 / WX, MODE>), dim3((unsigned)(c.yblocks * c.zchunks)), dim3(1024), 0, stream, F, sl.sc.p, slot_old,
@@ -2141,9 +2060,6 @@ struct Solver final : SolverBase {
         FusedCfg c = fused_cfg(sl);
         c.part = part;
         if (vec == 1) launch_fused_w<MODE, 1, 4>(sl, c, slot_old, slot_new, init, use_uw, alpha_slot, zsrc, pin, pout);
-#ifdef SHM_AB_SHAPES
-        else if (c.ry == 4) launch_fused_w<MODE, vec_width<T>(), 4>(sl, c, slot_old, slot_new, init, use_uw, alpha_slot, zsrc, pin, pout);
-#endif
         else launch_fused_w<MODE, vec_width<T>(), 2>(sl, c, slot_old, slot_new, init, use_uw, alpha_slot, zsrc, pin, pout);
         return c.yblocks * c.zchunks;
     }
@@ -2175,10 +2091,9 @@ struct Solver final : SolverBase {
         }
         if (!st) allreduce(0, 1 + m);
         for (Slab<T>& sl : slabs) {
-            // (SHM_PROJ_F32, round 5: the fp32 solve's projector with the fp32 copies of the matrices -- half the bytes per application, but the converged plain CG of
-            // rocker 128^3 fp32 then lands at 1.1e-3 of the fp64 solve instead of 6e-5: the projector has to be exact to the solve's own rounding.  Not adopted.)
-            static const bool proj_f32 = knob("SHM_PROJ_F32") != nullptr;
-            apply_Ginv(sl.red.p + 1, sl.u.p, proj_f32 && sizeof(T) == 4, stream);
+            // (the fp32 solve projects with the fp64 matrices too: with their fp32 copies the converged plain CG of rocker 128^3 fp32 lands at 1.1e-3 of the fp64 solve
+            // instead of 6e-5 -- the projector has to be exact to the solve's own rounding, round 5)
+            apply_Ginv(sl.red.p + 1, sl.u.p, false, stream);
             const int nred = std::max(1, std::min(16, m / 1024));   // workgroups of the u.w reduction (one per ~1000 rows)
             if (!sl.proj_ticket.p) {
                 sl.proj_ticket.alloc(1);
@@ -2300,40 +2215,14 @@ struct Solver final : SolverBase {
         if (seg && !kCanSeg) throw Error(SHM_ERR_INVALID, "DCT: segmented layout in a sweep that does not support it");
         if constexpr (kCanSeg) {
             if (seg) {
-                launch_dct_k<MODE, TIn, TOut, DOT, LOG2N, XPASS, true>(P, ntiles, in, out, dotw, partials, tile_list, elem_mask);
+                launch_dct_pf<MODE, TIn, TOut, DOT, LOG2N, XPASS, true, false>(P, ntiles, in, out, dotw, partials, tile_list, elem_mask);
                 return;
             }
         }
-        launch_dct_k<MODE, TIn, TOut, DOT, LOG2N, XPASS, false>(P, ntiles, in, out, dotw, partials, tile_list, elem_mask);
+        launch_dct_pf<MODE, TIn, TOut, DOT, LOG2N, XPASS, false, false>(P, ntiles, in, out, dotw, partials, tile_list, elem_mask);
     }
-    template <int MODE, typename TIn, typename TOut, bool DOT, int LOG2N, bool XPASS, bool SEG>
-    void launch_dct_k(const DctParams& P, int ntiles, const TIn* in, TOut* out, const TOut* dotw, double* partials, const int* tile_list, const unsigned* elem_mask) {
-        // Dense sweeps of the long transforms (n >= 256): the LDS-DMA double buffer of shm_dct.hip.h (PF, round 6) -- the next tile's input in flight, global -> LDS, under this
-        // tile's FFT passes and stores.  Built, verified (76 GPU tests) and measured SLOWER than two or three plain workgroups per CU out of phase: 512^3 fp64 0.639 -> 0.687 ms per
-        // sweep (0.46 -> 0.43 of the HBM peak), fp32 0.333 -> 0.411, 256^3 0.059 -> 0.070 (profiles/r06_dct_dma_rejected.txt): the sweeps are bound by their barrier-separated
-        // LDS passes at the occupancy the LDS footprint allows, not by the bytes in flight -- the staging tile costs a workgroup per CU and adds a pass.  (Round 4's register
-        // prefetch: the same verdict, profiles/r04_dct_prefetch_rejected.txt.)  Compiled only into -DSHM_DCT_PF builds; SHM_DCT_NO_PF=1 switches it off there (A/B).
-        static const bool no_pf = knob("SHM_DCT_NO_PF") != nullptr;
-#ifdef SHM_DCT_PF
-        constexpr bool kCanPf = LOG2N >= 8 && !SEG && sizeof(TIn) == sizeof(TP) && ((size_t)(1 << LOG2N) * dct_lines_for(LOG2N, (int)sizeof(TP)) * sizeof(TIn)) % (16 * kBlock) == 0;
-#else
-        constexpr bool kCanPf = false;
-#endif
-        bool use_pf = false;
-        if constexpr (kCanPf) {
-            // (unit stride between the lines of a y / z tile, 16-byte aligned rows: what the plain layouts of launch_precond have)
-            const bool aligned = XPASS ? (P.in.elem_stride == 1 && (P.in.line_stride * (long long)sizeof(TIn)) % 16 == 0)
-                                       : (P.in.line_stride == 1 && (P.in.elem_stride * (long long)sizeof(TIn)) % 16 == 0 && (P.in.a_stride * (long long)sizeof(TIn)) % 16 == 0);
-            use_pf = !no_pf && !tile_list && !elem_mask && aligned && (P.in.off * (long long)sizeof(TIn)) % 16 == 0 && (P.in.b_stride * (long long)sizeof(TIn)) % 16 == 0;
-        }
-        if constexpr (kCanPf) {
-            if (use_pf) {
-                launch_dct_pf<MODE, TIn, TOut, DOT, LOG2N, XPASS, SEG, true>(P, ntiles, in, out, dotw, partials, tile_list, elem_mask);
-                return;
-            }
-        }
-        launch_dct_pf<MODE, TIn, TOut, DOT, LOG2N, XPASS, SEG, false>(P, ntiles, in, out, dotw, partials, tile_list, elem_mask);
-    }
+    // PF = false everywhere: the kernel's LDS-DMA double buffer (the next tile's input in flight under this tile's passes, round 6) measured slower than two or three plain
+    // workgroups per CU out of phase -- 512^3 fp64 0.639 -> 0.687 ms per sweep (profiles/r06_dct_dma_rejected.txt; round 4's register prefetch: profiles/r04_dct_prefetch_rejected.txt).
     // (the kernel is named in the launch itself: a variant reached only through a function pointer assigned in a branch got no host stub from this compiler)
     template <int MODE, typename TIn, typename TOut, bool DOT, int LOG2N, bool XPASS, bool SEG, bool PF>
     void launch_dct_pf(const DctParams& P, int ntiles, const TIn* in, TOut* out, const TOut* dotw, double* partials, const int* tile_list, const unsigned* elem_mask) {
@@ -2346,14 +2235,8 @@ struct Solver final : SolverBase {
         }
         DctParams Q = P;
         Q.ntiles = ntiles;
-#ifdef SHM_EXPERIMENT_KNOBS
-        { static const int dbg = knob("SHM_DCT_SKIP") ? atoi(knob("SHM_DCT_SKIP")) : 0; Q.debug_skip = dbg; }
-#else
         Q.debug_skip = 0;
-#endif
-        const int per_cu = std::max(1, (int)((size_t)(160 * 1024) / lds));
-        const int grid = (int)std::min<long long>(ntiles, std::max<long long>(1, (long long)dct_grid_x16 * num_cus * per_cu / 16));
-        hipLaunchKernelGGL((dct_lines_kernel<TP, TIn, TOut, MODE, DOT, LOG2N, XPASS, SEG, PF>), dim3((unsigned)grid), dim3(kBlock), lds, stream, Q, in, out, d_tw.p, d_om.p, d_lam.p, dotw,
+        hipLaunchKernelGGL((dct_lines_kernel<TP, TIn, TOut, MODE, DOT, LOG2N, XPASS, SEG, PF>), dim3((unsigned)ntiles), dim3(kBlock), lds, stream, Q, in, out, d_tw.p, d_om.p, d_lam.p, dotw,
                            partials, tile_list, elem_mask);
     }
     template <int MODE, typename TIn, typename TOut, bool DOT, bool XPASS>
@@ -2502,6 +2385,96 @@ struct Solver final : SolverBase {
     }
 
     // ------------------------------------------------------------------------------------------
+    // Bookkeeping shared by the solve paths: the timeline of a solve, the phase part of shm_stats, the residual check of a batch of iterations, how a loop that
+    // did not converge is reported, and the sampled per-kernel timing.
+    // The events of one solve and its wall-clock origin.  solve_impl records them as it queues the stages; solve_gathered builds one for the whole-grid solver.
+    struct SolveClock {
+        Event e_start, e_conv, e_div;   // Step 1 and the divergence on `stream`
+        Event e_s2a, e_s2b;             // the constraint set-up on stream2
+        Event e_setup;                  // `stream` has waited for the set-up: the solve phase starts here
+        std::chrono::steady_clock::time_point wall0 = std::chrono::steady_clock::now();
+        bool has_step1 = true;          // false: Steps 1-2 ran elsewhere (the whole-grid solver of solve_gathered), e_start / e_conv / e_div carry no phase
+        bool has_setup = true;          // false: no constraint set-up (fast integration): the solve phase starts at e_div
+    };
+    // Everything of shm_stats that is the same on every path; what a path does not have stays zero.  h_pinned holds the scalars of the finished solve.
+    void fill_phase_stats(shm_stats* st, SolveClock& c, Event& e_pcg, Event& e_end, int iters, double rel_residual) {
+        const auto wall1 = std::chrono::steady_clock::now();
+        memset(st, 0, sizeof *st);
+        st->n = n;
+        st->S = S;
+        st->iters = iters;
+        st->rel_residual = rel_residual;
+        st->shift = h_pinned[SC_SHIFT];
+        if (c.has_step1) {
+            st->ms_conv = elapsed(c.e_start, c.e_conv);
+            st->ms_div = elapsed(c.e_conv, c.e_div);
+        }
+        if (c.has_setup) {
+            st->m = m;
+            HIPCHK(hipEventSynchronize(c.e_s2b.e));
+            st->ms_setup = last_setup_wall_ms;  // host wall time from the start of the set-up to "(A A^T)^-1 ready" (it runs beside Step 1)
+            if (c.has_step1) st->ms_wait_setup = elapsed(c.e_div, c.e_setup);
+        }
+        st->ms_pcg = elapsed(c.has_setup ? c.e_setup : c.e_div, e_pcg);
+        st->ms_shift = elapsed(e_pcg, e_end);
+        st->ms_total = std::chrono::duration<double, std::milli>(wall1 - c.wall0).count();
+    }
+    // The scalars of slab 0 after a batch of iterations (or after the shift), fetched to h_pinned behind everything queued on `stream`.
+    struct Residual {
+        double rr0 = 0., rr = 0.;
+        bool finite = true;
+        double rel() const { return rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.; }
+        bool below(double tol) const { return rr <= tol * tol * rr0; }  // (rr = ||r'||^2 - u.w may round slightly below 0 at convergence)
+    };
+    Residual fetch_residual(int extra_slot = -1 /* a further scalar that must be finite: rho of the primal loops, r.z of the dual one */) {
+        HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        Residual r;
+        r.rr0 = h_pinned[SC_RR0];
+        r.rr = h_pinned[SC_RR];
+        r.finite = std::isfinite(r.rr) && std::isfinite(r.rr0) && (extra_slot < 0 || std::isfinite(h_pinned[extra_slot]));
+        return r;
+    }
+    void throw_loop_end(const char* name, bool breakdown, bool converged, int it, const Residual& r, const shm_opts& o) {
+        if (breakdown) throw Error(SHM_ERR_BREAKDOWN, fmt("%s broke down at iteration %d (rr=%g, rr0=%g)", name, it, r.rr, r.rr0));
+        if (!converged) throw Error(SHM_ERR_NOCONV, fmt("%s: max_iters=%d reached, rel. residual %.3e > tol %.1e", name, o.max_iters, r.rel(), o.tol));
+    }
+    // Per-kernel durations from events around the launches of a few iterations (a sampled iteration runs slower: how many are sampled is the caller's choice).
+    struct SampleTimer {
+        std::vector<std::unique_ptr<Event>> ev;
+        const int max_samples, per;
+        int n = 0;
+        bool on = false;   // the iteration in progress is sampled
+        SampleTimer(bool enabled, int max_samples_, int events_per_sample) : max_samples(max_samples_), per(events_per_sample) {
+            if (enabled) for (int a = 0; a < per * max_samples; a++) ev.emplace_back(new Event());
+        }
+        bool begin(bool wanted = true) { return on = !ev.empty() && n < max_samples && wanted; }
+        void mark(int k, hipStream_t st) { if (on) ev[(size_t)(per * n + k)]->record(st); }
+        void end() { if (on) n++; on = false; }
+        double avg(int i, int j) const {   // mean time between marks i and j, ms
+            double a = 0.;
+            for (int q = 0; q < n; q++) a += elapsed(*ev[(size_t)(per * q + i)], *ev[(size_t)(per * q + j)]);
+            return n ? a / n : 0.;
+        }
+    };
+    // Start of projected CG, shared by the fused and the classic loop: x = 0, ||b||^2, r = P b, and where preconditioned z = P M^-1 r
+    void primal_prologue(bool pre, std::vector<int>& nparts, std::vector<int>& zparts) {
+        for (size_t s = 0; s < slabs.size(); s++) {
+            Slab<T>& sl = slabs[s];
+            HIPCHK(hipMemsetAsync(sl.x.p, 0, sl.ntot * sizeof(T), stream));
+            nparts[s] = stream_grid(sl);
+            if (vec == 1) launch_norm2<1>(sl, sl.r.p, nparts[s]);
+            else launch_norm2<vec_width<T>()>(sl, sl.r.p, nparts[s]);
+        }
+        launch_projection(nparts, false, 2);
+        if (pre) {
+            const int np = launch_precond(true);
+            for (auto& v : zparts) v = np;
+            launch_projection(zparts, true, 0);
+        }
+    }
+
+    // ------------------------------------------------------------------------------------------
     // shift + phi (:110-111), shared by the constrained solve and the fast path; x holds -phi.
     void launch_shift_and_phi() {
         for (Slab<T>& sl : slabs) {
@@ -2518,7 +2491,7 @@ struct Solver final : SolverBase {
 
     // fastIntegration: three families of prefix scans (see bfs_* kernels); slabs are chained bottom-up through the
     // top plane of x (device copy between local slabs, ncclSend/ncclRecv between ranks).
-    void solve_fast(const shm_opts& o, shm_stats* st, Event& e_start, Event& e_conv, Event& e_div, std::chrono::steady_clock::time_point wall0) {
+    void solve_fast(const shm_opts& o, shm_stats* st, SolveClock& clk) {
         (void)o;
         Event e_int, e_end;
         build_shift_items_only();
@@ -2542,19 +2515,10 @@ struct Solver final : SolverBase {
         e_int.record(stream);
         launch_shift_and_phi();
         e_end.record(stream);
-        HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        fetch_residual();
         have_phi = true;
         if (st) {
-            memset(st, 0, sizeof *st);
-            st->n = n;
-            st->S = S;
-            st->shift = h_pinned[SC_SHIFT];
-            st->ms_conv = elapsed(e_start, e_conv);
-            st->ms_div = elapsed(e_conv, e_div);
-            st->ms_pcg = elapsed(e_div, e_int);  // the integration that replaces the solve
-            st->ms_shift = elapsed(e_int, e_end);
-            st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+            fill_phase_stats(st, clk, e_int, e_end, 0, 0.);  // ms_pcg: the integration that replaces the solve
             st->preconditioner = SHM_PRECOND_NONE;
         }
     }
@@ -2624,10 +2588,8 @@ struct Solver final : SolverBase {
         Q.in = plain_addr(0, L, nn, 1, plane);
         Q.out = Q.in;
         // the recursive z step wins from n = 256 on (256^3: 79 -> 42 us, 512^3: 0.61 -> 0.09 ms per application); below that the transform of
-        // all lines is cheaper than one more launch.  SHM_DUAL_Z_FFT: A/B knob for the transform version
-        static const bool fft_z_env = knob("SHM_DUAL_Z_FFT") != nullptr;
-        const bool fft_z = fft_z_env || n < 256;
-        if (fft_z) launch_dct<DCT_FUSED, TP, TP, false, false>(Q, tiles_all, sl.S2.p, sl.W1.p, (const TP*)nullptr, nullptr, nullptr, sl.act_z.p);
+        // all lines is cheaper than one more launch
+        if (n < 256) launch_dct<DCT_FUSED, TP, TP, false, false>(Q, tiles_all, sl.S2.p, sl.W1.p, (const TP*)nullptr, nullptr, nullptr, sl.act_z.p);
         else {
             hipLaunchKernelGGL((zsolve_sparse_kernel<TP>), dim3((unsigned)((plane + kBlock - 1) / kBlock) + 1), dim3(kBlock), 0, stream, n, sl.n_act_planes,
                                sl.act_planes.p, d_lam64.p, sl.gp.inv_h2, sl.S2.p, sl.W1.p);   // + 1: the workgroup of the singular (0, 0) line
@@ -2645,8 +2607,7 @@ struct Solver final : SolverBase {
 
     // ------------------------------------------------------------------------------------------
     // Dual solver (see the block comment above the dual_* kernels): CG on S = A K^+ A^T for the multipliers.
-    void solve_dual(const shm_opts& o, shm_stats* st, Event& e_start, Event& e_conv, Event& e_div, Event& e_setup, Event& e_s2a, Event& e_s2b,
-                    std::chrono::steady_clock::time_point wall0) {
+    void solve_dual(const shm_opts& o, shm_stats* st, SolveClock& clk) {
         Event e_pcg, e_end;
         const int check_every = o.check_every > 0 ? std::min(o.check_every, 4) : 2;
         auto mv = [&](Slab<T>& sl, int k) { return sl.dv.p + (size_t)k * mp; };
@@ -2689,7 +2650,7 @@ struct Solver final : SolverBase {
             hipLaunchKernelGGL(dual_init_mu_kernel, dim3(1), dim3(kDualBlock), 0, stream, m, sl.pq.p, mv(sl, V_MU), sl.sc.p);
         }
         // ---- r = Pm(g - S mu), z, p
-        const bool sparse_ok = total_slabs == 1 && slabs[0].n_act_x > 0 && !knob("SHM_DENSE_DCT");
+        const bool sparse_ok = total_slabs == 1 && slabs[0].n_act_x > 0;
         // explicit S (shm_schur.hip.h): one dense mat-vec instead of scatter, five sweeps, gather.  Several slabs / ranks (round 6): S (and S^-1, G^-1, B) are replicated and
         // every slab applies them to its own copy of the m-vectors -- the same numbers everywhere, no communication inside the dual iteration
         const bool dense_S = have_S;
@@ -2711,11 +2672,9 @@ struct Solver final : SolverBase {
         if (!direct) precondition(1);
         HIPCHK(hipGetLastError());
 
-        const int kMaxSamples = 32;
-        std::vector<std::unique_ptr<Event>> ev;
-        if (st) for (int a = 0; a < 3 * kMaxSamples; a++) ev.emplace_back(new Event());
-        int nsamples = 0, it = 0;
-        double rr0 = 0., rr = 0.;
+        SampleTimer tm(st != nullptr, 32, 3);   // every iteration until 32 are sampled: [K^+ or S][the rest]
+        int it = 0;
+        Residual res;
         bool converged = false, breakdown = false;
         // ---- x = K^+ (A^T mu - b)   (the additive constant cancels in the shift), shift, phi
         // Transform sweeps: b - A^T mu is formed IN PLACE on the touched nodes of r and the sign rides in the spectral normalisation (-K^+ (b - A^T mu): bit for bit
@@ -2739,8 +2698,7 @@ struct Solver final : SolverBase {
             e_pcg.record(stream);
             launch_shift_and_phi();
             e_end.record(stream);
-            HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
+            return fetch_residual();
         };
         bool finished = false;
         if (direct) {
@@ -2755,97 +2713,64 @@ struct Solver final : SolverBase {
             const int max_passes = std::min(o.max_iters, 6);
             double rr_prev = -1.;
             while (it < max_passes && !converged && !breakdown) {
-                const bool sample = st && nsamples < kMaxSamples;
-                if (sample) ev[3 * nsamples]->record(stream);
+                tm.begin();
+                tm.mark(0, stream);
                 for (Slab<T>& sl : slabs) {
                     apply_Sinv(mv(sl, V_R), mv(sl, V_T1));
                     hipLaunchKernelGGL(dual_bordered_kernel, dim3(1), dim3(kDualBlock), 0, stream, m, mv(sl, V_T1), Sinv_ones.p, (const double*)nullptr, 1, mv(sl, V_MU));
                 }
-                if (sample) ev[3 * nsamples + 1]->record(stream);
+                tm.mark(1, stream);
                 apply_S(V_MU);
                 for (Slab<T>& sl : slabs)
                     hipLaunchKernelGGL(dual_init_residual_kernel, dim3(1), dim3(kDualBlock), 0, stream, m, mv(sl, V_G), sl.red.p + 1, mv(sl, V_R), sl.sc.p, 0);
-                if (sample) {
-                    ev[3 * nsamples + 2]->record(stream);
-                    nsamples++;
-                }
+                tm.mark(2, stream);
+                tm.end();
                 it++;
                 HIPCHK(hipGetLastError());
                 // The final stage is queued behind the pass without waiting for its residual: one host round trip per solve instead of two.  Should the pass
                 // not have converged (not seen on any test case: the first pass is the solution), refinement passes follow and the final stage runs again.
-                finish();
+                res = finish();
                 finished = true;
-                rr0 = h_pinned[SC_RR0];
-                rr = h_pinned[SC_RR];
-                if (!std::isfinite(rr) || !std::isfinite(rr0)) breakdown = true;
-                else if (rr <= o.tol * o.tol * rr0) converged = true;
-                else if (rr_prev >= 0. && rr > 0.0625 * rr_prev && rr <= 1e-18 * rr0) converged = true;   // stagnated at the rounding floor (residuals are squared here)
-                rr_prev = rr;
-                log("[shm] dual (direct) pass=%d rel_res=%.3e", it, rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.);
+                if (!res.finite) breakdown = true;
+                else if (res.below(o.tol)) converged = true;
+                else if (rr_prev >= 0. && res.rr > 0.0625 * rr_prev && res.rr <= 1e-18 * res.rr0) converged = true;   // stagnated at the rounding floor (residuals are squared here)
+                rr_prev = res.rr;
+                log("[shm] dual (direct) pass=%d rel_res=%.3e", it, res.rel());
             }
         }
         while (!direct && it < o.max_iters && !converged && !breakdown) {
             const int batch_end = std::min(o.max_iters, it + check_every);
             for (; it < batch_end; it++) {
-                const bool sample = st && nsamples < kMaxSamples;
+                tm.begin();
                 if (!dense_S) scatter(V_P, ARR_P, 0);
-                if (sample) ev[3 * nsamples]->record(stream);
+                tm.mark(0, stream);
                 if (dense_S) apply_S(V_P);
                 else if (sparse_ok) launch_precond_sparse(ARR_P, ARR_Z);
                 else launch_precond(false, ARR_P, ARR_Z);
-                if (sample) ev[3 * nsamples + 1]->record(stream);
+                tm.mark(1, stream);
                 if (!dense_S) gather(ARR_Z);
                 for (Slab<T>& sl : slabs)
                     hipLaunchKernelGGL(dual_update_kernel, dim3(1), dim3(kDualBlock), 0, stream, m, sl.red.p + 1, mv(sl, V_P), mv(sl, V_MU), mv(sl, V_R), sl.sc.p);
                 precondition(0);
-                if (sample) {
-                    ev[3 * nsamples + 2]->record(stream);
-                    nsamples++;
-                }
+                tm.mark(2, stream);
+                tm.end();
             }
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            rr0 = h_pinned[SC_RR0];
-            rr = h_pinned[SC_RR];
-#ifdef SHM_EXPERIMENT_KNOBS
-            static const int force_iters = knob("SHM_DUAL_FORCE_ITERS") ? atoi(knob("SHM_DUAL_FORCE_ITERS")) : 0;  // timing experiments only
-#else
-            const int force_iters = 0;
-#endif
-            if (force_iters > 0) converged = it >= force_iters;
-            else if (!std::isfinite(rr) || !std::isfinite(rr0) || !std::isfinite(h_pinned[SC_RZ])) breakdown = true;
-            else if (rr <= o.tol * o.tol * rr0) converged = true;
-            log("[shm] dual it=%d rel_res=%.3e", it, rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.);
+            res = fetch_residual(SC_RZ);
+            if (!res.finite) breakdown = true;
+            else if (res.below(o.tol)) converged = true;
+            log("[shm] dual it=%d rel_res=%.3e", it, res.rel());
         }
         if (!finished) finish();
         have_phi = true;
         have_div = false;  // r still holds b, but q (= phi now) and p were reused
         if (st) {
-            memset(st, 0, sizeof *st);
-            st->n = n;
-            st->m = m;
-            st->S = S;
-            st->iters = it;
-            st->rel_residual = rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.;
+            fill_phase_stats(st, clk, e_pcg, e_end, it, res.rel());
             // the reference shifts phi_ref = -x_kkt = -(x0 - mean(A x0)); report ITS shift: shift(-x0) + mean(A x0)
-            st->shift = h_pinned[SC_SHIFT] + h_pinned[SC_AXSUM] / (double)m;
-            st->ms_conv = elapsed(e_start, e_conv);
-            st->ms_div = elapsed(e_conv, e_div);
-            HIPCHK(hipEventSynchronize(e_s2b.e));
-            st->ms_setup = last_setup_wall_ms;  // host wall time from the start of the set-up to "(A A^T)^-1 ready" (it runs beside Step 1)
-            st->ms_wait_setup = elapsed(e_div, e_setup);
-            st->ms_pcg = elapsed(e_setup, e_pcg);
-            st->ms_shift = elapsed(e_pcg, e_end);
-            st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
-            double a_dct = 0., a_rest = 0.;
-            for (int a = 0; a < nsamples; a++) {
-                a_dct += elapsed(*ev[3 * a], *ev[3 * a + 1]);
-                a_rest += elapsed(*ev[3 * a + 1], *ev[3 * a + 2]);
-            }
-            st->ms_precond_avg = nsamples ? a_dct / nsamples : 0.;
-            st->ms_project_avg = nsamples ? a_rest / nsamples : 0.;  // gather, m-vector algebra, 2 G^-1 mat-vecs, B mat-vec
-            st->kernel_samples = nsamples;
+            st->shift += h_pinned[SC_AXSUM] / (double)m;
+            st->ms_precond_avg = tm.avg(0, 1);
+            st->ms_project_avg = tm.avg(1, 2);  // gather, m-vector algebra, 2 G^-1 mat-vecs, B mat-vec
+            st->kernel_samples = tm.n;
             st->preconditioner = SHM_PRECOND_DCT;
             st->solver = total_slabs > 1 ? SHM_SOLVER_DUAL_SLABS : SHM_SOLVER_DUAL;
             if (direct) {   // S^-1 and S once per pass (plus S^-1 1 once per solve)
@@ -2862,9 +2787,7 @@ struct Solver final : SolverBase {
                 st->bytes_per_iter = (double)N * (3.0 * sizeof(T) + 8.0 * sizeof(TP)) - (double)N * sizeof(T);  // five dense DCT sweeps, no r.z read
             }
         }
-        if (breakdown) throw Error(SHM_ERR_BREAKDOWN, fmt("dual CG broke down at iteration %d (rr=%g, rr0=%g)", it, rr, rr0));
-        if (!converged) throw Error(SHM_ERR_NOCONV, fmt("dual CG: max_iters=%d reached, rel. residual %.3e > tol %.1e", o.max_iters,
-                                                          std::sqrt(std::fabs(rr / rr0)), o.tol));
+        throw_loop_end("dual CG", breakdown, converged, it, res, o);
     }
 
     // ------------------------------------------------------------------------------------------
@@ -2873,11 +2796,14 @@ struct Solver final : SolverBase {
     // xGMI) and every rank runs the single-GPU dual solve on the whole grid, whose constraint set-up overlapped Step 1 as usual.
     // Each rank keeps phi for its own planes.  (The dual iteration works on m-vectors and a handful of sparse transforms; it is
     // latency-bound on one GPU already, and its distributed form -- SHM_SOLVER_DUAL_SLABS -- pays two all-to-alls per iteration.)
-    void solve_gathered(const shm_opts& o, const PlanIn& in, shm_stats* st, Event& e_start, Event& e_conv, Event& e_div, std::chrono::steady_clock::time_point wall0) {
+    void solve_gathered(const shm_opts& o, const PlanIn& in, shm_stats* st, SolveClock& clk) {
         Solver<T>& F = *full;
         Slab<T>& fs = F.slabs[0];
-        Event c_s2a, c_s2b, e_gather, f_start, f_setup;
-        c_s2a.record(F.stream2);
+        Event e_gather;
+        SolveClock fclk;   // the whole-grid solver's timeline: its set-up beside this rank's Step 1, its solve phase from the gathered b on; Steps 1-2 are this solver's
+        fclk.wall0 = clk.wall0;
+        fclk.has_step1 = false;
+        fclk.e_s2a.record(F.stream2);
         // The whole-grid solver plans its set-up with this rank's options, knobs and Step 1: what it can hide behind is this rank's share of Step 1 (in.conv_est_total_ms),
         // and beside WHICH Step-1 kernel it runs -- the tiered one leaves room only for the narrow GEMM shape (round 4: the whole-grid solver never learnt this and queued
         // the 256-register shape, which waits for Step 1's persistent waves to end).  Either tiered kernel counts as the fp64 one here, whatever the precision.
@@ -2887,7 +2813,7 @@ struct Solver final : SolverBase {
         Plan fplan;
         fplan.path = kPathGathered; fplan.dual_requested = true;
         F.build_constraints(fin, fplan);  // on the whole-grid solver's set-up stream: overlaps this rank's Step-1 kernel
-        c_s2b.record(F.stream2);
+        fclk.e_s2b.record(F.stream2);
         F.setup_precond();
         const size_t plane = (size_t)n * n;
         for (Slab<T>& sl : slabs)
@@ -2909,8 +2835,8 @@ struct Solver final : SolverBase {
         }
         e_gather.record(stream);
         HIPCHK(hipStreamWaitEvent(F.stream, e_gather.e, 0));
-        f_start.record(F.stream);
-        f_setup.record(F.stream);
+        fclk.e_start.record(F.stream);   // (never read -- has_step1 is false --: recorded so that the calls on F.stream stay what they were)
+        fclk.e_setup.record(F.stream);
         F.have_div = true;
         fs.div_sum_blocks = 0;   // (b came from the ranks' slabs: no partial sums of the whole grid)
         shm_stats cst;
@@ -2919,7 +2845,7 @@ struct Solver final : SolverBase {
         bool noconv = false;
         std::string noconv_msg;
         try {
-            F.solve_dual(o, &cst, f_start, f_start, f_start, f_setup, c_s2a, c_s2b, wall0);  // synchronises F.stream; phi = F.q
+            F.solve_dual(o, &cst, fclk);  // synchronises F.stream; phi = F.q
         } catch (const Error& e) {
             if (e.code != SHM_ERR_NOCONV) throw;
             noconv = true;
@@ -2931,10 +2857,10 @@ struct Solver final : SolverBase {
         have_phi = true;
         if (st) {
             *st = cst;
-            st->ms_conv = elapsed(e_start, e_conv);
-            st->ms_div = elapsed(e_conv, e_div);
-            st->ms_wait_setup = elapsed(e_div, e_gather);  // here: the gather of b (the set-up was waited for on the host before it)
-            st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+            st->ms_conv = elapsed(clk.e_start, clk.e_conv);
+            st->ms_div = elapsed(clk.e_conv, clk.e_div);
+            st->ms_wait_setup = elapsed(clk.e_div, e_gather);  // here: the gather of b (the set-up was waited for on the host before it)
+            st->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk.wall0).count();
         }
         if (noconv) throw Error(SHM_ERR_NOCONV, noconv_msg);
     }
@@ -2945,34 +2871,20 @@ struct Solver final : SolverBase {
     //      loop k { a_k = rho_k / (p_k . K p_k);  r = P(r + a_k K p_k);  z = P M^-1 r;  rho_{k+1} = r.z;  p_{k+1} = -z + (rho_{k+1}/rho_k) p_k }
     //      x = sum_k a_k p_k, accumulated two directions at a time (p_k lives in buffer k & 1: sl.p / sl.q)
     // N-sized launches per iteration: RES (r += a K p, ||r||^2), DIR (p' = -z + b p, p'.K p'), and x_update2 on odd k: 8 N T bytes.
-    void solve_primal_fused(const shm_opts& o, shm_stats* st, bool pre, Event& e_start, Event& e_conv, Event& e_div, Event& e_setup, Event& e_s2a,
-                            Event& e_s2b, std::chrono::steady_clock::time_point wall0) {
-        Event e_pcg, e_end;
+    void solve_primal_fused(const shm_opts& o, shm_stats* st, bool pre, SolveClock& clk) {
         std::vector<int> nparts(slabs.size()), zparts(slabs.size(), 0), kparts(slabs.size(), 0);
-        fold_pq = total_slabs == 1 && !comm && knob("SHM_CG_NO_PQFOLD") == nullptr;   // (A/B knob: finalize_sum_kernel after every DIR sweep, as until round 4)
+        fold_pq = total_slabs == 1 && !comm;   // (otherwise finalize_sum_kernel after every DIR sweep, as until round 4)
         fold_pq_np = 0;
         auto dirbuf = [&](Slab<T>& sl, int k) { return (k & 1) ? sl.q.p : sl.p.p; };
         const int zsel = pre ? ARR_Z : ARR_R;
-        for (size_t s = 0; s < slabs.size(); s++) {
-            Slab<T>& sl = slabs[s];
-            HIPCHK(hipMemsetAsync(sl.x.p, 0, sl.ntot * sizeof(T), stream));
-            nparts[s] = stream_grid(sl);
-            if (vec == 1) launch_norm2<1>(sl, sl.r.p, nparts[s]);
-            else launch_norm2<vec_width<T>()>(sl, sl.r.p, nparts[s]);
-        }
-        launch_projection(nparts, false, 2);
-        if (pre) {
-            const int np = launch_precond(true);
-            for (auto& v : zparts) v = np;
-            launch_projection(zparts, true, 0);
-        }
+        primal_prologue(pre, nparts, zparts);
         // Several slabs: the ghost planes of z travel on a second stream while the z chunks that do not touch them are swept (the first and the
         // last chunk of every slab follow once the planes have arrived).  One host thread issues everything in the same order on every rank; RCCL
-        // orders the operations of one communicator across streams itself.  SHM_HALO_SERIAL: exchange first, then one sweep (A/B knob).
+        // orders the operations of one communicator across streams itself.  Otherwise: exchange first, then one sweep.
         // With a communicator (several processes) the overlap is OPT-IN (SHM_HALO_OVERLAP=1) until it has run on real multi-rank RCCL: it relies on RCCL
         // serialising the send/recv of stream_h against the all-reduces the same communicator issues on `stream`, which only the librccl double and the
         // loop-back transport (several slabs in one process: device copies) have exercised so far.  Read per solve: the tests flip it inside one process.
-        const bool halo_serial = knob("SHM_HALO_SERIAL") != nullptr || (comm != nullptr && knob("SHM_HALO_OVERLAP") == nullptr);
+        const bool halo_serial = comm != nullptr && knob("SHM_HALO_OVERLAP") == nullptr;
         bool overlap = total_slabs > 1 && !halo_serial;
         for (Slab<T>& sl : slabs) overlap = overlap && fused_cfg(sl).zchunks >= 3;
         if (overlap && !stream_h) HIPCHK(hipStreamCreateWithFlags(&stream_h, hipStreamNonBlocking));
@@ -3014,21 +2926,16 @@ struct Solver final : SolverBase {
         // Per-kernel durations are sampled on a few iterations only: a sampled iteration keeps everything on one stream (no projection beside the x update) and records
         // eight events, i.e. it runs ~40 us slower than the others -- 32 of them were 16 % of the 200-iteration stencil-PCG leg of bench.py and 40 % of a DCT-preconditioned
         // solve (round 5: 12; the kernels are steady, their averages do not move)
-        const int kMaxSamples = 12, kEvPer = 8;
-        std::vector<std::unique_ptr<Event>> ev;
-        if (st) for (int a = 0; a < kEvPer * kMaxSamples; a++) ev.emplace_back(new Event());
-        int nsamples = 0;
+        SampleTimer tm(st != nullptr, 12, 8);
         const int sample_stride = pre ? 2 : 8;
-        static const bool no_xoverlap = knob("SHM_CG_NO_XOVERLAP") != nullptr;   // A/B knob
-        // (512^3, same box: rocker fp64 0.706 -> 0.717, fp32 0.680 -> 0.691 of the roofline, bunny fp64 0.720 -> 0.725, fp32 0.710 -> 0.722; profiles/r04_projection.txt)
-        const bool xoverlap = !no_xoverlap && total_slabs == 1 && !comm;
+        // the x update beside the projection (512^3, same box: rocker fp64 0.706 -> 0.717, fp32 0.680 -> 0.691 of the roofline, bunny fp64 0.720 -> 0.725, fp32 0.710 -> 0.722; profiles/r04_projection.txt)
+        const bool xoverlap = total_slabs == 1 && !comm;
         // Round 5: with the overlap on and no preconditioner, x is updated on HALF the grid in EVERY iteration instead of on all of it in every other one -- the upper half
         // on odd k, the lower half on even k, each time with the two latest directions (p_{k-1}, p_k: both buffers and both step lengths are valid once RES of
         // iteration k has run), so every a_j p_j reaches every node exactly once (the lower half takes a_0 p_0 alone at k = 0; the half that lags one step behind
         // at the end is flushed after the loop).  Same 4NT per two iterations -- but now EVERY projection (seven short dependent launches, 0.08 ms with the
         // two-level inverse) has 2NT of update to run beside, where the even iterations used to expose theirs in full.
-        static const bool no_xsplit = knob("SHM_CG_NO_XSPLIT") != nullptr;   // A/B knob: the round-4 schedule
-        const bool xsplit = xoverlap && !pre && !no_xsplit;
+        const bool xsplit = xoverlap && !pre;
         Event e_xfork, e_xjoin;
         // The second stream is the set-up stream (idle during the loop, of the highest priority -- the projection's short kernels get their CUs at once -- and
         // known to run beside `stream`: the whole set-up does).  A stream of its own, of the same or of the lowest priority, was measured to serialise with the
@@ -3036,16 +2943,14 @@ struct Solver final : SolverBase {
         // update: 0.31 instead of 0.08 ms per iteration, every sweep 15 % slower).
         hipStream_t const stream_x = stream2;
         int it = 0;
-        double rr0 = 0., rr = 0.;
+        Residual res;
         bool converged = false, breakdown = false;
         while (it < o.max_iters && !converged && !breakdown) {
             const int batch_end = std::min(o.max_iters, it + o.check_every);
             for (; it < batch_end; it++) {
                 const int slot_old = (it & 1) ? SC_RHO_B : SC_RHO_A, slot_new = (it & 1) ? SC_RHO_A : SC_RHO_B;
-                const bool sample = st && nsamples < kMaxSamples && (it % sample_stride == 1);
-                auto mark = [&](int k) {
-                    if (sample) ev[kEvPer * nsamples + k]->record(stream);
-                };
+                const bool sample = tm.begin(it % sample_stride == 1);
+                auto mark = [&](int k) { tm.mark(k, stream); };
                 mark(0);
                 for (size_t s = 0; s < slabs.size(); s++)
                     nparts[s] = launch_fused<CGF_RES>(slabs[s], slot_old, slot_new, 0, 0, (it & 1) ? SC_ALPHA_B : SC_ALPHA_A, (const T*)nullptr,
@@ -3080,17 +2985,13 @@ struct Solver final : SolverBase {
                 mark(6);
                 finalize_pq();
                 mark(7);
-                if (sample) nsamples++;
+                tm.end();
             }
             HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            rr0 = h_pinned[SC_RR0];
-            rr = h_pinned[SC_RR];
-            const double rho = h_pinned[(it & 1) ? SC_RHO_B : SC_RHO_A];
-            if (!std::isfinite(rr) || !std::isfinite(rr0) || !std::isfinite(rho)) breakdown = true;
-            else if (rr <= o.tol * o.tol * rr0) converged = true;
-            log("[shm] it=%d rel_res=%.3e", it, rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.);
+            res = fetch_residual((it & 1) ? SC_RHO_B : SC_RHO_A);
+            if (!res.finite) breakdown = true;
+            else if (res.below(o.tol)) converged = true;
+            log("[shm] it=%d rel_res=%.3e", it, res.rel());
         }
         if (xsplit) {
             // the half that was not updated in the last iteration is one direction behind: the upper half after an even last index, the lower half after an odd one
@@ -3098,55 +2999,99 @@ struct Solver final : SolverBase {
             else if (it > 0) launch_x_update2(slabs[0], 0, 1, nullptr, 0);
         } else if (it & 1)  // the last direction has an even index: its step is still missing from x
             for (Slab<T>& sl : slabs) launch_x_update2(sl, 1, 0);
+        // marks of a sampled iteration: 0 RES 1 projection 2 DCT 3 projection 4 x_update2 (sampled iterations are odd: one launch each) 5 DIR (incl. the halo exchange of z
+        // with several slabs) 6 sums 7.  3NT (DIR) + 3NT (RES) + 4NT every other iteration (x_update2; cg_form 4: 2NT -- half the grid -- every iteration)
+        const PrimalLoop loop = {xsplit ? 4 : 1, 8.0, {5, 6}, {0, 1}, {{1, 2}, {3, 4}}, {4, 5}, {2, 3}};
+        finish_primal(o, st, pre, clk, tm, it, res, converged, breakdown, loop);
+    }
+    // What a primal loop tells the shared epilogue about itself: shm_stats.cg_form, the bytes its sweeps move per iteration in units of N T, and between which
+    // marks of a sampled iteration each of the kernels shm_stats reports ran
+    struct PrimalLoop {
+        int cg_form;
+        double sweep_nt;
+        int stencil[2], update_xr[2], project[2][2], update_p[2], precond[2];
+    };
+    // End of both primal loops: shift and phi behind the last iteration, the statistics, and the loop's verdict
+    void finish_primal(const shm_opts& o, shm_stats* st, bool pre, SolveClock& clk, SampleTimer& tm, int it, const Residual& res, bool converged, bool breakdown,
+                       const PrimalLoop& loop) {
+        Event e_pcg, e_end;
         e_pcg.record(stream);
         launch_shift_and_phi();
         e_end.record(stream);
-        HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
+        fetch_residual();
         have_phi = true;
-        have_div = false;  // q (a direction buffer, then phi) and r were reused
-        const auto wall1 = std::chrono::steady_clock::now();
+        have_div = false;  // r (the residual) and q (a direction buffer or K p, then phi) were reused
         if (st) {
-            memset(st, 0, sizeof *st);
-            st->n = n;
-            st->m = m;
-            st->S = S;
-            st->iters = it;
-            st->rel_residual = rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.;
-            st->shift = h_pinned[SC_SHIFT];
-            st->ms_conv = elapsed(e_start, e_conv);
-            st->ms_div = elapsed(e_conv, e_div);
-            HIPCHK(hipEventSynchronize(e_s2b.e));
-            st->ms_setup = last_setup_wall_ms;  // host wall time from the start of the set-up to "(A A^T)^-1 ready" (it runs beside Step 1)
-            st->ms_wait_setup = elapsed(e_div, e_setup);
-            st->ms_pcg = elapsed(e_setup, e_pcg);
-            st->ms_shift = elapsed(e_pcg, e_end);
-            st->ms_total = std::chrono::duration<double, std::milli>(wall1 - wall0).count();
-            double acc[5] = {0, 0, 0, 0, 0};
-            for (int a = 0; a < nsamples; a++) {
-                auto el = [&](int i, int j) { return (double)elapsed(*ev[kEvPer * a + i], *ev[kEvPer * a + j]); };
-                acc[0] += el(5, 6);            // DIR sweep (incl. the halo exchange of z with several slabs)
-                acc[1] += el(0, 1);            // RES sweep
-                acc[2] += el(1, 2) + el(3, 4); // projections
-                acc[3] += el(4, 5);            // x_update2 (sampled iterations are odd: one launch each)
-                acc[4] += el(2, 3);            // DCT
-            }
-            const double inv = nsamples ? 1. / nsamples : 0.;
-            st->ms_stencil_avg = acc[0] * inv;
-            st->ms_update_xr_avg = acc[1] * inv;
-            st->ms_project_avg = acc[2] * inv;
-            st->ms_update_p_avg = acc[3] * inv;
-            st->ms_precond_avg = pre ? acc[4] * inv : 0.;
-            st->kernel_samples = nsamples;
+            fill_phase_stats(st, clk, e_pcg, e_end, it, res.rel());
+            auto avg = [&](const int (&ij)[2]) { return tm.avg(ij[0], ij[1]); };
+            st->ms_stencil_avg = avg(loop.stencil);
+            st->ms_update_xr_avg = avg(loop.update_xr);
+            st->ms_project_avg = avg(loop.project[0]) + avg(loop.project[1]);
+            st->ms_update_p_avg = avg(loop.update_p);
+            st->ms_precond_avg = pre ? avg(loop.precond) : 0.;
+            st->kernel_samples = tm.n;
             st->preconditioner = pre ? SHM_PRECOND_DCT : SHM_PRECOND_NONE;
             st->solver = SHM_SOLVER_PRIMAL;
-            st->cg_form = xsplit ? 4 : 1;
-            // 3NT (DIR) + 3NT (RES) + 4NT every other iteration (x_update2; cg_form 4: 2NT -- half the grid -- every iteration); the five DCT sweeps move 3T + 8TP more
-            st->bytes_per_iter = 8.0 * (double)N * sizeof(T) + (pre ? (double)N * (3.0 * sizeof(T) + 8.0 * sizeof(TP)) : 0.);
+            st->cg_form = loop.cg_form;
+            // the five DCT sweeps move 3T + 8TP more than the loop's own sweeps (read r twice + write z, 4 in-place sweeps of W)
+            st->bytes_per_iter = loop.sweep_nt * (double)N * sizeof(T) + (pre ? (double)N * (3.0 * sizeof(T) + 8.0 * sizeof(TP)) : 0.);
         }
-        if (breakdown) throw Error(SHM_ERR_BREAKDOWN, fmt("projected CG broke down at iteration %d (rr=%g, rr0=%g)", it, rr, rr0));
-        if (!converged) throw Error(SHM_ERR_NOCONV, fmt("projected CG: max_iters=%d reached, rel. residual %.3e > tol %.1e", o.max_iters,
-                                                          rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0., o.tol));
+        throw_loop_end("projected CG", breakdown, converged, it, res, o);
+    }
+
+    // ---- projected (preconditioned) CG, SURVEY 7.3 (the classic four-kernel loop: grids wider than 8 waves of vector lanes, or SHM_CG_CLASSIC):
+    //      x=0; r=P b; z=P M^-1 r; p=-z; loop { q=Kp; a=rho/p.q; x+=a p; r=P(r+a q); z=P M^-1 r; rho'=r.z; p=-z+(rho'/rho) p }
+    void solve_primal_classic(const shm_opts& o, shm_stats* st, bool pre, SolveClock& clk) {
+        std::vector<int> nparts(slabs.size()), zparts(slabs.size(), 0);
+        primal_prologue(pre, nparts, zparts);
+        update_p_all(SC_RHO_A, SC_RHO_A, 1, pre, nparts);
+        HIPCHK(hipGetLastError());
+
+        SampleTimer tm(st != nullptr, 32, 8);
+        const int sample_stride = pre ? 2 : 8;
+        int it = 0;
+        Residual res;
+        bool converged = false, breakdown = false;
+        while (it < o.max_iters && !converged && !breakdown) {
+            const int batch_end = std::min(o.max_iters, it + o.check_every);
+            for (; it < batch_end; it++) {
+                const int slot_old = (it & 1) ? SC_RHO_B : SC_RHO_A, slot_new = (it & 1) ? SC_RHO_A : SC_RHO_B;
+                halo_exchange_p();
+                tm.begin(it % sample_stride == 1);
+                auto mark = [&](int k) { tm.mark(k, stream); };
+                mark(0);
+                for (Slab<T>& sl : slabs) launch_stencil(sl);
+                mark(1);
+                for (Slab<T>& sl : slabs) {
+                    const StencilLaunch L = stencil_dims(sl);
+                    hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, stream, sl.partials.p, (int)L.grid.x, sl.pq.p);
+                }
+                allreduce(1, 1);
+                mark(2);
+                for (size_t s = 0; s < slabs.size(); s++) {
+                    if (vec == 1) launch_update_xr<1>(slabs[s], slot_old, nparts[s]);
+                    else launch_update_xr<vec_width<T>()>(slabs[s], slot_old, nparts[s]);
+                }
+                mark(3);
+                launch_projection(nparts, false, 1);
+                mark(4);
+                if (pre) launch_precond(true);
+                mark(5);
+                if (pre) launch_projection(zparts, true, 0);
+                mark(6);
+                update_p_all(slot_old, slot_new, 0, pre, nparts);
+                mark(7);
+                tm.end();
+            }
+            HIPCHK(hipGetLastError());
+            res = fetch_residual((it & 1) ? SC_RHO_B : SC_RHO_A);
+            if (!res.finite) breakdown = true;
+            else if (res.below(o.tol)) converged = true;
+            log("[shm] it=%d rel_res=%.3e", it, res.rel());
+        }
+        // marks of a sampled iteration: 0 stencil 1 sums 2 update_xr 3 projection 4 DCT 5 projection 6 update_p 7.  11NT for the four sweeps
+        const PrimalLoop loop = {0, 11.0, {0, 1}, {2, 3}, {{3, 4}, {5, 6}}, {6, 7}, {4, 5}};
+        finish_primal(o, st, pre, clk, tm, it, res, converged, breakdown, loop);
     }
 
     // ------------------------------------------------------------------------------------------
@@ -3180,11 +3125,10 @@ struct Solver final : SolverBase {
         if (o.max_iters <= 0) o.max_iters = 20 * n;
         if (o.check_every <= 0) o.check_every = pre ? 4 : 32;
 
-        Event e_start, e_conv, e_div, e_setup, e_pcg, e_end, e_s2a, e_s2b;
-        const auto wall0 = std::chrono::steady_clock::now();
+        SolveClock clk;
         step1_budget = o.step1_budget;
         select_step1_arith(o.step1_arith);
-        e_start.record(stream);
+        clk.e_start.record(stream);
         // the arrival counters of the projection's ticketed reductions are "zero between launches" by the last workgroup's reset: a launch cut short (a fault) would
         // leave them non-zero for the rest of the process, so every solve starts from zero.  Projections on the two streams share these counters and the
         // partial-sum scratch: they are event-serialised (fork / join around the x update), never concurrent.
@@ -3192,162 +3136,34 @@ struct Solver final : SolverBase {
             if (sl.proj_ticket.p) HIPCHK(hipMemsetAsync(sl.proj_ticket.p, 0, sizeof(unsigned), stream));
         o_fast_hint = o.fast_integration != 0;
         launch_conv();
-        e_conv.record(stream);
+        clk.e_conv.record(stream);
         launch_div(o.scrub_nonfinite);
-        e_div.record(stream);
+        clk.e_div.record(stream);
         if (p.path == kPathFast) {
             log("[shm] plan: fast");
-            solve_fast(o, st, e_start, e_conv, e_div, wall0);
+            clk.has_setup = false;   // (no constraints: the integration starts at e_div)
+            solve_fast(o, st, clk);
             return;
         }
         in.step1 = step1_kernel();   // (known once Step 1 is queued)
         in.conv_est_total_ms = conv_est_total_ms;
         if (p.path == kPathGathered) {
             ensure_full();
-            solve_gathered(o, in, st, e_start, e_conv, e_div, wall0);
+            solve_gathered(o, in, st, clk);
             return;
         }
         static const bool setup_alone = knob("SHM_SETUP_ALONE") != nullptr;  // measurement knob: wait for Step 1 first, so that shm_stats.ms_setup is
         if (setup_alone) HIPCHK(hipStreamSynchronize(stream));                  // the set-up's time on an otherwise idle GPU (tools/scaling_model.py)
-        e_s2a.record(stream2);
+        clk.e_s2a.record(stream2);
         build_constraints(in, p);  // on stream2: overlaps the Step-1 kernel; returns once (A A^T)^-1 (or S^-1, for the direct dual solve) is ready
-        e_s2b.record(stream2);
+        clk.e_s2b.record(stream2);
         const bool dual = p.path == kPathDualSlabs || p.path == kPathDualLocal;
         if (pre || dual) setup_precond();
-        e_setup.record(stream);
-        if (dual) {
-            solve_dual(o, st, e_start, e_conv, e_div, e_setup, e_s2a, e_s2b, wall0);
-            return;
-        }
-
-        if (p.path == kPathPrimalFused) {
-            solve_primal_fused(o, st, pre, e_start, e_conv, e_div, e_setup, e_s2a, e_s2b, wall0);
-            return;
-        }
-        // ---- projected (preconditioned) CG, SURVEY 7.3 (the classic four-kernel loop: grids wider than 8 waves of vector lanes, or SHM_CG_CLASSIC):
-        //      x=0; r=P b; z=P M^-1 r; p=-z; loop { q=Kp; a=rho/p.q; x+=a p; r=P(r+a q); z=P M^-1 r; rho'=r.z; p=-z+(rho'/rho) p }
-        std::vector<int> nparts(slabs.size()), zparts(slabs.size(), 0);
-        for (size_t s = 0; s < slabs.size(); s++) {
-            Slab<T>& sl = slabs[s];
-            HIPCHK(hipMemsetAsync(sl.x.p, 0, sl.ntot * sizeof(T), stream));
-            nparts[s] = stream_grid(sl);
-            if (vec == 1) launch_norm2<1>(sl, sl.r.p, nparts[s]);
-            else launch_norm2<vec_width<T>()>(sl, sl.r.p, nparts[s]);
-        }
-        launch_projection(nparts, false, 2);
-        if (pre) {
-            const int np = launch_precond(true);
-            for (auto& v : zparts) v = np;
-            launch_projection(zparts, true, 0);
-        }
-        update_p_all(SC_RHO_A, SC_RHO_A, 1, pre, nparts);
-        HIPCHK(hipGetLastError());
-
-        // sampled per-kernel timing (events on the solver's stream; 8 events per sampled iteration)
-        const int kMaxSamples = 32, kEvPer = 8;
-        std::vector<std::unique_ptr<Event>> ev;
-        if (st) for (int a = 0; a < kEvPer * kMaxSamples; a++) ev.emplace_back(new Event());
-        int nsamples = 0;
-        const int sample_stride = pre ? 2 : 8;
-
-        int it = 0;
-        double rr0 = 0., rr = 0.;
-        bool converged = false, breakdown = false;
-        while (it < o.max_iters && !converged && !breakdown) {
-            const int batch_end = std::min(o.max_iters, it + o.check_every);
-            for (; it < batch_end; it++) {
-                const int slot_old = (it & 1) ? SC_RHO_B : SC_RHO_A, slot_new = (it & 1) ? SC_RHO_A : SC_RHO_B;
-                halo_exchange_p();
-                const bool sample = st && nsamples < kMaxSamples && (it % sample_stride == 1);
-                auto mark = [&](int k) {
-                    if (sample) ev[kEvPer * nsamples + k]->record(stream);
-                };
-                mark(0);
-                for (Slab<T>& sl : slabs) launch_stencil(sl);
-                mark(1);
-                for (Slab<T>& sl : slabs) {
-                    const StencilLaunch L = stencil_dims(sl);
-                    hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, stream, sl.partials.p, (int)L.grid.x, sl.pq.p);
-                }
-                allreduce(1, 1);
-                mark(2);
-                for (size_t s = 0; s < slabs.size(); s++) {
-                    if (vec == 1) launch_update_xr<1>(slabs[s], slot_old, nparts[s]);
-                    else launch_update_xr<vec_width<T>()>(slabs[s], slot_old, nparts[s]);
-                }
-                mark(3);
-                launch_projection(nparts, false, 1);
-                mark(4);
-                if (pre) launch_precond(true);
-                mark(5);
-                if (pre) launch_projection(zparts, true, 0);
-                mark(6);
-                update_p_all(slot_old, slot_new, 0, pre, nparts);
-                mark(7);
-                if (sample) nsamples++;
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            rr0 = h_pinned[SC_RR0];
-            rr = h_pinned[SC_RR];
-            const double rho = h_pinned[(it & 1) ? SC_RHO_B : SC_RHO_A];
-            if (!std::isfinite(rr) || !std::isfinite(rr0) || !std::isfinite(rho)) breakdown = true;
-            else if (rr <= o.tol * o.tol * rr0) converged = true;  // rr = ||r'||^2 - u.w may round slightly below 0 at convergence
-            log("[shm] it=%d rel_res=%.3e", it, std::sqrt(std::fabs(rr / rr0)));
-        }
-        e_pcg.record(stream);
-
-        // ---- shift + phi (:110-111)
-        launch_shift_and_phi();
-        e_end.record(stream);
-        HIPCHK(hipMemcpyAsync(h_pinned, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        have_phi = true;
-        const auto wall1 = std::chrono::steady_clock::now();
-
-        if (st) {
-            memset(st, 0, sizeof *st);
-            st->n = n;
-            st->m = m;
-            st->S = S;
-            st->iters = it;
-            st->rel_residual = rr0 > 0. ? std::sqrt(std::fabs(rr / rr0)) : 0.;
-            st->shift = h_pinned[SC_SHIFT];
-            st->ms_conv = elapsed(e_start, e_conv);
-            st->ms_div = elapsed(e_conv, e_div);
-            HIPCHK(hipEventSynchronize(e_s2b.e));
-            st->ms_setup = last_setup_wall_ms;  // host wall time from the start of the set-up to "(A A^T)^-1 ready" (it runs beside Step 1)  // runs on stream2 concurrently with ms_conv
-            st->ms_wait_setup = elapsed(e_div, e_setup);
-            st->ms_pcg = elapsed(e_setup, e_pcg);
-            st->ms_shift = elapsed(e_pcg, e_end);
-            st->ms_total = std::chrono::duration<double, std::milli>(wall1 - wall0).count();
-            double acc[5] = {0, 0, 0, 0, 0};
-            for (int a = 0; a < nsamples; a++) {
-                auto el = [&](int i, int j) { return (double)elapsed(*ev[kEvPer * a + i], *ev[kEvPer * a + j]); };
-                acc[0] += el(0, 1);
-                acc[1] += el(2, 3);
-                acc[2] += el(3, 4) + el(5, 6);
-                acc[3] += el(6, 7);
-                acc[4] += el(4, 5);
-            }
-            const double inv = nsamples ? 1. / nsamples : 0.;
-            st->ms_stencil_avg = acc[0] * inv;
-            st->ms_update_xr_avg = acc[1] * inv;
-            st->ms_project_avg = acc[2] * inv;
-            st->ms_update_p_avg = acc[3] * inv;
-            st->ms_precond_avg = pre ? acc[4] * inv : 0.;
-            st->kernel_samples = nsamples;
-            st->preconditioner = pre ? SHM_PRECOND_DCT : SHM_PRECOND_NONE;
-            st->solver = SHM_SOLVER_PRIMAL;
-            // 11NT for the CG sweeps; the five DCT sweeps move 3T + 8TP more (read r twice + write z, 4 in-place sweeps of W)
-            st->bytes_per_iter = 11.0 * (double)N * sizeof(T) + (pre ? (double)N * (3.0 * sizeof(T) + 8.0 * sizeof(TP)) : 0.);
-        }
-        if (breakdown) throw Error(SHM_ERR_BREAKDOWN, fmt("projected CG broke down at iteration %d (rr=%g, rr0=%g)", it, rr, rr0));
-        if (!converged) throw Error(SHM_ERR_NOCONV, fmt("projected CG: max_iters=%d reached, rel. residual %.3e > tol %.1e", o.max_iters,
-                                                          std::sqrt(std::fabs(rr / rr0)), o.tol));
+        clk.e_setup.record(stream);
+        if (dual) solve_dual(o, st, clk);
+        else if (p.path == kPathPrimalFused) solve_primal_fused(o, st, pre, clk);
+        else solve_primal_classic(o, st, pre, clk);
     }
-
     // ------------------------------------------------------------------------------------------
     // global planes [ka, kb) of a field, clipped to what this process owns, packed in ascending plane order
     void copy_planes_to_host(int which, int ka, int kb, double* out) {

@@ -191,6 +191,28 @@ def test_plan_on_host(tmp_path):
     assert out.returncode == 0 and out.stdout.strip().endswith("OK"), out.stdout
 
 
+def test_every_experiment_knob_is_documented_and_read_by_something():
+    """A knob earns its branch in the library by being used: every `knob("SHM_...")` the sources read is listed by its whole name in INTEGRATION.md section 4a, and
+    a test, bench.py or a tool that is not a single round's script reads it.  A variant that was measured and rejected keeps its measurement (profiles/), not its code."""
+    names = set()
+    for d in (os.path.join(ROOT, "signed-heat-3d_amd", "csrc"), os.path.join(ROOT, "include")):
+        for f in sorted(os.listdir(d)):
+            names |= set(re.findall(r'knob\("(SHM_[A-Z0-9_]+)"\)', open(os.path.join(d, f), errors="replace").read()))
+    assert len(names) >= 10, names   # (the scan found the sources)
+    doc = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    sec = doc[doc.index("## 4a."):]
+    sec = sec[:sec.index("\n## ", 1)]
+    documented = set(re.findall(r"`(SHM_[A-Z0-9_]+)", sec))
+    assert not names - documented, sorted(names - documented)
+    readers = [os.path.join(ROOT, "bench.py")]
+    readers += [os.path.join(ROOT, "tests", f) for f in sorted(os.listdir(os.path.join(ROOT, "tests"))) if f.endswith(".py")]
+    readers += [os.path.join(ROOT, "tools", f) for f in sorted(os.listdir(os.path.join(ROOT, "tools")))
+                if os.path.isfile(os.path.join(ROOT, "tools", f)) and not re.search(r"(^r\d+_|_r\d+\.)", f)]
+    text = "".join(open(p, errors="replace").read() for p in readers)
+    used = {k for k in names if re.search(r"\b%s\b" % k, text)}
+    assert not names - used, sorted(names - used)
+
+
 def test_kernel_register_schedules():
     """The compiler's resource report of the library build (csrc/Makefile keeps it beside the .so).  Two things have cost measured time silently
     and are pinned here: a register spill in a transform kernel (n = 512 packed layout: 9 % of the sweep), and the fp64 Step-1 kernel falling out

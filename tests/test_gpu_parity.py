@@ -2,6 +2,7 @@
 (i) the committed golden fixtures (numpy/scipy oracle: literal KKT + SuperLU) and (ii) the C oracle on
 the same inputs.  Tolerances: fp64 L-infinity on phi < 1e-5 is the north-star gate; the intermediate
 stages are held to much tighter bounds because they are the same arithmetic in a different order."""
+import functools
 import numpy as np
 import pytest
 
@@ -1879,12 +1880,14 @@ print(repr(out))
     assert d["iters"] <= 2, d                                           # the direct solve: one pass, at most one of refinement
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("waves", ["16"])   # (round 6: the 4-wave shapes are A/B shapes, compiled only into -DSHM_AB_SHAPES builds)
-def test_fused_sweeps_other_workgroup_shapes_match_lu_golden(waves):
-    """The fused stencil-CG sweeps ship with 8 waves per workgroup where a grid row needs one or two waves and with 16 where it needs four or more
-    (512^3 fp64, 1024^3 fp32) -- sizes the small fixtures never reach.  SHM_FUSED_WAVES forces the 16-wave kernels onto the fixtures
-    (a fresh process: the knob is read once): same LU-golden phi from the plain and the DCT-preconditioned primal solvers, fp64 and fp32 transforms."""
+def _primal_solves_of_the_fixtures(**knobs):
+    return _primal_solves_cached(tuple(sorted(knobs.items())))
+
+
+@functools.lru_cache(maxsize=None)   # (two tests read the classic loop's run: one child process serves both)
+def _primal_solves_cached(knob_items):
+    """Plain and DCT-preconditioned primal solves of three LU fixtures in a fresh process with the knobs in its environment (the form knobs are read once per process):
+    {case/mode: (L_inf against the LU golden phi, iterations, cg_form, does DIV still claim to be available after the solve)}."""
     import os
     import subprocess
     import sys
@@ -1902,13 +1905,46 @@ for case in ("bunny_small_n32", "bunny_small_n64", "bunny_pc_n32"):
         s.set_problem(d["pos"], d["wnormal"], d["area"], float(d["lam"]), int(d["n"]), d["bbox_min"], float(d["cell"]))
         st = s.solve(tol=1e-10, scrub=not case.startswith("bunny_pc"), **kw)
         phi, _ = s.get_phi()
-        out[case + "/" + mode] = (float(np.abs(phi - d["phi"]).max()), int(st.iters), int(st.cg_form))
+        try:
+            s.get_field(s.FIELD_DIV)
+            div_served = True
+        except shm.ShmError as e:
+            div_served = False
+            assert e.status == 7, e   # SHM_ERR_STATE
+        out[case + "/" + mode] = (float(np.abs(phi - d["phi"]).max()), int(st.iters), int(st.cg_form), div_served)
         s.close()
 print(repr(out))
 """ % (ROOT, GOLDEN)
-    env = dict(os.environ, SHM_FUSED_WAVES=waves)
-    p = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=900)
+    p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **dict(knob_items)), capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout + p.stderr
-    res = eval(p.stdout.strip().splitlines()[-1])
-    for k, (err, iters, form) in res.items():
+    return eval(p.stdout.strip().splitlines()[-1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", ["16"])   # (the 8-wave shapes are what the fixtures run by default)
+def test_fused_sweeps_other_workgroup_shapes_match_lu_golden(waves):
+    """The fused stencil-CG sweeps ship with 8 waves per workgroup where a grid row needs one or two waves and with 16 where it needs four or more
+    (512^3 fp64, 1024^3 fp32) -- sizes the small fixtures never reach.  SHM_FUSED_WAVES forces the 16-wave kernels onto the fixtures
+    (a fresh process: the knob is read once): same LU-golden phi from the plain and the DCT-preconditioned primal solvers, fp64 and fp32 transforms."""
+    for k, (err, iters, form, div_served) in _primal_solves_of_the_fixtures(SHM_FUSED_WAVES=waves).items():
         assert form in (1, 4) and err < 1e-7, (k, err, iters, form)   # (4: plain CG on one GPU -- x updated on half the grid in every iteration)
+        assert not div_served, k                                      # (the loop overwrote r: the divergence is gone)
+
+
+@pytest.mark.gpu
+def test_classic_cg_loop_matches_lu_golden():
+    """The classic four-kernel loop is the shipped primal path where a grid row needs more than eight waves of vector lanes (n > 512 off the vector width, n > 1024 in
+    fp64) -- sizes no fixture reaches.  SHM_CG_CLASSIC=1 runs it on the fixtures: cg_form 0, and phi within the same 1e-7 of the LU golden vectors (the reference's
+    own fixtures) that the fused shapes are held to."""
+    res = _primal_solves_of_the_fixtures(SHM_CG_CLASSIC="1")
+    assert len(res) == 6, res
+    for k, (err, iters, form, _) in res.items():
+        assert form == 0 and err < 1e-7, (k, err, iters, form)
+
+
+@pytest.mark.gpu
+def test_divergence_is_not_served_after_a_classic_primal_solve():
+    """Every CG loop overwrites r, where the divergence b stood: get_field(DIV) after a primal solve must say SHM_ERR_STATE, not hand out the final residual.  The
+    fused loop said so; the classic loop (SHM_CG_CLASSIC=1 here) left the divergence marked as available."""
+    for k, (_, _, form, div_served) in _primal_solves_of_the_fixtures(SHM_CG_CLASSIC="1").items():
+        assert form == 0 and not div_served, (k, form, div_served)
