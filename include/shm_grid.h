@@ -99,7 +99,7 @@ typedef struct {
     int32_t check_every;      /* residual is inspected on the host every this many iterations; <=0 -> 32 (4 with the preconditioner) */
     int32_t preconditioner;   /* SHM_PRECOND_AUTO | _NONE | _DCT  (primal solver only) */
     int32_t solver;           /* SHM_SOLVER_AUTO | _PRIMAL | _DUAL | _DUAL_SLABS */
-    int32_t step1_arith;      /* SHM_STEP1_AUTO | SHM_STEP1_EXACT_F64: arithmetic of the Step-1 summation in an SHM_F64 handle (ignored by SHM_F32 handles) */
+    int32_t step1_arith;      /* SHM_STEP1_AUTO | SHM_STEP1_EXACT_F64 | SHM_STEP1_REFERENCE_F64: arithmetic of the Step-1 summation in an SHM_F64 handle (ignored by SHM_F32 handles) */
     int32_t dual_form;        /* SHM_DUAL_AUTO | _DIRECT | _EXPLICIT_S_CG | _THROUGH_GRID: which form of the dual solver runs (ABI 5; see below) */
     double step1_budget;      /* error budget of STEP1_AUTO's precision tiers on the normalised field Y; 0 -> 1e-8; accepted range [1e-12, 1e-3] (ABI 5) */
 } shm_opts;
@@ -127,8 +127,12 @@ enum { SHM_DUAL_AUTO = 0, SHM_DUAL_DIRECT = 1, SHM_DUAL_EXPLICIT_S_CG = 2, SHM_D
  * EXACT_F64: every (node, source) pair in fp64 like the reference (~1.4x the Step-1 time); Y agrees with the serial loops to 1e-11.  (Round 5: the tiered kernel with nothing far
  * and nothing dropped where every pair of the grid stays inside a block's exponent span -- lambda * grid diagonal below ~600 --, the all-fp64 kernel of rounds 1-4 otherwise.)
  * step1_budget (ABI 5) moves AUTO's three thresholds together: a budget b puts the far threshold at e^-(8 - ln(b / 1e-8)), the a-posteriori test at b / eps_far (1e-6, growing with the far terms' exponent beyond 24) and the
- * drop threshold at b / 5.  (With SHM_DEBUG_KNOBS=1 in the environment, SHM_CONV_EXACT=1 forces EXACT_F64 whatever the caller asks: A/B runs and tests.) */
-enum { SHM_STEP1_AUTO = 0, SHM_STEP1_EXACT_F64 = 1 };
+ * drop threshold at b / 5.  (With SHM_DEBUG_KNOBS=1 in the environment, SHM_CONV_EXACT=1 forces EXACT_F64 whatever the caller asks: A/B runs and tests.)
+ * REFERENCE_F64 (added within ABI 5): the most reference-like Step 1 the library has -- the all-fp64 kernel of rounds 1-4 (conv_normalize_kernel<double>: plain fp64 coordinates,
+ *            gradual underflow, the cubic body of 1.1e-16 lambda r per term; the kernel SHM_CONV_EXACT_CLASSIC=1 selects under EXACT_F64) with its fp32 far clusters and its
+ *            skip rule switched off: every (node, source) pair in fp64 whatever the grid (shm_stats.pairs_fp32 == 0).  The slowest mode; phi within 1e-9 of EXACT_F64's.
+ *            Ignored by SHM_F32 handles, like EXACT_F64. */
+enum { SHM_STEP1_AUTO = 0, SHM_STEP1_EXACT_F64 = 1, SHM_STEP1_REFERENCE_F64 = 2 };
 
 /* How the KKT system of signed_heat_grid_solver.cpp:101-107 is solved.
  * PRIMAL: projected (optionally DCT-preconditioned) CG on the N grid unknowns -- the matrix-free 7-point-stencil PCG.
@@ -281,6 +285,47 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices /* [3*nv] */,
  *   launched: host memory, another device's memory or an allocation smaller than Q points is SHM_ERR_INVALID. */
 shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered);
 shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered);
+
+/* --- audit of Step 1 at sampled grid nodes ---------------------------------------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * What it answers: what did the Step 1 that produced the resident Y cost in accuracy, at these nodes?  For every node of the list the device re-evaluates
+ *   X(x) = sum_s w_s exp(-lambda r) / r over EVERY source in the reference's arithmetic (yukawaPotential, signed_heat_3d.cpp:45-49: r = sqrt(d.d),
+ *   exp(-lambda * r) / r with the device library's sqrt, exp and a true division; the node at i * cell + bbox_min), sums it in double-double (exact products
+ *   by fma, error-free TwoSum), normalises it as the reference does and compares with the resident Y of the handle's precision:  dy = max_p |Y_p - Yref_p|.
+ *   Nothing is dropped, culled or tiered, and nothing is shared with the Step-1 kernels: no rsq seed, exponent table, block scale or grid-centred
+ *   coordinates, and the sources are read from a plain fp64 array in the caller's order (uploaded at the first audit of a problem), not from the sorted /
+ *   compacted lists Step 1 reads -- a bug there is visible here.  Cost: count * S pairs against Step 1's N * S.
+ * Classes: a node is AUDITED when its reference is finite, the device's Y is finite and lambda * r_min < 335 (r_min: distance to its nearest source; beyond
+ *   that the reference's own normalisation has lost its bits); OUT OF ZONE when lambda * r_min >= 335 (counted, excluded from max_dy);
+ *   NON-FINITE when the reference is non-finite (a source on the node) and the device's Y is too; a finite MISMATCH when exactly one of the two is finite;
+ *   NOT OWNED when its z-plane is not among this process's planes.
+ * dy_out / ratio_out (each [count] or NULL): per node dy (NaN unless both fields are finite there) and |X| / L1, L1 = sum_s |w_s|_1 g_s: how deep into
+ *   cancellation the node lies.  Nodes this process does not own get NaN in both.  max_dy / worst_node are the maximum / first argmax of dy over the audited nodes.
+ *   A random sample rarely reaches the deepest cancellation of a grid: min_ratio says how deep this one went.
+ * budget / step1_arith: the handle remembers what its last Step 1 ran.  budget is shm_opts.step1_budget of that run (1e-8 where it was 0, and in the stage entry
+ *   points) when the tiered AUTO arithmetic produced Y; 0 -- and within_budget -1 -- for EXACT_F64, REFERENCE_F64 and SHM_F32 handles, which have none.
+ *   within_budget = (max_dy <= budget && n_finite_mismatch == 0).
+ * Valid whenever SHM_FIELD_Y0 could be fetched (after shm_grid_run_conv* or any solve: no solve form reuses Y as scratch); SHM_ERR_STATE otherwise.  Y, phi
+ *   and every state flag are left as they were; two calls give bit-identical results; the result of a node does not depend on the slab plan.  Any count
+ *   (the nodes go through the device 2^22 at a time); count < 0, NULL nodes with count > 0, NULL out or an index outside [0, n^3) is SHM_ERR_INVALID.
+ *   With world > 1 the call is NOT collective: a rank audits the nodes it owns and counts the others in n_not_owned. */
+typedef struct {
+    int64_t n_audited, n_not_owned, n_nonfinite, n_out_of_zone, n_finite_mismatch;
+    double  max_dy;        /* over audited nodes */
+    int64_t worst_node;    /* flat index i + j n + k n^2; -1 when nothing was audited */
+    double  worst_ratio;   /* |X| / L1 at worst_node */
+    double  min_ratio;     /* smallest |X| / L1 among audited nodes: how deep into cancellation the sample reached */
+    double  budget;        /* budget in force in the Step 1 that produced the resident Y (step1_budget, or 1e-8); 0: that mode has none */
+    int32_t step1_arith;   /* what produced the resident Y */
+    int32_t within_budget; /* 1 / 0; -1 when budget == 0 */
+    double  ms;            /* device time of the audit */
+} shm_step1_audit;
+shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out /* [count] or NULL */, double* ratio_out /* [count] or NULL */,
+                                shm_step1_audit* out);
+/* pure host logic, no device: a deterministic stratified sample of the nodes of planes [k_begin, k_end).  Writes min(count, nodes in range) flat indices, ascending
+ * and distinct, and returns how many; a function of its arguments only.  Strata: layers of four planes counted from k_begin and, within a layer, the Step-1
+ * blocks of 8 x 8 x 4 nodes; the counts of two layers (of two blocks of a layer) differ by at most one unless the smaller stratum is taken whole. */
+int64_t shm_audit_sample_nodes(int32_t n, int32_t k_begin, int32_t k_end, int64_t count, uint64_t seed, int64_t* nodes_out);
 
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */

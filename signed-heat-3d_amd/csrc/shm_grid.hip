@@ -1,5 +1,6 @@
 // libshm_grid.so -- the C ABI (include/shm_grid.h) over shm::SolverBase; the solvers themselves live in shm_solver.hip.h (instantiated per precision in shm_solver_f64.hip / _f32.hip).
 #include "shm_host.hip.h"
+#include "shm_audit_sample.h"
 
 
 // =================================================================================================
@@ -216,6 +217,17 @@ shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* 
 }
 shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered) {
     return guard(s, [&] { s->impl->sample_device(Q, d_pts, d_phi, d_grad, n_answered); });
+}
+
+shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) {
+    return guard(s, [&] { s->impl->audit_step1(count, nodes, dy_out, ratio_out, out); });
+}
+int64_t shm_audit_sample_nodes(int32_t n, int32_t k_begin, int32_t k_end, int64_t count, uint64_t seed, int64_t* nodes_out) {
+    try {
+        return shm::audit_sample_nodes(n, k_begin, k_end, count, seed, nodes_out);
+    } catch (...) {   // (a failed allocation: nothing throws across the boundary)
+        return 0;
+    }
 }
 
 shm_status shm_comm_unique_id(void* out128) {

@@ -13,6 +13,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -566,6 +567,7 @@ struct SolverBase {
     virtual void get_isosurface(double*, int64_t*) = 0;
     virtual void sample(int64_t, const double*, double*, double*, int64_t*) = 0;
     virtual void sample_device(int64_t, const void*, void*, void*, int64_t*) = 0;
+    virtual void audit_step1(int64_t, const int64_t*, double*, double*, shm_step1_audit*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

@@ -20,6 +20,7 @@
 #include "shm_dct_gemm.hip.h"
 #include "shm_green_fft.hip.h"
 #include "shm_sample.hip.h"
+#include "shm_audit.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -87,6 +88,10 @@ struct Solver final : SolverBase {
     bool conv_tiered = false;                                  // fp64 only; SHM_CONV_EXACT=1 selects the all-fp64 kernel
     bool conv_tier_exact = false;                              // ... with every pair in its fp64 body (SHM_STEP1_EXACT_F64 where the exponent span allows)
     bool conv_tiered32 = false;                                // fp32 handles: Step 1 through the tiered kernel's packed-fp32 body
+    bool conv_reference = false;                               // SHM_STEP1_REFERENCE_F64: the all-fp64 kernel with no far cluster and nothing skipped
+    int step1_selected = SHM_STEP1_AUTO;                       // what select_step1_arith() chose, in the ABI's terms (fp32 handles: AUTO)
+    int last_step1_arith = SHM_STEP1_AUTO;                     // ... of the Step 1 that produced the resident Y, and the budget in force in it (0: that mode has none):
+    double last_step1_budget = 0.;                             // what shm_grid_audit_step1 reports
     bool fold_pq = false;                                      // fused stencil CG on one GPU: the RES sweep sums the DIR sweep's partials of p'.Kp' itself
     int fold_pq_np = 0;
     double step1_budget = 0.;                                  // shm_opts.step1_budget of the solve in progress (<= 0: kTierBudget)
@@ -531,6 +536,7 @@ struct Solver final : SolverBase {
         precond_ready = false;
         have_problem = true;
         have_conv = have_div = have_phi = have_constraints = false;
+        audit_src_ready = false;
         // (round 6: the whole-grid solver of the gathered multi-rank solve is created when a solve first takes that path -- ensure_full() -- so that a run whose solves
         // all take the slab-distributed forms never allocates whole-grid arrays on every rank)
         full_problem_set = false;
@@ -581,7 +587,10 @@ struct Solver final : SolverBase {
         return in;
     }
     void select_step1_arith(int arith) {
-        if (arith != SHM_STEP1_AUTO && arith != SHM_STEP1_EXACT_F64) throw Error(SHM_ERR_INVALID, "unknown step1_arith");
+        if (arith != SHM_STEP1_AUTO && arith != SHM_STEP1_EXACT_F64 && arith != SHM_STEP1_REFERENCE_F64) throw Error(SHM_ERR_INVALID, "unknown step1_arith");
+        // SHM_STEP1_REFERENCE_F64: the all-fp64 kernel (conv_normalize_kernel<double>, the cubic body: what SHM_CONV_EXACT_CLASSIC=1 selects under EXACT_F64), and in
+        // it every pair in fp64 -- launch_conv() switches its fp32 far clusters and its skip rule off.  fp32 handles ignore it, as they ignore EXACT_F64.
+        conv_reference = sizeof(T) == 8 && arith == SHM_STEP1_REFERENCE_F64;
         conv_tiered = sizeof(T) == 8 && arith == SHM_STEP1_AUTO && knob("SHM_CONV_EXACT") == nullptr && tier_exponent_span_ok();
         // SHM_STEP1_EXACT_F64 (round 5, late): the same kernel with nothing far and nothing dropped -- every (node, source) pair through its fp64 body, which is the
         // leaner of the two fp64 bodies since this round (exponent by integer add, four pairs of a source in flight: 22 vector instructions per pair against the
@@ -591,6 +600,7 @@ struct Solver final : SolverBase {
         conv_tiered = conv_tiered || conv_tier_exact;
         // fp32 handles (round 5): the same kernel with every kept pair in its packed-fp32 body and fp32 output; SHM_CONV32_CLASSIC=1: conv_normalize_kernel<float> (A/B)
         conv_tiered32 = sizeof(T) == 4 && knob("SHM_CONV32_CLASSIC") == nullptr && tier_exponent_span_ok();
+        step1_selected = sizeof(T) == 4 || (conv_tiered && !conv_tier_exact) ? SHM_STEP1_AUTO : conv_reference ? SHM_STEP1_REFERENCE_F64 : SHM_STEP1_EXACT_F64;
     }
     // The tiered kernel's near tier works relative to one power of two per block and inserts a term's own power of two into the exponent field by an integer
     // add (yukawa_near): valid while no evaluated term of a block is more than 2^-990 below the block's scale.  A source that is not dropped lies at most
@@ -736,7 +746,7 @@ struct Solver final : SolverBase {
             P.cexp = -lambda * 2954.639443740597;  // 2048 / ln 2
             P.S = n_clusters * conv_cluster<T>();
             P.n_clusters = n_clusters;
-            P.far_gap = (float)conv_far_gap;
+            P.far_gap = conv_reference ? 3.0e38f : (float)conv_far_gap;   // (REFERENCE_F64: no cluster is far)
             // shm_opts.step1_budget b (default kTierBudget = 1e-8) moves the three thresholds that derive from the budget together: the far threshold G by -ln(b / 1e-8)
             // (terms e^-G below the dominant one carry the packed-fp32 error eps_far: G = 8 at 1e-8), the a-posteriori test (b / eps_far) and the drop threshold (b / 5)
             const double budget = step1_budget > 0. ? step1_budget : kTierBudget;
@@ -747,7 +757,7 @@ struct Solver final : SolverBase {
                 const double ratio = budget / kTierEpsFar;
                 P.far_redo_ratio = ratio > 0. ? (float)ratio : 3.0e38f;
             }
-            P.skip_base = conv_tier_exact ? 3.0e38f : (float)std::min(conv_tiered ? conv_tier_skip_base - g_shift : conv_skip_base, 3.0e38);
+            P.skip_base = conv_tier_exact || conv_reference ? 3.0e38f : (float)std::min(conv_tiered ? conv_tier_skip_base - g_shift : conv_skip_base, 3.0e38);
             {   // the tiered kernels' drop rule (round 6; shm_conv_tiered.hip.h): eps follows the budget in the fp64 solve (a fifth of it, as before)
                 const double eps = conv_tier_exact ? 0. : sizeof(T) == 8 ? conv_drop_eps64 * (budget / kTierBudget) : conv_drop_eps32;
                 const double eps_soft = 0.875 * eps, tau = eps_soft / conv_drop_K, tau_hard = 0.125 * eps / (double)std::max<int64_t>(1, S);
@@ -907,6 +917,8 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
         exchange_Y_halos();
         have_conv = true;
+        last_step1_arith = step1_selected;
+        last_step1_budget = sizeof(T) == 8 && conv_tiered && !conv_tier_exact ? (step1_budget > 0. ? step1_budget : kTierBudget) : 0.;
     }
     // ghost planes of Y0, Y1, Y2 from the neighbouring slabs (device copies / ncclSend+ncclRecv): the divergence reads Y2 one plane
     // below (and above, at the global top), the fast integration reads all three one plane below
@@ -3499,6 +3511,101 @@ struct Solver final : SolverBase {
         launch_sample<T>(Q, (const T*)pts, (T*)out, (T*)grad);
         const int64_t a = sample_end();
         if (n_answered) *n_answered = a;
+    }
+
+    // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------
+    static constexpr int64_t kAuditChunk = (int64_t)1 << 22;   // nodes per launch: bounds the device buffers (36 B per node) whatever count is
+    DevArray<double> d_audit_src;      // [6][S]: pos x, y, z, wnormal x, y, z -- fp64, planar, in the caller's order; uploaded at the first audit of a problem
+    bool audit_src_ready = false;
+    DevArray<int64_t> d_audit_nodes;
+    DevArray<double> d_audit_out;      // [3][chunk]: dy, ratio, lambda r_min
+    DevArray<int> d_audit_cls;
+    std::unique_ptr<Event> audit_ev[2];
+
+    void audit_step1(int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) override {
+        if (!out) throw Error(SHM_ERR_INVALID, "audit_step1: null out");
+        if (count < 0) throw Error(SHM_ERR_INVALID, "audit_step1: count < 0");
+        if (count > 0 && !nodes) throw Error(SHM_ERR_INVALID, "audit_step1: null nodes");
+        need_problem();
+        if (!have_conv) throw Error(SHM_ERR_STATE, "no Y: Step 1 has not run (run_conv or a solve)");
+        for (int64_t q = 0; q < count; q++)
+            if (nodes[q] < 0 || nodes[q] >= (int64_t)N) throw Error(SHM_ERR_INVALID, fmt("audit_step1: node %lld outside [0, n^3)", (long long)nodes[q]));
+        HIPCHK(hipSetDevice(cfg.device));
+        if (!audit_src_ready) {
+            std::vector<double> planar((size_t)S * 6);
+            for (int64_t s = 0; s < S; s++)
+                for (int a = 0; a < 3; a++) {
+                    planar[(size_t)a * S + s] = h_pos[3 * s + a];
+                    planar[(size_t)(3 + a) * S + s] = h_wn[3 * s + a];
+                }
+            d_audit_src.upload(planar, stream);
+            audit_src_ready = true;
+        }
+        for (auto& e : audit_ev)
+            if (!e) e.reset(new Event());
+        memset(out, 0, sizeof *out);
+        out->worst_node = -1;
+        out->min_ratio = std::numeric_limits<double>::infinity();
+        out->budget = last_step1_budget;
+        out->step1_arith = last_step1_arith;
+        AuditParams P;
+        P.n = n;
+        P.kp0 = slabs.front().k0;
+        P.kp1 = slabs.back().k1;
+        P.cell = cell;
+        P.lambda = lambda;
+        P.S = S;
+        for (int a = 0; a < 3; a++) P.bbox_min[a] = bbox_min[a];
+        const int64_t C = std::min(count, kAuditChunk);
+        std::vector<double> h_out((size_t)std::max<int64_t>(C, 1) * 3);
+        std::vector<int> h_cls((size_t)std::max<int64_t>(C, 1));
+        if (C > 0) {
+            d_audit_nodes.alloc((size_t)C);
+            d_audit_out.alloc((size_t)C * 3);
+            d_audit_cls.alloc((size_t)C);
+        }
+        for (int64_t q0 = 0; q0 < count; q0 += C) {
+            const int64_t m = std::min(C, count - q0);
+            HIPCHK(hipMemcpyAsync(d_audit_nodes.p, nodes + q0, (size_t)m * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+            audit_ev[0]->record(stream);
+            const unsigned grid = (unsigned)((m + kAuditNodesPerBlock - 1) / kAuditNodesPerBlock);
+            for (size_t s = 0; s < slabs.size(); s++) {
+                P.k0 = slabs[s].k0;
+                P.k1 = slabs[s].k1;
+                P.mark_unowned = s == 0;
+                hipLaunchKernelGGL((step1_audit_kernel<T>), dim3(grid), dim3(kBlock), 0, stream, P, m, d_audit_nodes.p, d_audit_src.p, slabs[s].Y0.p, slabs[s].Y1.p,
+                                   slabs[s].Y2.p, d_audit_out.p, d_audit_out.p + C, d_audit_out.p + 2 * C, d_audit_cls.p);
+            }
+            HIPCHK(hipGetLastError());
+            audit_ev[1]->record(stream);
+            HIPCHK(hipMemcpyAsync(h_out.data(), d_audit_out.p, (size_t)C * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(h_cls.data(), d_audit_cls.p, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            out->ms += (double)elapsed(*audit_ev[0], *audit_ev[1]);
+            // max / argmax on the host, in the order of the list: the first of equal maxima is the worst node
+            for (int64_t a = 0; a < m; a++) {
+                const double dy = h_out[(size_t)a], ratio = h_out[(size_t)(C + a)];
+                if (dy_out) dy_out[q0 + a] = dy;
+                if (ratio_out) ratio_out[q0 + a] = ratio;
+                switch (h_cls[(size_t)a]) {
+                    case kAuditAudited:
+                        out->n_audited++;
+                        if (out->worst_node < 0 || dy > out->max_dy) {
+                            out->max_dy = dy;
+                            out->worst_node = nodes[q0 + a];
+                            out->worst_ratio = ratio;
+                        }
+                        out->min_ratio = std::min(out->min_ratio, ratio);
+                        break;
+                    case kAuditOutOfZone: out->n_out_of_zone++; break;
+                    case kAuditNonFinite: out->n_nonfinite++; break;
+                    case kAuditMismatch: out->n_finite_mismatch++; break;
+                    default: out->n_not_owned++; break;
+                }
+            }
+        }
+        if (out->n_audited == 0) out->min_ratio = 0.;
+        out->within_budget = out->budget > 0. ? (out->max_dy <= out->budget && out->n_finite_mismatch == 0 ? 1 : 0) : -1;
     }
 
     void get_isosurface(double* vertices, int64_t* triangles) override {

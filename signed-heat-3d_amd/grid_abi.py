@@ -20,7 +20,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
-               "shm_grid_sample", "shm_grid_sample_device", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
+               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
 class ShmError(RuntimeError):
@@ -55,6 +55,16 @@ class ShmStats(C.Structure):
                 ("ms_update_xr_avg", C.c_double), ("ms_project_avg", C.c_double), ("ms_update_p_avg", C.c_double),
                 ("ms_precond_avg", C.c_double), ("kernel_samples", C.c_int32), ("preconditioner", C.c_int32),
                 ("solver", C.c_int32), ("bytes_per_iter", C.c_double), ("cg_form", C.c_int32), ("pairs_fp64", C.c_double), ("pairs_fp32", C.c_double), ("conv_launches", C.c_int32), ("pairs_redone", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ShmStep1Audit(C.Structure):
+    """shm_step1_audit of include/shm_grid.h (shm_grid_audit_step1)."""
+    _fields_ = [("n_audited", C.c_int64), ("n_not_owned", C.c_int64), ("n_nonfinite", C.c_int64), ("n_out_of_zone", C.c_int64),
+                ("n_finite_mismatch", C.c_int64), ("max_dy", C.c_double), ("worst_node", C.c_int64), ("worst_ratio", C.c_double), ("min_ratio", C.c_double),
+                ("budget", C.c_double), ("step1_arith", C.c_int32), ("within_budget", C.c_int32), ("ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -102,6 +112,10 @@ def load_library():
     lib.shm_grid_get_isosurface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shm_grid_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shm_grid_sample_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "shm_grid_audit_step1"):   # added within ABI 5: found by symbol (another build named by SHM_GRID_LIB may predate it)
+        lib.shm_grid_audit_step1.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmStep1Audit)]
+        lib.shm_audit_sample_nodes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p]
+        lib.shm_audit_sample_nodes.restype = C.c_int64
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -118,6 +132,14 @@ def plan_slab(n, nslabs, slab):
     k0, k1 = C.c_int32(), C.c_int32()
     lib.shm_plan_slab(n, nslabs, slab, C.byref(k0), C.byref(k1))
     return k0.value, k1.value
+
+
+def audit_sample_nodes(n, k_begin, k_end, count, seed=0):
+    """A deterministic stratified sample of the nodes of planes [k_begin, k_end) (shm_audit_sample_nodes: pure host logic, no GPU): ascending flat indices."""
+    lib = load_library()
+    out = np.empty(max(0, min(int(count), max(0, int(k_end) - int(k_begin)) * int(n) * int(n))), dtype=np.int64)
+    got = lib.shm_audit_sample_nodes(int(n), int(k_begin), int(k_end), int(out.size), int(seed) & 0xFFFFFFFFFFFFFFFF, out.ctypes.data) if out.size else 0
+    return out[:got]
 
 
 def step1_plane_weights(pos, wnormal, lam, n, bbox_min, cell, precision=SHM_F64):
@@ -210,7 +232,7 @@ class GridSolver:
 
     SOLVER = {"auto": 0, "primal": 1, "dual": 2, "dual_slabs": 3}
 
-    STEP1 = {"auto": 0, "exact_f64": 1}
+    STEP1 = {"auto": 0, "exact_f64": 1, "reference_f64": 2}
 
     DUAL_FORM = {"auto": 0, "direct": 1, "explicit_s_cg": 2, "through_grid": 3}
 
@@ -331,6 +353,24 @@ class GridSolver:
         self._chk(self._lib.shm_grid_sample_device(self._h, Q, points.data_ptr() if Q else None, phi.data_ptr() if Q else None,
                                                    g.data_ptr() if grad and Q else None, C.byref(na)))
         return (phi, g, na.value) if grad else (phi, na.value)
+
+    def audit_step1(self, nodes=None, count=4096, seed=0, per_node=False):
+        """What the Step 1 behind the resident Y cost at sampled nodes (shm_grid_audit_step1): the struct as a dict, plus "nodes", "dy" and "ratio" with
+        per_node=True.  nodes=None audits audit_sample_nodes(count, seed) of the owned planes."""
+        if nodes is None:
+            k0, k1 = self.owned_planes()
+            nodes = audit_sample_nodes(self.n, k0, k1, count, seed)
+        nodes = np.ascontiguousarray(nodes, dtype=np.int64).reshape(-1)
+        Q = nodes.size
+        dy = np.empty(Q) if per_node else None
+        ratio = np.empty(Q) if per_node else None
+        a = ShmStep1Audit()
+        self._chk(self._lib.shm_grid_audit_step1(self._h, Q, nodes.ctypes.data if Q else None, dy.ctypes.data if per_node and Q else None,
+                                                 ratio.ctypes.data if per_node and Q else None, C.byref(a)))
+        out = a.as_dict()
+        if per_node:
+            out.update(nodes=nodes, dy=dy, ratio=ratio)
+        return out
 
     def compute_distance(self, pos, wnormal, area, lam, n, bbox_min, cell, **kw):
         """One-shot convenience mirroring shm_grid_compute_distance (set_problem + solve + get_phi)."""

@@ -85,6 +85,17 @@ class SignedHeatGridSolver {
 
     bool VERBOSE = true;
     bool exactStep1 = false;   // backend knob (no counterpart in the reference): Step 1 entirely in fp64, shm_opts.step1_arith
+    bool referenceStep1 = false;   // ... in the all-fp64 kernel with nothing far and nothing skipped (SHM_STEP1_REFERENCE_F64; takes precedence)
+
+    // What the Step 1 of the last computeDistance() cost on Y, audited on the device at a stratified sample of `count` grid nodes (shm_grid_audit_step1)
+    shm_step1_audit auditStep1(size_t count = 4096, uint64_t seed = 0) {
+        if (!handle) throw std::runtime_error("auditStep1: computeDistance has not been called");
+        std::vector<int64_t> nodes(count < nx * ny * nz ? count : nx * ny * nz);
+        int64_t got = shm_audit_sample_nodes((int32_t)nx, 0, (int32_t)nz, (int64_t)nodes.size(), seed, nodes.data());
+        shm_step1_audit a{};
+        if (shm_grid_audit_step1(handle, got, nodes.data(), nullptr, nullptr, &a) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        return a;
+    }
 
   private:
     shm_solver* handle = nullptr;
@@ -127,7 +138,7 @@ class SignedHeatGridSolver {
         shm_opts opts{};
         opts.fast_integration = options.fastIntegration;
         opts.scrub_nonfinite = scrub;
-        opts.step1_arith = exactStep1 ? SHM_STEP1_EXACT_F64 : SHM_STEP1_AUTO;
+        opts.step1_arith = referenceStep1 ? SHM_STEP1_REFERENCE_F64 : exactStep1 ? SHM_STEP1_EXACT_F64 : SHM_STEP1_AUTO;
         Vector<double> phi(nx * ny * nz);
         if (VERBOSE) std::cerr << "Steps 1 & 2... Step 3..." << std::endl;
         if (shm_grid_compute_distance(handle, &src, &grid, &opts, phi.data(), nullptr) != SHM_OK)

@@ -1,5 +1,6 @@
 // Flat C wrapper around the C++ host layer so that Python tests / bench.py can drive the same code path the
 // headless CLI uses (ctypes cannot call C++ methods).  Not part of the drop-in boundary.
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -34,6 +35,21 @@ extern "C" {
 
 const char* shmh_last_error(void) { return g_err.c_str(); }
 
+// Step-1 arithmetic of the solves that follow: 0 AUTO, 1 EXACT_F64, 2 REFERENCE_F64 (GridBackendOptions::exactStep1 / referenceStep1); takes effect with the
+// handle's first solve, so call it before shmh_compute_distance.  Kept apart from shmh_new, whose signature existing callers rely on.
+void* shmh_new_arith(int device, int precision, double tol, int max_iters, int local_slabs, int verbose, int step1_arith) {
+    GridBackendOptions b;
+    b.device = device;
+    b.precision = precision;
+    b.tol = tol;
+    b.maxIters = max_iters;
+    b.localSlabs = local_slabs;
+    b.exactStep1 = step1_arith == SHM_STEP1_EXACT_F64;
+    b.referenceStep1 = step1_arith == SHM_STEP1_REFERENCE_F64;
+    Host* h = new Host(b);
+    h->solver.VERBOSE = verbose != 0;
+    return h;
+}
 void* shmh_new(int device, int precision, double tol, int max_iters, int local_slabs, int verbose) {
     GridBackendOptions b;
     b.device = device;
@@ -172,6 +188,12 @@ int shmh_sample(void* hv, int64_t Q, const double* pts, double* phi_out, double*
             for (int64_t a = 0; a < Q; a++)
                 for (int b = 0; b < 3; b++) grad_out[3 * a + b] = g[(size_t)a][b];
     });
+}
+
+// auditStep1 through the C++ class: the Step 1 of the last compute_distance at a stratified sample of `count` nodes.
+int shmh_audit_step1(void* hv, int64_t count, uint64_t seed, shm_step1_audit* out) {
+    Host* h = (Host*)hv;
+    return guard([&] { *out = h->solver.auditStep1((size_t)std::max<int64_t>(count, 0), seed); });
 }
 
 // Wall time of the C++ drop-in call alone -- computeDistance() returning its VectorXd, as the reference's main.cpp:90-91 consumes it --

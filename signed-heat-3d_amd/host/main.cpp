@@ -22,6 +22,8 @@ static void usage() {
                  "      --h <hCoef>       Grid resolution: n = 2*2^(hCoef+3) nodes per side (default 0 -> 16^3)\n"
                  "      --t <tCoef>       Diffusion time coefficient (default 1)\n      --fp32            Compute in fp32 (default fp64)\n"
                  "      --exact-step1     fp64 only: every (node, source) pair of Step 1 in fp64 like the reference (default: error-budgeted tiers)\n"
+                 "      --reference-step1 fp64 only: Step 1 in the all-fp64 kernel, nothing far, nothing skipped (the slowest; exclusive with --exact-step1)\n"
+                 "      --audit <count>   Audit Step 1 on the device at <count> sampled grid nodes against the reference's arithmetic; exit status 3 over budget\n"
                  "      --tol <x>         Projected-CG relative residual tolerance\n      --device <i>      HIP device ordinal\n"
                  "      --out <file>      Write phi as raw little-endian float64 (n^3 values, x fastest)\n"
                  "      --iso <value>     Contour phi at this value (default 0) and export the isosurface\n"
@@ -33,6 +35,7 @@ static void usage() {
 int main(int argc, char** argv) {
     std::string path, out, exportPath, queryPath, queryOut;
     double isoval = 0.;
+    long long auditCount = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
     bool verbose = false;
@@ -53,6 +56,8 @@ int main(int argc, char** argv) {
         else if (s == "--t") opts.tCoef = atof(need("--t"));
         else if (s == "--fp32") backend.precision = 32;
         else if (s == "--exact-step1") backend.exactStep1 = true;
+        else if (s == "--reference-step1") backend.referenceStep1 = true;
+        else if (s == "--audit") auditCount = atoll(need("--audit"));
         else if (s == "--tol") backend.tol = atof(need("--tol"));
         else if (s == "--device") backend.device = atoi(need("--device"));
         else if (s == "--out") out = need("--out");
@@ -67,10 +72,15 @@ int main(int argc, char** argv) {
         std::cerr << "--query and --query-out go together." << std::endl;
         return EXIT_FAILURE;
     }
+    if (backend.exactStep1 && backend.referenceStep1) {
+        std::cerr << "--exact-step1 and --reference-step1 exclude each other." << std::endl;
+        return EXIT_FAILURE;
+    }
     if (path.empty()) {
         std::cerr << "Please specify a mesh file as argument." << std::endl;
         return EXIT_FAILURE;
     }
+    bool auditFailed = false;
     try {
         SignedHeatGridSolver solver(backend);
         solver.VERBOSE = verbose;
@@ -88,6 +98,18 @@ int main(int argc, char** argv) {
         if (verbose) std::cerr << "Solve time (s): " << std::chrono::duration<double>(t2 - t1).count() << std::endl;
         const auto mm = std::minmax_element(phi.begin(), phi.end());
         std::cerr << "min: " << *mm.first << "\tmax: " << *mm.second << std::endl;  // src/main.cpp:101
+        if (auditCount >= 0) {
+            const shm_step1_audit a = solver.auditStep1((size_t)auditCount);
+            const char* verdict = a.within_budget < 0 ? "no budget in this mode" : a.within_budget ? "within budget" : "OVER BUDGET";
+            char line[512];
+            snprintf(line, sizeof line,
+                     "step1 audit: max_dy %.3e budget %.1e %s worst_node %lld worst_ratio %.3e min_ratio %.3e audited %lld out_of_zone %lld nonfinite %lld "
+                     "mismatch %lld not_owned %lld ms %.3f",
+                     a.max_dy, a.budget, verdict, (long long)a.worst_node, a.worst_ratio, a.min_ratio, (long long)a.n_audited, (long long)a.n_out_of_zone,
+                     (long long)a.n_nonfinite, (long long)a.n_finite_mismatch, (long long)a.n_not_owned, a.ms);
+            std::cerr << line << std::endl;
+            auditFailed = a.n_finite_mismatch > 0 || a.within_budget == 0;
+        }
         if (!out.empty()) {
             std::ofstream f(out, std::ios::binary);
             f.write((const char*)phi.data(), (std::streamsize)(phi.size() * sizeof(double)));
@@ -125,5 +147,5 @@ int main(int argc, char** argv) {
         std::cerr << "error: " << e.what() << std::endl;
         return 2;
     }
-    return EXIT_SUCCESS;
+    return auditFailed ? 3 : EXIT_SUCCESS;
 }

@@ -26,6 +26,7 @@ struct GridBackendOptions {
     int maxIters = 0;
     int localSlabs = 1;
     bool exactStep1 = false;   // shm_opts.step1_arith = SHM_STEP1_EXACT_F64: every (node, source) pair of Step 1 in the reference's fp64 arithmetic
+    bool referenceStep1 = false;   // shm_opts.step1_arith = SHM_STEP1_REFERENCE_F64: the all-fp64 kernel, nothing far, nothing skipped (takes precedence over exactStep1)
 };
 
 Vector3 centroid(const VertexPositionGeometry& geometry);                       // signed_heat_3d.cpp:3-12

@@ -1,5 +1,6 @@
 #include "signed_heat_grid_solver.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <iostream>
@@ -61,7 +62,7 @@ VectorXd SignedHeatGridSolver::solveOnDevice(bool scrub, const SignedHeat3DOptio
     opts.scrub_nonfinite = scrub ? 1 : 0;
     opts.tol = backend.tol;
     opts.max_iters = backend.maxIters;
-    opts.step1_arith = backend.exactStep1 ? SHM_STEP1_EXACT_F64 : SHM_STEP1_AUTO;
+    opts.step1_arith = backend.referenceStep1 ? SHM_STEP1_REFERENCE_F64 : backend.exactStep1 ? SHM_STEP1_EXACT_F64 : SHM_STEP1_AUTO;
     VectorXd phi(nx * ny * nz);
     if (VERBOSE) std::cerr << "Steps 1 & 2..." << std::endl;
     const shm_status rc = shm_grid_compute_distance(handle, &src, &grid, &opts, phi.data(), &stats);
@@ -85,6 +86,16 @@ void SignedHeatGridSolver::isosurface(double isoval, std::vector<Vector3>& verti
     faces.resize((size_t)nt);
     for (int64_t a = 0; a < nv; a++) vertices[(size_t)a] = Vector3{v[3 * a], v[3 * a + 1], v[3 * a + 2]};
     for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
+}
+
+shm_step1_audit SignedHeatGridSolver::auditStep1(size_t count, uint64_t seed) {
+    if (!handle) throw std::runtime_error("auditStep1: computeDistance has not been called");
+    std::vector<int64_t> nodes(std::min(count, nx * ny * nz));
+    const int64_t got = shm_audit_sample_nodes((int32_t)nx, 0, (int32_t)nz, (int64_t)nodes.size(), seed, nodes.data());
+    shm_step1_audit a{};
+    if (shm_grid_audit_step1(handle, got, nodes.data(), nullptr, nullptr, &a) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_audit_step1: ") + shm_grid_last_error(handle));
+    return a;
 }
 
 std::vector<double> SignedHeatGridSolver::evaluateFunction(const std::vector<Vector3>& q, std::vector<Vector3>* gradients) {

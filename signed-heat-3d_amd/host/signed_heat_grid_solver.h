@@ -45,6 +45,10 @@ class SignedHeatGridSolver {
     // With gradients != nullptr it is resized to q.size() and receives the gradient of the trilinear interpolant in each point's cell.
     std::vector<double> evaluateFunction(const std::vector<Vector3>& q, std::vector<Vector3>* gradients = nullptr);
 
+    // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
+    // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).
+    shm_step1_audit auditStep1(size_t count = 4096, uint64_t seed = 0);
+
     // Read-only views of the grid block the reference keeps private (used by the CLI / tests / the Polyscope
     // side effect `registerVolumeGrid("domain", {nx,ny,nz}, bboxMin, bboxMax)`, :35 / :143).
     size_t gridSize() const { return nx; }

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .grid_abi import ShmStats, load_library
+from .grid_abi import ShmStats, ShmStep1Audit, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -28,6 +28,9 @@ def load_host_library():
     lib.shmh_last_error.restype = C.c_char_p
     lib.shmh_new.restype = C.c_void_p
     lib.shmh_new.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int]
+    lib.shmh_new_arith.restype = C.c_void_p
+    lib.shmh_new_arith.argtypes = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int]
+    lib.shmh_audit_step1.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(ShmStep1Audit)]
     lib.shmh_delete.argtypes = [C.c_void_p]
     lib.shmh_delete.restype = None
     lib.shmh_load.argtypes = [C.c_void_p, C.c_char_p]
@@ -47,9 +50,11 @@ def load_host_library():
 class HostSolver:
     """SignedHeatGridSolver (C++ mirror) + a loaded mesh / point cloud."""
 
-    def __init__(self, path=None, device=0, precision=64, tol=0.0, max_iters=0, local_slabs=1, verbose=False):
+    STEP1 = {"auto": 0, "exact_f64": 1, "reference_f64": 2}   # GridBackendOptions::exactStep1 / referenceStep1
+
+    def __init__(self, path=None, device=0, precision=64, tol=0.0, max_iters=0, local_slabs=1, verbose=False, step1="auto"):
         self._lib = load_host_library()
-        self._h = C.c_void_p(self._lib.shmh_new(device, precision, tol, max_iters, local_slabs, int(verbose)))
+        self._h = C.c_void_p(self._lib.shmh_new_arith(device, precision, tol, max_iters, local_slabs, int(verbose), self.STEP1[step1]))
         if path is not None:
             self.load(path)
 
@@ -119,3 +124,10 @@ class HostSolver:
         g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
         self._chk(self._lib.shmh_sample(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None))
         return (phi, g) if grad else phi
+
+    def audit_step1(self, count=4096, seed=0):
+        """auditStep1 of the C++ mirror: the Step 1 of the last compute_distance audited on the device at a stratified sample of `count` nodes
+        (shm_grid_audit_step1); the struct as a dict."""
+        a = ShmStep1Audit()
+        self._chk(self._lib.shmh_audit_step1(self._h, int(count), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(a)))
+        return a.as_dict()
