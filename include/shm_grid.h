@@ -286,6 +286,28 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices /* [3*nv] */,
 shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered);
 shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered);
 
+/* --- indexed isosurface of the resident phi, built on the device in a canonical order ------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the three entry points by their symbols (dlsym).
+ * The same surface as shm_grid_isosurface (marching cubes: the case table, inside = phi < isovalue, one vertex per cut grid edge at
+ *   idx*cell + bbox_min per axis plus tt*cell on the edge's axis, tt = (iso - va)/(vb - va) from the edge's lower node, all fp64 from the handle's nodes),
+ *   but numbered, welded and kept on the device: nothing is sorted or hashed on the host, and the mesh stays resident in library-owned device memory.
+ * Order (a function of phi, isovalue and this process's plane range only -- not of local_slabs, the slab plan or any atomic):
+ *   vertices ascend in 3*g + axis, g = i + j*n + k*n^2 the edge's lower node, axis 0/1/2 = x/y/z;
+ *   triangles ascend in (g of the cell's node 000, position in the case's table entry), corners in the table's order -- the order shm_grid_isosurface's
+ *   sort produces, so the two meshes differ only by a renumbering of the vertices.  Two calls give bit-identical buffers.
+ * Coverage: as shm_grid_isosurface -- the cells whose lower z-plane this process owns, the plane above the last owned one read from the ghost layer
+ *   (exchanged inside the call: COLLECTIVE with world > 1).  Indices are local to the process's vertex array; seam vertices are duplicated between ranks.
+ * shm_grid_isosurface_indexed: builds the mesh and returns the counts.  Valid whenever shm_grid_isosurface is; SHM_ERR_STATE without a resident phi.
+ *   An empty surface is SHM_OK with 0, 0.  phi, Y, the mesh of shm_grid_isosurface and every state flag are left as they were.  Ids are 64-bit throughout.
+ * shm_grid_get_isosurface_indexed: host buffers, vertices always fp64.  shm_grid_get_isosurface_indexed_device: device buffers on the handle's device,
+ *   vertices in the handle's precision (the fp64 position rounded once on the store for SHM_F32), triangles int64; synchronous; both pointers are checked
+ *   (hipPointerGetAttributes / hipMemGetAddressRange) before anything is enqueued: host memory, another device's memory or an allocation that is too
+ *   small is SHM_ERR_INVALID.  Both getters return SHM_ERR_STATE before a build and after anything that replaced or invalidated phi (a new solve,
+ *   shm_grid_set_problem, a stage entry point that overwrites it), and accept NULL for an empty mesh. */
+shm_status shm_grid_isosurface_indexed(shm_solver* s, double isovalue, int64_t* n_vertices, int64_t* n_triangles);
+shm_status shm_grid_get_isosurface_indexed(shm_solver* s, double* vertices /* [3*nv] */, int64_t* triangles /* [3*nt] */);
+shm_status shm_grid_get_isosurface_indexed_device(shm_solver* s, void* d_vertices /* [3*nv], handle precision */, void* d_triangles /* [3*nt] int64 */);
+
 /* --- audit of Step 1 at sampled grid nodes ---------------------------------------------------------------------------------------------------------------
  * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
  * What it answers: what did the Step 1 that produced the resident Y cost in accuracy, at these nodes?  For every node of the list the device re-evaluates

@@ -212,6 +212,16 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices, int64_t* tri
     return guard(s, [&] { s->impl->get_isosurface(vertices, triangles); });
 }
 
+shm_status shm_grid_isosurface_indexed(shm_solver* s, double isovalue, int64_t* n_vertices, int64_t* n_triangles) {
+    return guard(s, [&] { s->impl->isosurface_indexed(isovalue, n_vertices, n_triangles); });
+}
+shm_status shm_grid_get_isosurface_indexed(shm_solver* s, double* vertices, int64_t* triangles) {
+    return guard(s, [&] { s->impl->get_isosurface_indexed(vertices, triangles); });
+}
+shm_status shm_grid_get_isosurface_indexed_device(shm_solver* s, void* d_vertices, void* d_triangles) {
+    return guard(s, [&] { s->impl->get_isosurface_indexed_device(d_vertices, d_triangles); });
+}
+
 shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered) {
     return guard(s, [&] { s->impl->sample(Q, pts, phi_out, grad_out, n_answered); });
 }

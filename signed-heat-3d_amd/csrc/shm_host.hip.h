@@ -567,6 +567,9 @@ struct SolverBase {
     virtual void get_isosurface(double*, int64_t*) = 0;
     virtual void sample(int64_t, const double*, double*, double*, int64_t*) = 0;
     virtual void sample_device(int64_t, const void*, void*, void*, int64_t*) = 0;
+    virtual void isosurface_indexed(double, int64_t*, int64_t*) = 0;
+    virtual void get_isosurface_indexed(double*, int64_t*) = 0;
+    virtual void get_isosurface_indexed_device(void*, void*) = 0;
     virtual void audit_step1(int64_t, const int64_t*, double*, double*, shm_step1_audit*) = 0;
 };
 

@@ -1,0 +1,274 @@
+// Indexed, welded marching-cubes mesh of the resident phi, built on the device in a canonical order (shm_grid_isosurface_indexed).
+// Case table, inside rule and vertex arithmetic are those of iso_mc_kernel (shm_kernels.hip.h); what differs is the assembly: one vertex per cut grid edge,
+// numbered by a scan instead of a host hash map, and triangles written at scanned offsets instead of through an atomic counter.
+//
+// Order.  Vertices ascend in 3*g + axis (g = i + j*n + k*n^2 the edge's lower node, axis 0/1/2 = x/y/z); triangles ascend in (g of the cell's node 000, tr),
+// corners in the table's order.  Both follow from one rule: every pass maps lane -> node identically, nodes ascend in g, and a node's rank is a prefix sum.
+//
+// Passes (one launch per slab each; a launch never waits for another workgroup):
+//   count   one lane per node, tiles of kIsoTile nodes per workgroup: the cut +x/+y/+z edges the node owns and kMcCount of the cell it is corner 000 of;
+//           wave totals from ballots, one pair of totals per tile
+//   scan    one workgroup: exclusive prefix sums of the tile totals (64-bit); the last entries are nv and nt
+//   verts   same lanes, same ballots: position at tile offset + rank, and the node's record (first vertex id << 3 | cut bits) for the triangle pass
+//   tris    same lanes: three ids per triangle from the records of the edges' lower nodes
+// Tiles with no vertex (no triangle) return after reading their two offsets, so away from the surface only the count pass reads phi.
+// The record array is indexed by the node's position in the PROCESS's plane range, so a cell in a slab's top layer finds the edges of the plane above in
+// the same array, whichever slab wrote them.  Records of nodes that own no cut edge are never read and never written.
+// Node and edge indices are 64-bit throughout (3 n^3 exceeds 2^31 at 1024^3 and 2^32 a little above it).
+#pragma once
+#include "shm_kernels.hip.h"
+
+namespace shm {
+
+constexpr int kIsoChunks = 8;                     // chunks of kBlock nodes a workgroup walks in order
+constexpr int kIsoTile = kBlock * kIsoChunks;     // nodes per tile
+constexpr int kIsoScanBlock = 1024;
+
+struct IsoIdxParams {
+    int n;
+    int k0;          // global plane of the slab's first owned plane: grid plane k sits at (k - k0 + 1) * n^2 of phi (ghost layout)
+    int kb;          // first plane of the process
+    int ktop;        // last plane that carries vertices, min(ke, n-1); cells and z edges exist for k < ktop
+    int nplanes;     // node planes this launch covers, from k0 upwards (the last slab's reach the ghost plane when ke < n)
+    double bbox_min[3];
+    double cell;
+    double iso;
+};
+
+// What one lane knows about its node.  v[q] is phi at corner q of the cell the node is corner 000 of; a corner past the grid (or past ktop) repeats the
+// nearest one inside, so every load is in bounds and an edge that does not exist is never seen as cut.
+struct IsoNode {
+    int i, j, k;
+    int cut;      // bit a: the edge from this node along axis a is cut
+    int inside;   // the cell's case
+    int ntri;     // kMcCount of the case, 0 where the node is corner 000 of no cell
+    double v[8];
+};
+
+template <typename T>
+__device__ __forceinline__ void iso_node_load(const IsoIdxParams& P, const T* __restrict__ phi, int kk, int j, int i, size_t plane, IsoNode& nd) {
+    const int n = P.n;
+    const int k = P.k0 + kk;
+    const int di = i < n - 1 ? 1 : 0, dj = j < n - 1 ? 1 : 0, dk = k < P.ktop ? 1 : 0;
+    const size_t base = (size_t)(kk + 1) * plane + (size_t)j * n + i;
+    int inside = 0;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        nd.v[q] = (double)phi[base + (size_t)((q & 1) * di) + (size_t)(((q >> 1) & 1) * dj) * (size_t)n + (size_t)(((q >> 2) & 1) * dk) * plane];
+        inside |= (nd.v[q] < P.iso ? 1 : 0) << q;
+    }
+    nd.i = i; nd.j = j; nd.k = k;
+    nd.inside = inside;
+    const int in0 = inside & 1;
+    nd.cut = (di & (((inside >> 1) & 1) ^ in0)) | ((dj & (((inside >> 2) & 1) ^ in0)) << 1) | ((dk & (((inside >> 4) & 1) ^ in0)) << 2);
+    nd.ntri = (di & dj & dk) ? (int)kMcCount[inside] : 0;
+}
+
+// The node a lane holds while its workgroup walks a tile: (kk, j, i) of node l of the launch, found by division once and then advanced by kBlock nodes per
+// chunk with carries (a 64-bit division per node and pass would cost more than the loads).
+struct IsoWalk {
+    size_t l;
+    int kk, j, i;
+    __device__ __forceinline__ void start(size_t l0, int n, size_t plane) {
+        l = l0;
+        kk = (int)(l0 / plane);
+        const unsigned rem = (unsigned)(l0 - (size_t)kk * plane);
+        j = (int)(rem / (unsigned)n);
+        i = (int)(rem - (unsigned)j * (unsigned)n);
+    }
+    __device__ __forceinline__ void next(int n) {
+        l += kBlock;
+        i += kBlock;
+        while (i >= n) { i -= n; j++; }
+        while (j >= n) { j -= n; kk++; }
+    }
+};
+
+// Ballots of the three cut bits and of the three bits of the triangle count (0..5).  `below` masks the lanes under this one: wave64, so 64-bit masks.
+struct IsoBallots {
+    unsigned long long c0, c1, c2, t0, t1, t2;
+    __device__ __forceinline__ void take(int cut, int ntri) {
+        c0 = __ballot(cut & 1); c1 = __ballot(cut & 2); c2 = __ballot(cut & 4);
+        t0 = __ballot(ntri & 1); t1 = __ballot(ntri & 2); t2 = __ballot(ntri & 4);
+    }
+    __device__ __forceinline__ unsigned verts() const { return __popcll(c0) + __popcll(c1) + __popcll(c2); }
+    __device__ __forceinline__ unsigned tris() const { return __popcll(t0) + 2u * __popcll(t1) + 4u * __popcll(t2); }
+    __device__ __forceinline__ unsigned verts_below(unsigned long long below) const { return __popcll(c0 & below) + __popcll(c1 & below) + __popcll(c2 & below); }
+    __device__ __forceinline__ unsigned tris_below(unsigned long long below) const {
+        return __popcll(t0 & below) + 2u * __popcll(t1 & below) + 4u * __popcll(t2 & below);
+    }
+};
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void iso_idx_count_kernel(IsoIdxParams P, const T* __restrict__ phi /* ghost layout */, unsigned* __restrict__ tile_verts,
+                                                               unsigned* __restrict__ tile_tris) {
+    __shared__ unsigned wv[kBlock / kWave], wt[kBlock / kWave];
+    const size_t plane = (size_t)P.n * P.n;
+    const size_t nnodes = plane * (size_t)P.nplanes;
+    const size_t tile0 = (size_t)blockIdx.x * kIsoTile;
+    unsigned nv = 0, nt = 0;   // wave totals: the same in every lane of the wave
+    IsoWalk w0;
+    w0.start(tile0 + threadIdx.x, P.n, plane);
+    for (int c = 0; c < kIsoChunks; c++, w0.next(P.n)) {
+        int cut = 0, ntri = 0;
+        if (w0.l < nnodes) {
+            IsoNode nd;
+            iso_node_load(P, phi, w0.kk, w0.j, w0.i, plane, nd);
+            cut = nd.cut;
+            ntri = nd.ntri;
+        }
+        IsoBallots B;
+        B.take(cut, ntri);
+        nv += B.verts();
+        nt += B.tris();
+    }
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    if (lane == 0) { wv[w] = nv; wt[w] = nt; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned sv = 0, st = 0;
+        for (int a = 0; a < kBlock / kWave; a++) { sv += wv[a]; st += wt[a]; }
+        tile_verts[blockIdx.x] = sv;
+        tile_tris[blockIdx.x] = st;
+    }
+}
+
+// One workgroup: off[t] = sum of tot[0..t), off[ntiles] = the total, for both arrays.  Every thread owns a contiguous run of tiles.
+// (A template so that the two solver translation units may both hold it.)
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void iso_idx_scan_kernel(size_t ntiles, const unsigned* __restrict__ tile_verts, const unsigned* __restrict__ tile_tris,
+                                                                     unsigned long long* __restrict__ vert_off, unsigned long long* __restrict__ tri_off) {
+    __shared__ unsigned long long sv[BLOCK], st[BLOCK];
+    const size_t per = (ntiles + BLOCK - 1) / BLOCK;
+    const size_t a = per * threadIdx.x < ntiles ? per * threadIdx.x : ntiles, b = a + per < ntiles ? a + per : ntiles;
+    unsigned long long mv = 0, mt = 0;
+    for (size_t t = a; t < b; t++) { mv += tile_verts[t]; mt += tile_tris[t]; }
+    sv[threadIdx.x] = mv;
+    st[threadIdx.x] = mt;
+    __syncthreads();
+    for (int d = 1; d < BLOCK; d <<= 1) {   // inclusive scan of the run sums
+        unsigned long long xv = 0, xt = 0;
+        if ((int)threadIdx.x >= d) { xv = sv[threadIdx.x - d]; xt = st[threadIdx.x - d]; }
+        __syncthreads();
+        sv[threadIdx.x] += xv;
+        st[threadIdx.x] += xt;
+        __syncthreads();
+    }
+    unsigned long long ov = sv[threadIdx.x] - mv, ot = st[threadIdx.x] - mt;
+    for (size_t t = a; t < b; t++) {
+        vert_off[t] = ov; tri_off[t] = ot;
+        ov += tile_verts[t]; ot += tile_tris[t];
+    }
+    if (threadIdx.x == BLOCK - 1) {
+        vert_off[ntiles] = sv[threadIdx.x];
+        tri_off[ntiles] = st[threadIdx.x];
+    }
+}
+
+// Positions: tt from the edge's lower node, idx*cell + bbox_min per axis plus tt*cell on the edge's axis -- iso_mc_kernel's expressions in its order.
+template <typename T>
+__global__ __launch_bounds__(kBlock) void iso_idx_verts_kernel(IsoIdxParams P, const T* __restrict__ phi, const unsigned long long* __restrict__ vert_off /* this slab's tiles */,
+                                                               unsigned long long* __restrict__ record /* the process's nodes */, double* __restrict__ verts /* [nv][3] */) {
+    __shared__ unsigned wv[2][kBlock / kWave];
+    const unsigned long long first = vert_off[blockIdx.x];
+    if (vert_off[blockIdx.x + 1] == first) return;   // (uniform: the whole workgroup leaves)
+    const size_t plane = (size_t)P.n * P.n;
+    const size_t nnodes = plane * (size_t)P.nplanes;
+    const size_t rec0 = (size_t)(P.k0 - P.kb) * plane;
+    const size_t tile0 = (size_t)blockIdx.x * kIsoTile;
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+    unsigned long long run = first;
+    IsoWalk w0;
+    w0.start(tile0 + threadIdx.x, P.n, plane);
+    for (int c = 0; c < kIsoChunks; c++, w0.next(P.n)) {
+        const size_t l = w0.l;
+        IsoNode nd;
+        nd.cut = 0;
+        if (l < nnodes) iso_node_load(P, phi, w0.kk, w0.j, w0.i, plane, nd);
+        IsoBallots B;
+        B.take(nd.cut, 0);
+        if (lane == 0) wv[c & 1][w] = B.verts();
+        __syncthreads();   // (the other buffer is the previous chunk's: one barrier per chunk is enough)
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int a = 0; a < kBlock / kWave; a++) {
+            const unsigned x = wv[c & 1][a];
+            before += a < w ? x : 0u;
+            total += x;
+        }
+        if (nd.cut) {
+            unsigned long long id = run + before + B.verts_below(below);
+            record[rec0 + l] = id << 3 | (unsigned long long)nd.cut;
+            const double pa[3] = {nd.i * P.cell + P.bbox_min[0], nd.j * P.cell + P.bbox_min[1], nd.k * P.cell + P.bbox_min[2]};
+            const double va = nd.v[0];
+#pragma unroll
+            for (int ax = 0; ax < 3; ax++) {
+                if (!((nd.cut >> ax) & 1)) continue;
+                const double vb = nd.v[1 << ax];
+                const double tt = (P.iso - va) / (vb - va);
+                verts[id * 3 + 0] = pa[0] + (ax == 0 ? tt * P.cell : 0.);
+                verts[id * 3 + 1] = pa[1] + (ax == 1 ? tt * P.cell : 0.);
+                verts[id * 3 + 2] = pa[2] + (ax == 2 ? tt * P.cell : 0.);
+                id++;
+            }
+        }
+        run += total;
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void iso_idx_tris_kernel(IsoIdxParams P, const T* __restrict__ phi, const unsigned long long* __restrict__ tri_off /* this slab's tiles */,
+                                                              const unsigned long long* __restrict__ record, int64_t* __restrict__ tris /* [nt][3] */) {
+    __shared__ unsigned wt[2][kBlock / kWave];
+    const unsigned long long first = tri_off[blockIdx.x];
+    if (tri_off[blockIdx.x + 1] == first) return;
+    const size_t plane = (size_t)P.n * P.n;
+    const size_t nnodes = plane * (size_t)P.nplanes;
+    const size_t rec0 = (size_t)(P.k0 - P.kb) * plane;
+    const size_t tile0 = (size_t)blockIdx.x * kIsoTile;
+    const int lane = threadIdx.x & (kWave - 1), w = threadIdx.x / kWave;
+    const unsigned long long below = (1ULL << lane) - 1ULL;
+    unsigned long long run = first;
+    IsoWalk w0;
+    w0.start(tile0 + threadIdx.x, P.n, plane);
+    for (int c = 0; c < kIsoChunks; c++, w0.next(P.n)) {
+        const size_t l = w0.l;
+        IsoNode nd;
+        nd.ntri = 0;
+        nd.inside = 0;
+        if (l < nnodes) iso_node_load(P, phi, w0.kk, w0.j, w0.i, plane, nd);
+        IsoBallots B;
+        B.take(0, nd.ntri);
+        if (lane == 0) wt[c & 1][w] = B.tris();
+        __syncthreads();
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int a = 0; a < kBlock / kWave; a++) {
+            const unsigned x = wt[c & 1][a];
+            before += a < w ? x : 0u;
+            total += x;
+        }
+        unsigned long long slot = run + before + B.tris_below(below);
+        for (int tr = 0; tr < nd.ntri; tr++, slot++) {
+#pragma unroll
+            for (int a = 0; a < 3; a++) {
+                const int e = kMcTris[nd.inside][3 * tr + a];
+                const int qa = kMcEdge[e][0], qb = kMcEdge[e][1];   // qa < qb: the edge's lower node
+                const int ax = qa ^ qb;                              // 1, 2 or 4
+                const size_t ln = rec0 + l + (size_t)(qa & 1) + (size_t)((qa >> 1) & 1) * (size_t)P.n + (size_t)((qa >> 2) & 1) * plane;
+                const unsigned long long rec = record[ln];
+                tris[slot * 3 + a] = (int64_t)((rec >> 3) + (unsigned long long)__popc((unsigned)rec & 7u & (unsigned)(ax - 1)));
+            }
+        }
+        run += total;
+    }
+}
+
+// device fp64 positions -> the handle's precision, rounded once on the store
+template <typename T>
+__global__ __launch_bounds__(kBlock) void iso_idx_store_kernel(size_t count, const double* __restrict__ src, T* __restrict__ dst) {
+    for (size_t a = (size_t)blockIdx.x * kBlock + threadIdx.x; a < count; a += (size_t)gridDim.x * kBlock) dst[a] = (T)src[a];
+}
+
+}  // namespace shm

@@ -21,6 +21,7 @@
 #include "shm_green_fft.hip.h"
 #include "shm_sample.hip.h"
 #include "shm_audit.hip.h"
+#include "shm_iso_indexed.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -536,6 +537,7 @@ struct Solver final : SolverBase {
         precond_ready = false;
         have_problem = true;
         have_conv = have_div = have_phi = have_constraints = false;
+        iso_idx_valid = false;
         audit_src_ready = false;
         // (round 6: the whole-grid solver of the gathered multi-rank solve is created when a solve first takes that path -- ensure_full() -- so that a run whose solves
         // all take the slab-distributed forms never allocates whole-grid arrays on every rank)
@@ -3132,6 +3134,7 @@ struct Solver final : SolverBase {
         PlanIn in = plan_inputs(&o);   // (the options are checked here, before anything is launched)
         const Plan p = plan_solve(in);
         if (p.status != SHM_OK) throw Error(p.status, p.error);
+        iso_idx_valid = false;   // q is about to be overwritten: the indexed mesh no longer belongs to the resident phi
         const bool pre = p.precond;
         if (!(o.tol > 0.)) o.tol = sizeof(T) == 8 ? 1e-8 : 1e-5;
         if (o.max_iters <= 0) o.max_iters = 20 * n;
@@ -3289,6 +3292,7 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_phi = false;  // q now holds L u, not phi
+        iso_idx_valid = false;
     }
 
     void get_constraints(int64_t* nodes, double* coeffs, int32_t* m_out) override {
@@ -3481,20 +3485,20 @@ struct Solver final : SolverBase {
     }
 
     // device buffers of type T, checked to lie in device memory of this handle's device and to hold Q points before anything is launched
-    void check_device_buffer(const void* p, size_t bytes, const char* what) {
+    void check_device_buffer(const void* p, size_t bytes, const char* what, const char* who = "sample_device", const char* short_of = "the Q points asked for") {
         hipPointerAttribute_t at;
         memset(&at, 0, sizeof at);
         const hipError_t e = hipPointerGetAttributes(&at, p);
         if (e != hipSuccess) (void)hipGetLastError();
         if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != cfg.device)
-            throw Error(SHM_ERR_INVALID, fmt("sample_device: %s is not device memory of device %d", what, cfg.device));
+            throw Error(SHM_ERR_INVALID, fmt("%s: %s is not device memory of device %d", who, what, cfg.device));
         hipDeviceptr_t base = nullptr;
         size_t size = 0;
         if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
             (void)hipGetLastError();
-            throw Error(SHM_ERR_INVALID, fmt("sample_device: %s is not a device allocation", what));
+            throw Error(SHM_ERR_INVALID, fmt("%s: %s is not a device allocation", who, what));
         }
-        if ((const char*)p + bytes > (const char*)base + size) throw Error(SHM_ERR_INVALID, fmt("sample_device: %s holds fewer than the Q points asked for", what));
+        if ((const char*)p + bytes > (const char*)base + size) throw Error(SHM_ERR_INVALID, fmt("%s: %s holds fewer than %s", who, what, short_of));
     }
     void sample_device(int64_t Q, const void* pts, void* out, void* grad, int64_t* n_answered) override {
         if (Q < 0) throw Error(SHM_ERR_INVALID, "sample_device: Q < 0");
@@ -3511,6 +3515,108 @@ struct Solver final : SolverBase {
         launch_sample<T>(Q, (const T*)pts, (T*)out, (T*)grad);
         const int64_t a = sample_end();
         if (n_answered) *n_answered = a;
+    }
+
+    // ---- indexed isosurface built on the device (shm_iso_indexed.hip.h) ---------------------------------------------------------------------------------
+    // Working memory: one 8-byte record per node of the process's vertex planes, and the tile totals / offsets.  Allocated on first use, kept while n is
+    // unchanged, freed with the handle.  No solver array is borrowed: the audit reads Y, sampling and the host-welded isosurface read q.
+    DevArray<unsigned long long> d_iso_rec;
+    DevArray<unsigned> d_iso_tot;              // [2][ntiles]: vertices, triangles per tile
+    DevArray<unsigned long long> d_iso_off;    // [2][ntiles + 1]: their exclusive prefix sums
+    DevArray<double> d_iso_V;                  // the resident mesh: [nv][3] fp64 positions, [nt][3] indices local to this process
+    DevArray<int64_t> d_iso_F;
+    int64_t iso_idx_nv = 0, iso_idx_nt = 0;
+    int iso_idx_n = -1;
+    bool iso_idx_valid = false;
+
+    void isosurface_indexed(double iso, int64_t* nv_out, int64_t* nt_out) override {
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        HIPCHK(hipSetDevice(cfg.device));
+        halo_exchange(ARR_Q);  // phi lives in q; cells of the top owned plane need the plane above (collective with world > 1)
+        iso_idx_valid = false;
+        iso_idx_nv = iso_idx_nt = 0;
+        const int kb = slabs.front().k0, ke = slabs.back().k1;
+        const int ktop = std::min(ke, n - 1);   // last plane that carries vertices; cells are k in [kb, ktop)
+        if (ktop > kb) {
+            if (iso_idx_n != n) {
+                d_iso_rec.release();
+                d_iso_tot.release();
+                d_iso_off.release();
+                iso_idx_n = n;
+            }
+            const size_t plane = (size_t)n * n;
+            std::vector<IsoIdxParams> P(slabs.size());
+            std::vector<size_t> tile_base(slabs.size() + 1, 0);
+            for (size_t s = 0; s < slabs.size(); s++) {
+                IsoIdxParams& p = P[s];
+                p.n = n; p.k0 = slabs[s].k0; p.kb = kb; p.ktop = ktop;
+                p.nplanes = s + 1 < slabs.size() ? slabs[s].nzl : ktop - slabs[s].k0 + 1;
+                for (int a = 0; a < 3; a++) p.bbox_min[a] = bbox_min[a];
+                p.cell = cell; p.iso = iso;
+                tile_base[s + 1] = tile_base[s] + (plane * (size_t)p.nplanes + kIsoTile - 1) / kIsoTile;
+            }
+            const size_t ntiles = tile_base.back();
+            d_iso_rec.alloc(plane * (size_t)(ktop - kb + 1));
+            d_iso_tot.alloc(2 * ntiles);
+            d_iso_off.alloc(2 * (ntiles + 1));
+            unsigned* tot_v = d_iso_tot.p;
+            unsigned* tot_t = d_iso_tot.p + ntiles;
+            unsigned long long* off_v = d_iso_off.p;
+            unsigned long long* off_t = d_iso_off.p + ntiles + 1;
+            auto tiles = [&](size_t s) { return dim3((unsigned)(tile_base[s + 1] - tile_base[s])); };
+            for (size_t s = 0; s < slabs.size(); s++)
+                hipLaunchKernelGGL((iso_idx_count_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, tot_v + tile_base[s], tot_t + tile_base[s]);
+            hipLaunchKernelGGL((iso_idx_scan_kernel<kIsoScanBlock>), dim3(1), dim3(kIsoScanBlock), 0, stream, ntiles, tot_v, tot_t, off_v, off_t);
+            HIPCHK(hipGetLastError());
+            unsigned long long total[2] = {0, 0};
+            HIPCHK(hipMemcpyAsync(&total[0], off_v + ntiles, sizeof total[0], hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipMemcpyAsync(&total[1], off_t + ntiles, sizeof total[1], hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (total[0] > 0) {
+                d_iso_V.alloc((size_t)total[0] * 3);
+                d_iso_F.alloc(std::max<size_t>(1, (size_t)total[1] * 3));
+                for (size_t s = 0; s < slabs.size(); s++)
+                    hipLaunchKernelGGL((iso_idx_verts_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, off_v + tile_base[s], d_iso_rec.p, d_iso_V.p);
+                for (size_t s = 0; s < slabs.size(); s++)   // after every slab's records: a slab's top layer reads the next slab's
+                    hipLaunchKernelGGL((iso_idx_tris_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, off_t + tile_base[s], d_iso_rec.p, d_iso_F.p);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipStreamSynchronize(stream));
+            }
+            iso_idx_nv = (int64_t)total[0];
+            iso_idx_nt = (int64_t)total[1];
+        }
+        iso_idx_valid = true;
+        if (nv_out) *nv_out = iso_idx_nv;
+        if (nt_out) *nt_out = iso_idx_nt;
+    }
+    void need_iso_indexed(const char* who) const {
+        if (!iso_idx_valid || !have_phi)
+            throw Error(SHM_ERR_STATE, fmt("%s: no indexed isosurface of the resident phi (shm_grid_isosurface_indexed has not run since phi was last replaced)", who));
+    }
+    void get_isosurface_indexed(double* vertices, int64_t* triangles) override {
+        need_iso_indexed("get_isosurface_indexed");
+        if ((iso_idx_nv > 0 && !vertices) || (iso_idx_nt > 0 && !triangles)) throw Error(SHM_ERR_INVALID, "get_isosurface_indexed: null buffer for a non-empty mesh");
+        HIPCHK(hipSetDevice(cfg.device));
+        if (iso_idx_nv > 0) HIPCHK(hipMemcpyAsync(vertices, d_iso_V.p, (size_t)iso_idx_nv * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        if (iso_idx_nt > 0) HIPCHK(hipMemcpyAsync(triangles, d_iso_F.p, (size_t)iso_idx_nt * 3 * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    void get_isosurface_indexed_device(void* d_vertices, void* d_triangles) override {
+        const char* who = "get_isosurface_indexed_device";
+        need_iso_indexed(who);
+        if ((iso_idx_nv > 0 && !d_vertices) || (iso_idx_nt > 0 && !d_triangles)) throw Error(SHM_ERR_INVALID, fmt("%s: null buffer for a non-empty mesh", who));
+        HIPCHK(hipSetDevice(cfg.device));
+        const size_t cv = (size_t)iso_idx_nv * 3, ct = (size_t)iso_idx_nt * 3;
+        if (cv > 0) check_device_buffer(d_vertices, cv * sizeof(T), "the vertex buffer", who, "the 3 nv positions of the mesh");
+        if (ct > 0) check_device_buffer(d_triangles, ct * sizeof(int64_t), "the triangle buffer", who, "the 3 nt indices of the mesh");
+        if (cv > 0) {
+            if (sizeof(T) == 8) HIPCHK(hipMemcpyAsync(d_vertices, d_iso_V.p, cv * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            else hipLaunchKernelGGL((iso_idx_store_kernel<T>), dim3(grid_for(cv, 4096)), dim3(kBlock), 0, stream, cv, d_iso_V.p, (T*)d_vertices);
+        }
+        if (ct > 0) HIPCHK(hipMemcpyAsync(d_triangles, d_iso_F.p, ct * sizeof(int64_t), hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
     }
 
     // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------
@@ -3625,6 +3731,7 @@ struct Solver final : SolverBase {
         for (Slab<T>& sl : slabs) HIPCHK(hipMemcpyAsync(sl.q.p, sl.z.p, sl.ntot * sizeof(T), hipMemcpyDeviceToDevice, stream));
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_conv = have_div = have_phi = false;
+        iso_idx_valid = false;
     }
 };
 

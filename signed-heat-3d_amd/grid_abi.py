@@ -20,6 +20,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
+               "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
@@ -112,6 +113,10 @@ def load_library():
     lib.shm_grid_get_isosurface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shm_grid_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shm_grid_sample_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "shm_grid_isosurface_indexed"):   # added within ABI 5: found by symbol
+        lib.shm_grid_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        lib.shm_grid_get_isosurface_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.shm_grid_get_isosurface_indexed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(lib, "shm_grid_audit_step1"):   # added within ABI 5: found by symbol (another build named by SHM_GRID_LIB may predate it)
         lib.shm_grid_audit_step1.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmStep1Audit)]
         lib.shm_audit_sample_nodes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p]
@@ -320,6 +325,28 @@ class GridSolver:
         V = np.empty((nv.value, 3), dtype=np.float64)
         F = np.empty((nt.value, 3), dtype=np.int64)
         self._chk(self._lib.shm_grid_get_isosurface(self._h, V.ctypes.data, F.ctypes.data))
+        return V, F
+
+    def isosurface_indexed(self, isovalue=0.0, device=False):
+        """The marching-cubes surface of isosurface(), welded and numbered on the device in a canonical order (shm_grid_isosurface_indexed): vertices
+        ascend in 3 * (i + j n + k n^2) + axis of their grid edge, triangles in (cell, position in the case's table entry) -- isosurface()'s triangle
+        order, so the two differ by a renumbering of the vertices.  Returns (V [nv, 3] float64, F [nt, 3] int64) as numpy arrays; with device=True,
+        torch tensors on this handle's device, V float64 for SHM_F64 and float32 for SHM_F32 (the fp64 position rounded once), F int64, copied
+        device to device from the resident mesh.  As for sample_device, import torch before this library is loaded."""
+        nv, nt = C.c_int64(), C.c_int64()
+        self._chk(self._lib.shm_grid_isosurface_indexed(self._h, float(isovalue), C.byref(nv), C.byref(nt)))
+        if not device:
+            V = np.empty((nv.value, 3), dtype=np.float64)
+            F = np.empty((nt.value, 3), dtype=np.int64)
+            self._chk(self._lib.shm_grid_get_isosurface_indexed(self._h, V.ctypes.data if nv.value else None, F.ctypes.data if nt.value else None))
+            return V, F
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("isosurface_indexed: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dev = torch.device("cuda", self.device)
+        V = torch.empty((nv.value, 3), dtype=torch.float64 if self.precision == SHM_F64 else torch.float32, device=dev)
+        F = torch.empty((nt.value, 3), dtype=torch.int64, device=dev)
+        self._chk(self._lib.shm_grid_get_isosurface_indexed_device(self._h, V.data_ptr() if nv.value else None, F.data_ptr() if nt.value else None))
         return V, F
 
     def sample(self, points, grad=False):

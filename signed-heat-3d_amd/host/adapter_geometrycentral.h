@@ -13,6 +13,7 @@
 #include "shm_grid.h"        // this repository's include/shm_grid.h
 #include "signed_heat_3d.h"  // the reference's own header: SignedHeat3DOptions, centroid, radius, meanEdgeLength, setFaceVectorAreas
 
+#include <array>
 #include <cmath>
 #include <iostream>
 #include <stdexcept>
@@ -95,6 +96,21 @@ class SignedHeatGridSolver {
         shm_step1_audit a{};
         if (shm_grid_audit_step1(handle, got, nodes.data(), nullptr, nullptr, &a) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
         return a;
+    }
+
+    // Marching-cubes isosurface of the phi of the last computeDistance(), welded and numbered on the device in a canonical order
+    // (shm_grid_isosurface_indexed): vertices ascend in 3*(i + j n + k n^2) + axis of their grid edge, faces in (cell, position in the case's table entry).
+    void isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces) {
+        if (!handle) throw std::runtime_error("isosurfaceIndexed: computeDistance has not been called");
+        int64_t nv = 0, nt = 0;
+        if (shm_grid_isosurface_indexed(handle, isoval, &nv, &nt) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        std::vector<double> v((size_t)3 * nv);
+        std::vector<int64_t> f((size_t)3 * nt);
+        if (shm_grid_get_isosurface_indexed(handle, nv ? v.data() : nullptr, nt ? f.data() : nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        vertices.resize((size_t)nv);
+        faces.resize((size_t)nt);
+        for (int64_t a = 0; a < nv; a++) vertices[(size_t)a] = Vector3{v[3 * a], v[3 * a + 1], v[3 * a + 2]};
+        for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
     }
 
   private:

@@ -190,6 +190,25 @@ int shmh_sample(void* hv, int64_t Q, const double* pts, double* phi_out, double*
     });
 }
 
+// isosurfaceIndexed through the C++ class, in two calls: vertices == NULL builds the mesh of the last compute_distance and returns the counts; with
+// buffers ([3 nv] doubles, [3 nt] int64) it builds again -- the canonical order makes the second mesh the first -- and copies it out.
+int shmh_isosurface_indexed(void* hv, double isoval, int64_t* nv, int64_t* nt, double* vertices, int64_t* triangles) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> v;
+        std::vector<std::array<size_t, 3>> f;
+        h->solver.isosurfaceIndexed(isoval, v, f);
+        if (nv) *nv = (int64_t)v.size();
+        if (nt) *nt = (int64_t)f.size();
+        if (vertices)
+            for (size_t a = 0; a < v.size(); a++)
+                for (int b = 0; b < 3; b++) vertices[3 * a + b] = v[a][b];
+        if (triangles)
+            for (size_t a = 0; a < f.size(); a++)
+                for (int b = 0; b < 3; b++) triangles[3 * a + b] = (int64_t)f[a][(size_t)b];
+    });
+}
+
 // auditStep1 through the C++ class: the Step 1 of the last compute_distance at a stratified sample of `count` nodes.
 int shmh_audit_step1(void* hv, int64_t count, uint64_t seed, shm_step1_audit* out) {
     Host* h = (Host*)hv;

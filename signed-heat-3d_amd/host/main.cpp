@@ -28,6 +28,7 @@ static void usage() {
                  "      --out <file>      Write phi as raw little-endian float64 (n^3 values, x fastest)\n"
                  "      --iso <value>     Contour phi at this value (default 0) and export the isosurface\n"
                  "      --export <file>   OBJ file of the isosurface (the demo writes ../export/isosurface.obj)\n"
+                 "      --iso-indexed     Build the exported isosurface on the device in the canonical order (vertices by grid edge, triangles by cell)\n"
                  "      --query <file>    Points to evaluate phi at: raw little-endian float64 xyz triples\n"
                  "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n";
 }
@@ -38,7 +39,7 @@ int main(int argc, char** argv) {
     long long auditCount = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
-    bool verbose = false;
+    bool verbose = false, isoIndexed = false;
     for (int a = 1; a < argc; a++) {
         const std::string s = argv[a];
         auto need = [&](const char* what) -> const char* {
@@ -63,6 +64,7 @@ int main(int argc, char** argv) {
         else if (s == "--out") out = need("--out");
         else if (s == "--iso") isoval = atof(need("--iso"));
         else if (s == "--export") exportPath = need("--export");
+        else if (s == "--iso-indexed") isoIndexed = true;
         else if (s == "--query") queryPath = need("--query");
         else if (s == "--query-out") queryOut = need("--query-out");
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
@@ -118,7 +120,8 @@ int main(int argc, char** argv) {
         if (!exportPath.empty()) {
             std::vector<Vector3> iv;
             std::vector<std::array<size_t, 3>> jf;
-            solver.isosurface(isoval, iv, jf);
+            if (isoIndexed) solver.isosurfaceIndexed(isoval, iv, jf);
+            else solver.isosurface(isoval, iv, jf);
             writeSurfaceMesh(iv, jf, exportPath);
             std::cerr << "Isosurface written to " << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
         }

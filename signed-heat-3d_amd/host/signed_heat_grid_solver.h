@@ -39,6 +39,9 @@ class SignedHeatGridSolver {
     // Headless stand-in for the demo's contour()/export path (src/main.cpp:116-128,167-191, done there by Polyscope's marching
     // cubes): isosurface of the phi of the LAST computeDistance() call, extracted on the device (marching cubes: shm_grid_isosurface).
     void isosurface(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces);
+    // The same surface welded and numbered on the device in a canonical order (shm_grid_isosurface_indexed): vertices ascend in 3*(i + j n + k n^2) + axis
+    // of their grid edge, faces keep isosurface()'s order, so the two differ by a renumbering of the vertices.  No host sort, no host weld.
+    void isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces);
 
     // Stands for the reference's private evaluateFunction(u, q) (signed_heat_grid_solver.cpp:405-431), here public and batched: the trilinear value of the phi of
     // the LAST computeDistance() call at every point of q, evaluated on the device (shm_grid_sample; box, NaN and gradient rules in include/shm_grid.h).

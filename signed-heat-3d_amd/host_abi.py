@@ -41,6 +41,7 @@ def load_host_library():
                                     C.POINTER(C.c_int64)]
     lib.shmh_compute_distance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(ShmStats)]
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.shmh_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.argtypes = [C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.restype = None
     _LIB = lib
@@ -124,6 +125,16 @@ class HostSolver:
         g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
         self._chk(self._lib.shmh_sample(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None))
         return (phi, g) if grad else phi
+
+    def isosurface_indexed(self, isovalue=0.0):
+        """isosurfaceIndexed of the C++ mirror: the marching-cubes surface of the last compute_distance, welded and numbered on the device in the
+        canonical order (shm_grid_isosurface_indexed).  Returns (V [nv, 3] float64, F [nt, 3] int64)."""
+        nv, nt = C.c_int64(), C.c_int64()
+        self._chk(self._lib.shmh_isosurface_indexed(self._h, float(isovalue), C.byref(nv), C.byref(nt), None, None))
+        V = np.empty((nv.value, 3), dtype=np.float64)
+        F = np.empty((nt.value, 3), dtype=np.int64)
+        self._chk(self._lib.shmh_isosurface_indexed(self._h, float(isovalue), None, None, V.ctypes.data, F.ctypes.data))
+        return V, F
 
     def audit_step1(self, count=4096, seed=0):
         """auditStep1 of the C++ mirror: the Step 1 of the last compute_distance audited on the device at a stratified sample of `count` nodes
