@@ -44,13 +44,15 @@
 // weights broadcast by op_sel, and a register diet (181 -> 171 with four pairs of a near source in flight) -- 16.4 -> 15.4 VALU instructions per nominal pair.
 // Round 6 (profiles/NOTES_r06.md): the accumulated drop rule, the cluster scan as a lane-parallel batch test, the far loop written stage by stage
 // (the scheduler's 24 s_nop are gone), the in-launch verdict of the far-rule sample as one word written by compare-and-swap.  176 registers.
+// Round 7 (profiles/NOTES_r07.md): the near body's Newton step folded into the exponent scale -- 11 fp64 instructions per pair behind v_rsq_f64 instead of 12, the near loop 100
+// instructions per source instead of 104 (see yukawa_near); the near list's weights are staged times 1 / |c|.  13.81 VALU instructions per nominal pair (14.20), 176 registers.
 #pragma once
 #include "shm_kernels.hip.h"
 
 namespace shm {
 
 // e^{-lambda r}/r from x = r^2 for the near tier: hardware v_rsq_f64 seed (2^-24) + one second-order step (relative error 3/8 e^2 ~ 1e-15 in r
-// and 1/r), exponent remainder with a single rounding against the 2048-entry table of 2^(j/2048), degree-2 polynomial of 2^(f/2048)
+// and 1/r; since round 7 folded into the exponent scale, see below), exponent remainder with a single rounding against the 2048-entry table of 2^(j/2048), degree-2 polynomial of 2^(f/2048)
 // (truncation (ln2/4096)^3/6 = 8e-13).
 // Round 5: the power of two is no longer applied by v_ashrrev + v_ldexp_f64 but ADDED INTO THE EXPONENT FIELD of the table entry by one v_lshl_add_u32:
 // with ki = 2048 k + j the low word of the rounding trick holds ki, and (ki << 9) = (k << 20) + (j << 9) -- the table is stored with (j << 9) subtracted
@@ -65,29 +67,42 @@ typedef unsigned uint2v __attribute__((ext_vector_type(2)));
 // (round 6, late: at nodes where the sources' terms cancel to 1e-4 of their sum -- inside SprayBottle.pc at 1024^3 -- the 8e-13 was the whole 8.1e-9 of the measured
 // error of Y: tools/r06_worst_node_diag.py, NOTES_r06.md section 7)
 constexpr double kNearA1 = 3.384507729693224e-04;
-__device__ __forceinline__ double yukawa_near(double x, double c, double m1, const uint2v* __restrict__ tab) {
+// Round 7: the Newton step is FOLDED INTO THE EXPONENT SCALE.  Neither r nor 1/r is needed on its own: r is only ever multiplied by the constant c = -lambda 2048 / ln 2
+// (< 0) and 1/r is only a factor of the result, and both carry the same Newton factor (1 + e), e = (1 - x y0^2) / 2.  With e2 = 2 e and the two wave-uniform constants
+// c1 = |c|, c2 = |c| / 2:
+//     t = x y0;  e2 = fma(-t, y0, 1);  cc = fma(e2, c2, c1);                       cc = |c| (1 + e)
+//     tm = fma(-t, cc, m1);  kf = tm - m1;  f = fma(-t, cc, -kf);                    r c = -t cc
+//     p = 1 + A1 f + A2 f^2 (two fma);  q = y0 cc;  g' = tab (p q)                  q = |c| / r,  g' = |c| g
+// -- 11 fp64 instructions behind v_rsq_f64 where rounds 5-6 spent 12 (t, 0.5 y0, e, r, 1/r, tm, kf, f, two fma, p / r, tab (...)).  The common factor |c| is taken out once
+// per staged near source: the classifying lane writes its weights times 1 / |c| (ConvParams::cexp_inv, formed on the host) into the fp64 list, so acc += w' g' is the
+// sum it was and nothing else in the kernel learns of the scale.  The same Newton step and the same remainder f (still the rounding error of one fma); what is new is one
+// more rounding, of cc, inside the exponent: at most 2^-53 |r c| ln 2 / 2048 relative in the term -- 7.7e-14 at the edge of the 2^-990 span the host allows
+// (Solver::tier_exponent_span_ok), <= 1e-14 at exponents of 30 ... 70 octaves; the polynomial's 2.0e-13 stays the dominant term (tests/test_near_body_model.py
+// models both chains in exact arithmetic).  x = 0: y0 = inf, t = NaN -- the NaN under a source on a node is the reference's, as before.
+// Returns |c| e^{-lambda r} / r.
+__device__ __forceinline__ double yukawa_near(double x, double c1, double c2, double m1, const uint2v* __restrict__ tab) {
     const double y0 = __builtin_amdgcn_rsq(x);
     const double t = x * y0;
-    const double h = 0.5 * y0;
-    const double e = fma(-t, h, 0.5);            // (1 - x y0^2) / 2
-    const double r = fma(t, e, t);
-    const double rinv = fma(y0, e, y0);
-    const double tm = fma(r, c, m1);             // round(r c) - 2048 k0 lands in the low mantissa bits
+    const double e2 = fma(-t, y0, 1.0);          // 1 - x y0^2
+    const double cc = fma(e2, c2, c1);           // |c| (1 + e)
+    const double tm = fma(-t, cc, m1);           // round(r c) - 2048 k0 lands in the low mantissa bits
     const double kf = tm - m1;
     const unsigned ki = (unsigned)__double_as_longlong(tm);
-    const double f = fma(r, c, -kf);
+    const double f = fma(-t, cc, -kf);
+    const double q = y0 * cc;                    // |c| / r
     double p = 5.727446245172041e-08;                   // (ln2/2048)^2 / 2
     p = fma(p, f, kNearA1);
     p = fma(p, f, 1.0);
     uint2v tv = tab[ki & 2047u];
     tv.y += ki << 9;
-    return __builtin_bit_cast(double, tv) * (p * rinv);   // r = 0 -> NaN (0 * inf), like exp(0)/0 -> inf -> NaN after normalise
+    return __builtin_bit_cast(double, tv) * (p * q);   // r = 0 -> NaN, like exp(0)/0 -> inf -> NaN after normalise
 }
 
-// the same for B values at once, stage by stage (breadth-first): the source order the scheduler starts from interleaves the B dependent chains
+// the same for B values at once, stage by stage (breadth-first): the source order the scheduler starts from interleaves the B dependent chains.  q = y0 cc does not
+// depend on the exponent chain: it stands behind the table loads, where it covers their latency
 template <int B>
-__device__ __forceinline__ void yukawa_near_batch(const double* __restrict__ x, double c, double m1, const uint2v* __restrict__ tab, double* __restrict__ g) {
-    double y0[B], t[B], e[B], r[B], rinv[B], tm[B], f[B], p[B];
+__device__ __forceinline__ void yukawa_near_batch(const double* __restrict__ x, double c1, double c2, double m1, const uint2v* __restrict__ tab, double* __restrict__ g) {
+    double y0[B], t[B], cc[B], q[B], tm[B], f[B], p[B];
     unsigned ki[B];
     uint2v tv[B];
 #pragma unroll
@@ -95,26 +110,26 @@ __device__ __forceinline__ void yukawa_near_batch(const double* __restrict__ x, 
 #pragma unroll
     for (int b = 0; b < B; b++) t[b] = x[b] * y0[b];
 #pragma unroll
-    for (int b = 0; b < B; b++) e[b] = fma(-t[b], 0.5 * y0[b], 0.5);
+    for (int b = 0; b < B; b++) cc[b] = fma(fma(-t[b], y0[b], 1.0), c2, c1);
 #pragma unroll
-    for (int b = 0; b < B; b++) r[b] = fma(t[b], e[b], t[b]);
-#pragma unroll
-    for (int b = 0; b < B; b++) tm[b] = fma(r[b], c, m1);
+    for (int b = 0; b < B; b++) tm[b] = fma(-t[b], cc[b], m1);
 #pragma unroll
     for (int b = 0; b < B; b++) {
         ki[b] = (unsigned)__double_as_longlong(tm[b]);
         tv[b] = tab[ki[b] & 2047u];
-        tv[b].y += ki[b] << 9;
     }
 #pragma unroll
-    for (int b = 0; b < B; b++) f[b] = fma(r[b], c, -(tm[b] - m1));
+    for (int b = 0; b < B; b++) q[b] = y0[b] * cc[b];
 #pragma unroll
-    for (int b = 0; b < B; b++) rinv[b] = fma(y0[b], e[b], y0[b]);
+    for (int b = 0; b < B; b++) f[b] = fma(-t[b], cc[b], -(tm[b] - m1));
 #pragma unroll
     for (int b = 0; b < B; b++) p[b] = fma(fma(5.727446245172041e-08, f[b], kNearA1), f[b], 1.0);
 #pragma unroll
+    for (int b = 0; b < B; b++) p[b] *= q[b];
+#pragma unroll
     for (int b = 0; b < B; b++) {
-        g[b] = __builtin_bit_cast(double, tv[b]) * (p[b] * rinv[b]);
+        tv[b].y += ki[b] << 9;   // (the first use of the table entries: behind everything that does not need them)
+        g[b] = __builtin_bit_cast(double, tv[b]) * p[b];
     }
 }
 
@@ -290,6 +305,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
     const float rt_w = (float)(sqrt(kHalfX * kHalfX + kHalfY * kHalfY + kHalfZ * kHalfZ) * P.cell) * 1.000001f;
     const float hx = uniform_f32((float)(kHalfX * P.cell) * 1.000001f), hy = uniform_f32((float)(kHalfY * P.cell) * 1.000001f),
                 hz = uniform_f32((float)(kHalfZ * P.cell) * 1.000001f);   // half extents of a block
+    const double c1 = -P.cexp, c2 = -0.5 * P.cexp;   // |c|, |c| / 2: the near body's two constants (yukawa_near)
     unsigned long long cnt_near = 0, cnt_far = 0, cnt_redo = 0;
     int decided = -1;   // the sample's verdict, once this wave has needed it
     // Eight queue heads, one per XCD (workgroup b runs on XCD b % 8): the units -- x fastest, then y, then z -- are cut into eight contiguous ranges, so
@@ -664,7 +680,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                 if (to64) {
                     const int rnk = mask_rank(nearmask);
 #pragma unroll
-                    for (int a = 0; a < 6; a++) tile[rnk * 6 + a] = q[a];
+                    for (int a = 0; a < 6; a++) tile[rnk * 6 + a] = a < 3 ? q[a] : q[a] * P.cexp_inv;   // (the near body returns |c| e^{-lambda r} / r: see yukawa_near)
                 } else if (to32) {
                     const int rnk = mask_rank(farmask);
                     // positions in units of 1 / (lambda log2 e): the far loop then gets lambda r log2 e = d2' rsq(d2') without a multiplication of its own
@@ -704,12 +720,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                 double x[NPT], g[NPT];
 #pragma unroll
                 for (int e = 0; e < NPT; e++) {
-                    const double dz = e ? dz0 + e * P.cell : dz0;   // (the block's nodes are consecutive planes: one z per lane, the others by the cell size)
+                    // (the block's nodes are consecutive planes: one z per lane, the others by the cell size; 2 cell is exact, so the fma is the same sum -- and takes the
+                    // cell size from its scalar pair where the sum held 2 cell in two registers through the loop)
+                    const double dz = e == 2 ? fma(2.0, P.cell, dz0) : e ? dz0 + e * P.cell : dz0;
                     x[e] = fma(dz, dz, dxy2);
                 }
                 constexpr int kB = SHM_TIER_NEAR_BATCH < NPT ? SHM_TIER_NEAR_BATCH : NPT;
 #pragma unroll
-                for (int b0 = 0; b0 < NPT; b0 += kB) yukawa_near_batch<kB>(x + b0, P.cexp, m1, exp_tab, g + b0);
+                for (int b0 = 0; b0 < NPT; b0 += kB) yukawa_near_batch<kB>(x + b0, c1, c2, m1, exp_tab, g + b0);
 #pragma unroll
                 for (int e = 0; e < NPT; e++) {
                     ax[e] = fma(rec[3], g[e], ax[e]);

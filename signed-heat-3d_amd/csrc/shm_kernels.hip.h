@@ -140,6 +140,7 @@ struct ConvParams {
     double cell;
     double lambda;
     double cexp;        // -lambda * 2048 / ln 2 (fp64 path: exponent in table units)
+    double cexp_inv;    // 1 / |cexp|: the tiered kernels stage the near list's weights times this (their near body returns |cexp| e^{-lambda r} / r)
     int S;              // padded to whole clusters
     int n_clusters;
     float far_gap;      // fp64 path: a cluster is "far" when d_lo(tile, cluster) - r_hi(tile) > far_gap
@@ -639,6 +640,33 @@ __global__ __launch_bounds__(kBlock) void divergence_march_kernel(GridParams G, 
         mysum = block_sum(mysum, red);
         if (threadIdx.x == 0) sum_partials[blockIdx.x] = mysum;
     }
+}
+
+// The sum of b alone, in the ORDER divergence_march_kernel forms it: the same logical blocks, the same nodes per lane in the same sequence, the same block_sum, the
+// partial at the same index -- so that finalize_sum_kernel returns, for a b that came from elsewhere (the gathered solve: every rank's slabs), bit for bit the 1^T b that
+// the one-process solve gets from its divergence kernel.  Launched with that kernel's geometry for the slab.
+template <typename T, int VEC>
+__global__ __launch_bounds__(kBlock) void sum_march_kernel(GridParams G, int LX, int xchunks, int rowgroups, int ZC, const T* __restrict__ b, double* __restrict__ sum_partials) {
+    __shared__ double red[8];
+    double mysum = 0.;
+    const int n = G.n;
+    const size_t plane = (size_t)n * n;
+    const unsigned lb = xcd_remap(blockIdx.x, gridDim.x);
+    const int xc = (int)(lb % (unsigned)xchunks), rg = (int)((lb / (unsigned)xchunks) % (unsigned)rowgroups), zc = (int)(lb / ((unsigned)xchunks * (unsigned)rowgroups));
+    const int lx = (int)threadIdx.x % LX, ry = (int)threadIdx.x / LX, RB = kBlock / LX;
+    const int i0 = (xc * LX + lx) * VEC, j = rg * RB + ry;
+    const int kk_lo = zc * ZC, kk_hi = min(G.nzl, kk_lo + ZC);
+    if (i0 < n && j < n) {     // (n % VEC == 0: a vector never straddles the end of a row)
+        size_t c = (size_t)(kk_lo + 1) * plane + (size_t)j * n + i0;
+        for (int kk = kk_lo; kk < kk_hi; kk++, c += plane) {
+            T v[VEC];
+            load_vec<T, VEC>(b + c, v);
+#pragma unroll
+            for (int e = 0; e < VEC; e++) mysum += (double)v[e];
+        }
+    }
+    mysum = block_sum(mysum, red);
+    if (threadIdx.x == 0) sum_partials[blockIdx.x] = mysum;
 }
 
 // Register-blocked z-march: a lane owns VEC consecutive x nodes of RY consecutive rows and walks ZC planes keeping the

@@ -746,6 +746,7 @@ struct Solver final : SolverBase {
             for (int a = 0; a < 3; a++) P.pad_pos[a] = P.bbox_min[a] - (double)n * cell;
             P.lambda = lambda;
             P.cexp = -lambda * 2954.639443740597;  // 2048 / ln 2
+            P.cexp_inv = 1.0 / std::fabs(P.cexp);
             P.S = n_clusters * conv_cluster<T>();
             P.n_clusters = n_clusters;
             P.far_gap = conv_reference ? 3.0e38f : (float)conv_far_gap;   // (REFERENCE_F64: no cluster is far)
@@ -938,21 +939,45 @@ struct Solver final : SolverBase {
                 continue;
             }
             constexpr int V = vec_width<T>();
-            const int lanes = (n + V - 1) / V;
-            int LX = 1;
-            while (LX < lanes && LX < kBlock) LX *= 2;
-            const int xchunks = (lanes + LX - 1) / LX, RB = kBlock / LX, rowgroups = (n + RB - 1) / RB;
-            // planes per workgroup: 4 measured best at 256^3 and 512^3 in both precisions (512^3 fp64: 0.79 ms against 0.84 with 32 and 0.80 with 2 --
-            // many short marches keep more loads in flight than few deep ones; the first plane's extra load is a fifth of a march)
-            const int ZC = 4;
-            const unsigned nblk = (unsigned)((long long)xchunks * rowgroups * ((sl.nzl + ZC - 1) / ZC));
-            sl.div_partials.alloc(nblk);
-            sl.div_sum_blocks = (int)nblk;
-            hipLaunchKernelGGL((divergence_march_kernel<T, V>), dim3(nblk), dim3(kBlock), 0, stream, sl.gp, LX, xchunks, rowgroups, ZC, sl.Y0.p, sl.Y1.p, sl.Y2.p,
+            const DivGeometry g = div_geometry(sl);
+            sl.div_partials.alloc(g.nblk);
+            sl.div_sum_blocks = (int)g.nblk;
+            hipLaunchKernelGGL((divergence_march_kernel<T, V>), dim3(g.nblk), dim3(kBlock), 0, stream, sl.gp, g.LX, g.xchunks, g.rowgroups, g.ZC, sl.Y0.p, sl.Y1.p, sl.Y2.p,
                                sl.r.p, scrub, sl.div_partials.p);
         }
         HIPCHK(hipGetLastError());
         have_div = true;
+    }
+    // launch shape of divergence_march_kernel on a slab
+    struct DivGeometry {
+        int LX, xchunks, rowgroups, ZC;
+        unsigned nblk;
+    };
+    DivGeometry div_geometry(const Slab<T>& sl) const {
+        constexpr int V = vec_width<T>();
+        const int lanes = (n + V - 1) / V;
+        int LX = 1;
+        while (LX < lanes && LX < kBlock) LX *= 2;
+        const int xchunks = (lanes + LX - 1) / LX, RB = kBlock / LX, rowgroups = (n + RB - 1) / RB;
+        // planes per workgroup: 4 measured best at 256^3 and 512^3 in both precisions (512^3 fp64: 0.79 ms against 0.84 with 32 and 0.80 with 2 --
+        // many short marches keep more loads in flight than few deep ones; the first plane's extra load is a fifth of a march)
+        const int ZC = 4;
+        return {LX, xchunks, rowgroups, ZC, (unsigned)((long long)xchunks * rowgroups * ((sl.nzl + ZC - 1) / ZC))};
+    }
+    // The partial sums of a b that this solver's divergence kernel did not write (the gathered solve: b comes from every rank's slabs), formed in that kernel's own
+    // order: the dual solve's 1^T b -- and with it phi -- is then bit for bit what the one-process solve of the same Y returns, whatever the values (with sum_kernel's
+    // order the two sums agreed only where their roundings happened to: tests/test_iso_indexed.py::test_two_ranks holds the two solves to each other bit for bit).
+    void sum_b_in_div_order(Slab<T>& sl, hipStream_t on) {
+        if (vec == 1) {   // (the one-node-per-thread divergence kernel sums nothing: sum_kernel in either solve)
+            sl.div_sum_blocks = 0;
+            return;
+        }
+        constexpr int V = vec_width<T>();
+        const DivGeometry g = div_geometry(sl);
+        sl.div_partials.alloc(g.nblk);
+        sl.div_sum_blocks = (int)g.nblk;
+        hipLaunchKernelGGL((sum_march_kernel<T, V>), dim3(g.nblk), dim3(kBlock), 0, on, sl.gp, g.LX, g.xchunks, g.rowgroups, g.ZC, sl.r.p, sl.div_partials.p);
+        HIPCHK(hipGetLastError());
     }
 
     void run_conv(int step1_arith) override {
@@ -2852,7 +2877,7 @@ struct Solver final : SolverBase {
         fclk.e_start.record(F.stream);   // (never read -- has_step1 is false --: recorded so that the calls on F.stream stay what they were)
         fclk.e_setup.record(F.stream);
         F.have_div = true;
-        fs.div_sum_blocks = 0;   // (b came from the ranks' slabs: no partial sums of the whole grid)
+        F.sum_b_in_div_order(fs, F.stream);   // (b came from the ranks' slabs: its partial sums in the order the whole grid's divergence kernel would have formed them)
         shm_stats cst;
         memset(&cst, 0, sizeof cst);
         // "did not converge" still leaves phi (include/shm_grid.h: SHM_ERR_NOCONV): finish the hand-over, then report it
