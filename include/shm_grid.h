@@ -349,6 +349,42 @@ shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nod
  * blocks of 8 x 8 x 4 nodes; the counts of two layers (of two blocks of a layer) differ by at most one unless the smaller stratum is taken whole. */
 int64_t shm_audit_sample_nodes(int32_t n, int32_t k_begin, int32_t k_end, int64_t count, uint64_t seed, int64_t* nodes_out);
 
+/* --- ray casts against a level set of the resident phi ---------------------------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the entry points by their symbols (dlsym).
+ * Where does the ray o + t d first meet the surface phi = isovalue?  (The reference answers it on screen: Polyscope ray-casts the isosurface of the node
+ *   scalar quantity, src/main.cpp:121-123.)
+ * Field: F is the trilinear interpolant shm_grid_sample evaluates -- the same cell rule, box and fp64 arithmetic, nodes read from the handle's own array
+ *   (an SHM_F32 handle reads fp32 nodes and promotes them).  F is continuous across cell faces, so a ray that runs inside a face or along a grid line has
+ *   one answer whichever adjacent cell is walked.
+ *   On an axis with d[a] = 0 the ray's weight is one number, and an origin that is exactly the position of its cell's upper plane has weight 1 exactly
+ *   (shm_grid_sample's rule for the upper faces of the box, kept for every plane), so an edge-aligned ray meets the surface where marching cubes puts its vertex.
+ * Answer: for ray q the smallest t in [t_min, t_max] with o + t d in the closed box and f(t) = F(o + t d) - isovalue = 0, a crossing being a sign change
+ *   of f or an exact zero.  d need not be normalised: t is in units of d.  A ray that starts with f < 0 (inside) returns the point where it leaves; there
+ *   is no separate mode: the caller tells entering from leaving by the sign of d . grad.  Sphere tracing is not used (nothing bounds |grad phi| by 1 for
+ *   this field): empty space is skipped exactly, from the minima and maxima of phi over bricks of 8^3 cells, and inside a cell the cubic of f along the ray
+ *   is split at its extrema and the first bracketing piece bisected, so a thin sheet cannot be stepped over.
+ * Outputs: t_out[q] is t, or NaN for "no hit".  grad_out (optional) is the gradient of the interpolant at the hit, by shm_grid_sample's formula in the
+ *   cell the ray was in when it hit; not normalised; NaN x 3 for no hit.  *n_hits counts the finite answers.  Every entry is written, outputs are in
+ *   input order, and two calls give bit-identical buffers.  Rays that are neighbours in space should be neighbours in the arrays: a wavefront of 64
+ *   consecutive rays runs as long as its longest ray.
+ * NaN, not an error: a non-finite origin or direction; d = 0; t_min > t_max; a ray that misses the box (with d[a] = 0, an o[a] outside
+ *   [bbox_min[a], (n-1)*cell + bbox_min[a]] is a miss).  t_max = +inf is valid.
+ * Non-finite nodes: a cell with a non-finite corner is never hit, and a brick that holds one is never skipped.
+ * State: valid whenever shm_grid_sample is; SHM_ERR_STATE before a solve or after a test entry point that overwrote phi.  phi, Y, both isosurface meshes
+ *   and every flag are left as they were.  The brick extrema (1/256 of phi) are built at the first cast of a phi -- about 1.4 reads of phi -- and kept
+ *   until phi is replaced.
+ * Errors: SHM_ERR_INVALID for Q < 0 or Q > 2^48, for NULL origins / dirs / t_out with Q > 0, or for a NaN isovalue.  Q = 0 is valid.
+ * Scope: world == 1 only (any local_slabs); with world > 1 both calls return SHM_ERR_STATE: a ray crosses other ranks' planes.
+ * shm_grid_raycast: host buffers, fp64; origins and dirs [3Q] xyz-interleaved, t_out [Q], grad_out [3Q] or NULL.  The rays stream through the device in
+ *   chunks of 2^20 through pinned staging buffers the handle keeps.
+ * shm_grid_raycast_device: device buffers of the handle's precision on the handle's device, same layouts; synchronous.  Every pointer is checked
+ *   (hipPointerGetAttributes / hipMemGetAddressRange) before anything is enqueued: host memory, another device's memory or an allocation smaller than Q
+ *   rays is SHM_ERR_INVALID. */
+shm_status shm_grid_raycast(shm_solver* s, int64_t Q, const double* origins /* [3Q] */, const double* dirs /* [3Q] */, double isovalue, double t_min, double t_max,
+                            double* t_out /* [Q] */, double* grad_out /* [3Q] or NULL */, int64_t* n_hits);
+shm_status shm_grid_raycast_device(shm_solver* s, int64_t Q, const void* d_origins, const void* d_dirs, double isovalue, double t_min, double t_max, void* d_t,
+                                   void* d_grad, int64_t* n_hits);
+
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */
 shm_status shm_comm_unique_id(void* out128);

@@ -229,6 +229,15 @@ shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, v
     return guard(s, [&] { s->impl->sample_device(Q, d_pts, d_phi, d_grad, n_answered); });
 }
 
+shm_status shm_grid_raycast(shm_solver* s, int64_t Q, const double* origins, const double* dirs, double isovalue, double t_min, double t_max, double* t_out,
+                            double* grad_out, int64_t* n_hits) {
+    return guard(s, [&] { s->impl->raycast(Q, origins, dirs, isovalue, t_min, t_max, t_out, grad_out, n_hits); });
+}
+shm_status shm_grid_raycast_device(shm_solver* s, int64_t Q, const void* d_origins, const void* d_dirs, double isovalue, double t_min, double t_max, void* d_t,
+                                   void* d_grad, int64_t* n_hits) {
+    return guard(s, [&] { s->impl->raycast_device(Q, d_origins, d_dirs, isovalue, t_min, t_max, d_t, d_grad, n_hits); });
+}
+
 shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) {
     return guard(s, [&] { s->impl->audit_step1(count, nodes, dy_out, ratio_out, out); });
 }

@@ -571,6 +571,8 @@ struct SolverBase {
     virtual void get_isosurface_indexed(double*, int64_t*) = 0;
     virtual void get_isosurface_indexed_device(void*, void*) = 0;
     virtual void audit_step1(int64_t, const int64_t*, double*, double*, shm_step1_audit*) = 0;
+    virtual void raycast(int64_t, const double*, const double*, double, double, double, double*, double*, int64_t*) = 0;
+    virtual void raycast_device(int64_t, const void*, const void*, double, double, double, void*, void*, int64_t*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

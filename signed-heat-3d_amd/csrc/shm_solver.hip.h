@@ -22,6 +22,7 @@
 #include "shm_sample.hip.h"
 #include "shm_audit.hip.h"
 #include "shm_iso_indexed.hip.h"
+#include "shm_raycast.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -213,6 +214,8 @@ struct Solver final : SolverBase {
         if (comm) (void)Rccl::get().CommDestroy(comm);
         if (h_pinned) (void)hipHostFree(h_pinned);
         for (void* b : smp_pinned)
+            if (b) (void)hipHostFree(b);
+        for (void* b : ray_pinned)
             if (b) (void)hipHostFree(b);
         slabs.clear();
         if (stream) (void)hipStreamDestroy(stream);
@@ -538,6 +541,7 @@ struct Solver final : SolverBase {
         have_problem = true;
         have_conv = have_div = have_phi = have_constraints = false;
         iso_idx_valid = false;
+        ray_bricks_valid = false;
         audit_src_ready = false;
         // (round 6: the whole-grid solver of the gathered multi-rank solve is created when a solve first takes that path -- ensure_full() -- so that a run whose solves
         // all take the slab-distributed forms never allocates whole-grid arrays on every rank)
@@ -3160,6 +3164,7 @@ struct Solver final : SolverBase {
         const Plan p = plan_solve(in);
         if (p.status != SHM_OK) throw Error(p.status, p.error);
         iso_idx_valid = false;   // q is about to be overwritten: the indexed mesh no longer belongs to the resident phi
+        ray_bricks_valid = false;
         const bool pre = p.precond;
         if (!(o.tol > 0.)) o.tol = sizeof(T) == 8 ? 1e-8 : 1e-5;
         if (o.max_iters <= 0) o.max_iters = 20 * n;
@@ -3318,6 +3323,7 @@ struct Solver final : SolverBase {
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_phi = false;  // q now holds L u, not phi
         iso_idx_valid = false;
+        ray_bricks_valid = false;
     }
 
     void get_constraints(int64_t* nodes, double* coeffs, int32_t* m_out) override {
@@ -3644,6 +3650,140 @@ struct Solver final : SolverBase {
         HIPCHK(hipStreamSynchronize(stream));
     }
 
+    // ---- ray casts against a level set of the resident phi (shm_raycast.hip.h) ----------------------------------------------------------------------------
+    // Working memory: one {min, max} pair per brick of 8^3 cells (1/256 of phi), the slab table, and for the host entry two staging slots of 2^20 rays.
+    // The bricks are built at the first cast of a phi and kept until phi is replaced (ray_bricks_valid falls with iso_idx_valid); freed with the handle.
+    static constexpr int64_t kRayChunk = (int64_t)1 << 20;   // rays per chunk of the host entry: 80 MiB of pinned staging and as much device memory (two slots)
+    DevArray<T> d_ray_minmax;
+    DevArray<RaySlab<T>> d_ray_slabs;
+    DevArray<unsigned long long> d_ray_hits;
+    DevArray<double> ray_dev[2];                 // per slot: origins [3C], directions [3C], t [C], gradient [3C]
+    void* ray_pinned[2] = {nullptr, nullptr};
+    int64_t ray_cap = 0;
+    std::unique_ptr<Event> ray_done[2];
+    bool ray_bricks_valid = false;
+
+    void raycast_check(const char* who, int64_t Q, const void* org, const void* dir, const void* t, double iso) {
+        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
+        if (Q > ((int64_t)1 << 48)) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 rays", who));   // (the byte counts below must not wrap)
+        if (Q > 0 && (!org || !dir || !t)) throw Error(SHM_ERR_INVALID, fmt("%s: null origins, directions or output", who));
+        if (iso != iso) throw Error(SHM_ERR_INVALID, fmt("%s: the isovalue is NaN", who));
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        if (cfg.world != 1)
+            throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: a ray crosses the planes of other ranks (gather phi, or cast on a single-process handle)", who));
+    }
+    RayParams raycast_begin(double iso, double t_min, double t_max) {
+        HIPCHK(hipSetDevice(cfg.device));
+        halo_exchange(ARR_Q);  // phi lives in q; cells of a slab's top plane read the plane above from its ghost layer
+        RayParams P;
+        P.n = n;
+        P.nb = (n - 1 + kRayBrick - 1) / kRayBrick;
+        P.nslabs = (int)slabs.size();
+        P.cell = cell;
+        for (int a = 0; a < 3; a++) {
+            P.bbox_min[a] = bbox_min[a];
+            P.hi[a] = (n - 1) * cell + bbox_min[a];
+        }
+        P.iso = iso;
+        P.t_min = t_min;
+        P.t_max = t_max;
+        if (!ray_bricks_valid) {
+            std::vector<RaySlab<T>> tab(slabs.size());
+            for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
+            d_ray_slabs.upload(tab, stream);
+            const size_t nbricks = (size_t)P.nb * P.nb * P.nb;
+            d_ray_minmax.alloc(2 * nbricks);
+            for (auto& e : ray_done)
+                if (!e) e.reset(new Event());
+            hipLaunchKernelGGL((ray_bricks_kernel<T>), dim3((unsigned)((nbricks + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, stream, P, d_ray_slabs.p,
+                               d_ray_minmax.p);
+            HIPCHK(hipGetLastError());
+            ray_bricks_valid = true;
+        }
+        d_ray_hits.alloc(4);   // [0] hits; [1..3] only in the counting build (SHM_RAY_COUNT)
+        HIPCHK(hipMemsetAsync(d_ray_hits.p, 0, 4 * sizeof(unsigned long long), stream));
+        return P;
+    }
+    int64_t raycast_end() {
+        unsigned long long c[4] = {0, 0, 0, 0};
+        HIPCHK(hipMemcpyAsync(c, d_ray_hits.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+#ifdef SHM_RAY_COUNT
+        fprintf(stderr, "ray_count brick_steps %llu cells_examined %llu cells_kept %llu\n", c[1], c[2], c[3]);
+#endif
+        return (int64_t)c[0];
+    }
+    template <typename TIO> void launch_raycast(const RayParams& P, int64_t Q, const TIO* org, const TIO* dir, TIO* t, TIO* grad) {
+        if (Q <= 0) return;
+        const int grid = grid_for((size_t)Q, 16384);
+        if (grad) hipLaunchKernelGGL((raycast_kernel<T, TIO, true>), dim3(grid), dim3(kBlock), 0, stream, P, Q, org, dir, d_ray_slabs.p, d_ray_minmax.p, t, grad, d_ray_hits.p);
+        else hipLaunchKernelGGL((raycast_kernel<T, TIO, false>), dim3(grid), dim3(kBlock), 0, stream, P, Q, org, dir, d_ray_slabs.p, d_ray_minmax.p, t, grad, d_ray_hits.p);
+        HIPCHK(hipGetLastError());
+    }
+
+    // host buffers: the rays stream through two pinned staging slots of their own (a ray is 6 + 4 doubles against sample's 3 + 4), as in sample()
+    void raycast(int64_t Q, const double* org, const double* dir, double iso, double t_min, double t_max, double* t_out, double* grad, int64_t* n_hits) override {
+        raycast_check("raycast", Q, org, dir, t_out, iso);
+        const RayParams P = raycast_begin(iso, t_min, t_max);
+        const int64_t C = std::min(Q, kRayChunk);
+        if (C > ray_cap) {
+            for (int b = 0; b < 2; b++) {
+                if (ray_pinned[b]) HIPCHK(hipHostFree(ray_pinned[b]));
+                ray_pinned[b] = nullptr;
+                ray_dev[b].release();
+            }
+            ray_cap = 0;
+            for (int b = 0; b < 2; b++) {
+                HIPCHK(hipHostMalloc(&ray_pinned[b], (size_t)C * 10 * sizeof(double)));
+                ray_dev[b].alloc((size_t)C * 10);
+            }
+            ray_cap = C;
+        }
+        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
+        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
+            const int b = (int)(c & 1);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            HIPCHK(hipEventSynchronize(ray_done[b]->e));
+            const double* hb = (const double*)ray_pinned[b];
+            memcpy(t_out + q0, hb + 6 * C, (size_t)m * sizeof(double));
+            if (grad) memcpy(grad + 3 * q0, hb + 7 * C, (size_t)m * 3 * sizeof(double));
+        };
+        for (int64_t c = 0; c < nchunks; c++) {
+            const int b = (int)(c & 1);
+            if (c >= 2) finish(c - 2);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            double* hb = (double*)ray_pinned[b];
+            double* db = ray_dev[b].p;
+            memcpy(hb, org + 3 * q0, (size_t)m * 3 * sizeof(double));
+            memcpy(hb + 3 * C, dir + 3 * q0, (size_t)m * 3 * sizeof(double));
+            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(db + 3 * C, hb + 3 * C, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+            launch_raycast<double>(P, m, db, db + 3 * C, db + 6 * C, grad ? db + 7 * C : nullptr);
+            HIPCHK(hipMemcpyAsync(hb + 6 * C, db + 6 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (grad) HIPCHK(hipMemcpyAsync(hb + 7 * C, db + 7 * C, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipEventRecord(ray_done[b]->e, stream));
+        }
+        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        const int64_t a = raycast_end();
+        if (n_hits) *n_hits = a;
+    }
+    void raycast_device(int64_t Q, const void* org, const void* dir, double iso, double t_min, double t_max, void* t_out, void* grad, int64_t* n_hits) override {
+        const char* who = "raycast_device";
+        raycast_check(who, Q, org, dir, t_out, iso);
+        HIPCHK(hipSetDevice(cfg.device));
+        if (Q > 0) {
+            check_device_buffer(org, (size_t)Q * 3 * sizeof(T), "the origin buffer", who, "the Q rays asked for");
+            check_device_buffer(dir, (size_t)Q * 3 * sizeof(T), "the direction buffer", who, "the Q rays asked for");
+            check_device_buffer(t_out, (size_t)Q * sizeof(T), "the t buffer", who, "the Q rays asked for");
+            if (grad) check_device_buffer(grad, (size_t)Q * 3 * sizeof(T), "the gradient buffer", who, "the Q rays asked for");
+        }
+        const RayParams P = raycast_begin(iso, t_min, t_max);
+        launch_raycast<T>(P, Q, (const T*)org, (const T*)dir, (T*)t_out, (T*)grad);
+        const int64_t a = raycast_end();
+        if (n_hits) *n_hits = a;
+    }
+
     // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------
     static constexpr int64_t kAuditChunk = (int64_t)1 << 22;   // nodes per launch: bounds the device buffers (36 B per node) whatever count is
     DevArray<double> d_audit_src;      // [6][S]: pos x, y, z, wnormal x, y, z -- fp64, planar, in the caller's order; uploaded at the first audit of a problem
@@ -3757,6 +3897,7 @@ struct Solver final : SolverBase {
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_conv = have_div = have_phi = false;
         iso_idx_valid = false;
+        ray_bricks_valid = false;
     }
 };
 

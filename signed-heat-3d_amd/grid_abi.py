@@ -21,7 +21,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
-               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
+               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
 class ShmError(RuntimeError):
@@ -121,6 +121,9 @@ def load_library():
         lib.shm_grid_audit_step1.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmStep1Audit)]
         lib.shm_audit_sample_nodes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p]
         lib.shm_audit_sample_nodes.restype = C.c_int64
+    if hasattr(lib, "shm_grid_raycast"):   # added within ABI 5: found by symbol
+        lib.shm_grid_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.shm_grid_raycast_device.argtypes = lib.shm_grid_raycast.argtypes
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -380,6 +383,43 @@ class GridSolver:
         self._chk(self._lib.shm_grid_sample_device(self._h, Q, points.data_ptr() if Q else None, phi.data_ptr() if Q else None,
                                                    g.data_ptr() if grad and Q else None, C.byref(na)))
         return (phi, g, na.value) if grad else (phi, na.value)
+
+    def raycast(self, origins, dirs, isovalue=0.0, t_min=0.0, t_max=float("inf"), grad=False):
+        """Where each ray origins[q] + t dirs[q] first meets the level set phi = isovalue of the resident phi (shm_grid_raycast): returns (t [Q], n_hits)
+        or, with grad=True, (t [Q], grad [Q, 3], n_hits), float64; NaN for a ray that does not hit.  t is in units of dirs[q], which need not be normalised;
+        grad is the interpolant's gradient at the hit, so dirs . grad < 0 says the ray entered and > 0 that it left.  Keep neighbouring rays neighbours."""
+        o, d = _f64(origins).reshape(-1, 3), _f64(dirs).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("raycast: origins and dirs must both be [Q, 3]")
+        Q = o.shape[0]
+        t = np.empty(Q, dtype=np.float64)
+        g = np.empty((Q, 3), dtype=np.float64) if grad else None
+        nh = C.c_int64()
+        self._chk(self._lib.shm_grid_raycast(self._h, Q, o.ctypes.data, d.ctypes.data, float(isovalue), float(t_min), float(t_max), t.ctypes.data,
+                                             g.ctypes.data if grad else None, C.byref(nh)))
+        return (t, g, nh.value) if grad else (t, nh.value)
+
+    def raycast_device(self, origins, dirs, isovalue=0.0, t_min=0.0, t_max=float("inf"), grad=False):
+        """The same on device memory (shm_grid_raycast_device), with sample_device's conventions: contiguous [Q, 3] torch tensors on this handle's device with
+        its dtype; returns torch tensors (t [Q], [grad [Q, 3],] n_hits) of that dtype on that device.  Import torch before this library is loaded."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("raycast_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        for x in (origins, dirs):
+            if x.dtype != dt or x.dim() != 2 or x.shape[1] != 3 or not x.is_contiguous():
+                raise ValueError("raycast_device: origins and dirs must be contiguous [Q, 3] %s tensors" % dt)
+        if origins.shape != dirs.shape or origins.device != dirs.device:
+            raise ValueError("raycast_device: origins and dirs must have one shape and one device")
+        Q = origins.shape[0]
+        t = torch.empty(Q, dtype=dt, device=origins.device)
+        g = torch.empty((Q, 3), dtype=dt, device=origins.device) if grad else None
+        if origins.is_cuda:
+            torch.cuda.current_stream(origins.device).synchronize()   # the rays may still be in flight on torch's stream
+        nh = C.c_int64()
+        self._chk(self._lib.shm_grid_raycast_device(self._h, Q, origins.data_ptr() if Q else None, dirs.data_ptr() if Q else None, float(isovalue),
+                                                    float(t_min), float(t_max), t.data_ptr() if Q else None, g.data_ptr() if grad and Q else None, C.byref(nh)))
+        return (t, g, nh.value) if grad else (t, nh.value)
 
     def audit_step1(self, nodes=None, count=4096, seed=0, per_node=False):
         """What the Step 1 behind the resident Y cost at sampled nodes (shm_grid_audit_step1): the struct as a dict, plus "nodes", "dy" and "ratio" with

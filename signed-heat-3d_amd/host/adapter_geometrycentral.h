@@ -16,6 +16,7 @@
 #include <array>
 #include <cmath>
 #include <iostream>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -111,6 +112,29 @@ class SignedHeatGridSolver {
         faces.resize((size_t)nt);
         for (int64_t a = 0; a < nv; a++) vertices[(size_t)a] = Vector3{v[3 * a], v[3 * a + 1], v[3 * a + 2]};
         for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
+    }
+
+    // Where each ray origins[q] + t dirs[q] first meets the level set phi = isoval of the last computeDistance(), cast on the device (shm_grid_raycast):
+    // t per ray in units of dirs[q], NaN for no hit; with gradients != nullptr the interpolant's gradient at each hit (dirs[q] . gradient < 0: entering).
+    std::vector<double> castRays(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double isoval = 0., double tMin = 0.,
+                                 double tMax = std::numeric_limits<double>::infinity(), std::vector<Vector3>* gradients = nullptr) {
+        if (!handle) throw std::runtime_error("castRays: computeDistance has not been called");
+        if (origins.size() != dirs.size()) throw std::runtime_error("castRays: origins and dirs differ in length");
+        size_t Q = origins.size();
+        std::vector<double> o(3 * Q), d(3 * Q), t(Q), g(gradients ? 3 * Q : 0);
+        for (size_t a = 0; a < Q; a++)
+            for (int b = 0; b < 3; b++) {
+                o[3 * a + b] = origins[a][b];
+                d[3 * a + b] = dirs[a][b];
+            }
+        int64_t hits = 0;
+        if (shm_grid_raycast(handle, (int64_t)Q, o.data(), d.data(), isoval, tMin, tMax, t.data(), gradients ? g.data() : nullptr, &hits) != SHM_OK)
+            throw std::runtime_error(shm_grid_last_error(handle));
+        if (gradients) {
+            gradients->resize(Q);
+            for (size_t a = 0; a < Q; a++) (*gradients)[a] = Vector3{g[3 * a], g[3 * a + 1], g[3 * a + 2]};
+        }
+        return t;
     }
 
   private:

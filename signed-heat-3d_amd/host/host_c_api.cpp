@@ -190,6 +190,29 @@ int shmh_sample(void* hv, int64_t Q, const double* pts, double* phi_out, double*
     });
 }
 
+// castRays through the C++ class: rays [3Q] + [3Q] against phi = isoval of the last compute_distance -> t_out [Q], grad_out [3Q] or NULL, *n_hits finite answers.
+int shmh_raycast(void* hv, int64_t Q, const double* origins, const double* dirs, double isoval, double t_min, double t_max, double* t_out, double* grad_out,
+                 int64_t* n_hits) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> o((size_t)Q), d((size_t)Q);
+        for (int64_t a = 0; a < Q; a++) {
+            o[(size_t)a] = Vector3{origins[3 * a], origins[3 * a + 1], origins[3 * a + 2]};
+            d[(size_t)a] = Vector3{dirs[3 * a], dirs[3 * a + 1], dirs[3 * a + 2]};
+        }
+        std::vector<Vector3> g;
+        const std::vector<double> t = h->solver.castRays(o, d, isoval, t_min, t_max, grad_out ? &g : nullptr);
+        int64_t hits = 0;
+        for (int64_t a = 0; a < Q; a++) {
+            t_out[a] = t[(size_t)a];
+            hits += t[(size_t)a] == t[(size_t)a] ? 1 : 0;
+            if (grad_out)
+                for (int b = 0; b < 3; b++) grad_out[3 * a + b] = g[(size_t)a][b];
+        }
+        if (n_hits) *n_hits = hits;
+    });
+}
+
 // isosurfaceIndexed through the C++ class, in two calls: vertices == NULL builds the mesh of the last compute_distance and returns the counts; with
 // buffers ([3 nv] doubles, [3 nt] int64) it builds again -- the canonical order makes the second mesh the first -- and copies it out.
 int shmh_isosurface_indexed(void* hv, double isoval, int64_t* nv, int64_t* nt, double* vertices, int64_t* triangles) {

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <string>
 
 #include "mesh_io.h"
@@ -30,12 +31,15 @@ static void usage() {
                  "      --export <file>   OBJ file of the isosurface (the demo writes ../export/isosurface.obj)\n"
                  "      --iso-indexed     Build the exported isosurface on the device in the canonical order (vertices by grid edge, triangles by cell)\n"
                  "      --query <file>    Points to evaluate phi at: raw little-endian float64 xyz triples\n"
-                 "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n";
+                 "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n"
+                 "      --rays <file>     Rays to cast against a level set of phi: raw little-endian float64, six values per ray (origin xyz, direction xyz)\n"
+                 "      --rays-out <file> Raw float64, four values per ray: t of the first hit in units of the direction (NaN: none), then the gradient there\n"
+                 "      --rays-iso <v>    The level the rays are cast against (default 0; independent of --iso)\n";
 }
 
 int main(int argc, char** argv) {
-    std::string path, out, exportPath, queryPath, queryOut;
-    double isoval = 0.;
+    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut;
+    double isoval = 0., raysIso = 0.;
     long long auditCount = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
@@ -67,11 +71,18 @@ int main(int argc, char** argv) {
         else if (s == "--iso-indexed") isoIndexed = true;
         else if (s == "--query") queryPath = need("--query");
         else if (s == "--query-out") queryOut = need("--query-out");
+        else if (s == "--rays") raysPath = need("--rays");
+        else if (s == "--rays-out") raysOut = need("--rays-out");
+        else if (s == "--rays-iso") raysIso = atof(need("--rays-iso"));
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
         else path = s;
     }
     if (queryPath.empty() != queryOut.empty()) {
         std::cerr << "--query and --query-out go together." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (raysPath.empty() != raysOut.empty()) {
+        std::cerr << "--rays and --rays-out go together." << std::endl;
         return EXIT_FAILURE;
     }
     if (backend.exactStep1 && backend.referenceStep1) {
@@ -145,6 +156,32 @@ int main(int argc, char** argv) {
             std::ofstream o(queryOut, std::ios::binary);
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
             std::cerr << "phi and its gradient at " << q.size() << " points written to " << queryOut << std::endl;
+        }
+        if (!raysPath.empty()) {
+            std::ifstream f(raysPath, std::ios::binary | std::ios::ate);
+            if (!f) throw std::runtime_error("cannot read " + raysPath);
+            const std::streamsize bytes = f.tellg();
+            if (bytes % (std::streamsize)(6 * sizeof(double)) != 0) throw std::runtime_error(raysPath + ": size is not a multiple of 48 bytes (float64 origin and direction)");
+            std::vector<double> raw((size_t)bytes / sizeof(double));
+            f.seekg(0);
+            f.read((char*)raw.data(), bytes);
+            std::vector<Vector3> ro(raw.size() / 6), rd(raw.size() / 6);
+            for (size_t a = 0; a < ro.size(); a++) {
+                ro[a] = Vector3{raw[6 * a], raw[6 * a + 1], raw[6 * a + 2]};
+                rd[a] = Vector3{raw[6 * a + 3], raw[6 * a + 4], raw[6 * a + 5]};
+            }
+            std::vector<Vector3> g;
+            const std::vector<double> t = solver.castRays(ro, rd, raysIso, 0., std::numeric_limits<double>::infinity(), &g);
+            std::vector<double> res(4 * ro.size());
+            size_t hits = 0;
+            for (size_t a = 0; a < ro.size(); a++) {
+                res[4 * a] = t[a];
+                hits += t[a] == t[a] ? 1 : 0;
+                for (int b = 0; b < 3; b++) res[4 * a + 1 + b] = g[a][b];
+            }
+            std::ofstream o(raysOut, std::ios::binary);
+            o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
+            std::cerr << ro.size() << " rays cast against phi = " << raysIso << ": " << hits << " hits, t and gradient written to " << raysOut << std::endl;
         }
     } catch (const std::exception& e) {
         std::cerr << "error: " << e.what() << std::endl;

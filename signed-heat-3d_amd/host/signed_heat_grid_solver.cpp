@@ -127,6 +127,27 @@ std::vector<double> SignedHeatGridSolver::evaluateFunction(const std::vector<Vec
     return phi;
 }
 
+std::vector<double> SignedHeatGridSolver::castRays(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double isoval, double tMin, double tMax,
+                                                   std::vector<Vector3>* gradients) {
+    if (!handle) throw std::runtime_error("castRays: computeDistance has not been called");
+    if (origins.size() != dirs.size()) throw std::runtime_error("castRays: origins and dirs differ in length");
+    const size_t Q = origins.size();
+    std::vector<double> o(3 * Q), d(3 * Q), t(Q), g(gradients ? 3 * Q : 0);
+    for (size_t a = 0; a < Q; a++)
+        for (int b = 0; b < 3; b++) {
+            o[3 * a + b] = origins[a][b];
+            d[3 * a + b] = dirs[a][b];
+        }
+    int64_t hits = 0;
+    if (shm_grid_raycast(handle, (int64_t)Q, o.data(), d.data(), isoval, tMin, tMax, t.data(), gradients ? g.data() : nullptr, &hits) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_raycast: ") + shm_grid_last_error(handle));
+    if (gradients) {
+        gradients->resize(Q);
+        for (size_t a = 0; a < Q; a++) (*gradients)[a] = Vector3{g[3 * a], g[3 * a + 1], g[3 * a + 2]};
+    }
+    return t;
+}
+
 VectorXd SignedHeatGridSolver::computeDistance(VertexPositionGeometry& geometry, const SignedHeat3DOptions& options) {
     if (options.rebuild || !gridBuilt) {
         const Vector3 c = centroid(geometry);

@@ -5,6 +5,7 @@
 // (signed_heat_grid_solver.cpp:30, never solved with) is not reproduced.
 #pragma once
 #include <memory>
+#include <limits>
 #include <vector>
 
 #include "../../include/shm_grid.h"
@@ -47,6 +48,13 @@ class SignedHeatGridSolver {
     // the LAST computeDistance() call at every point of q, evaluated on the device (shm_grid_sample; box, NaN and gradient rules in include/shm_grid.h).
     // With gradients != nullptr it is resized to q.size() and receives the gradient of the trilinear interpolant in each point's cell.
     std::vector<double> evaluateFunction(const std::vector<Vector3>& q, std::vector<Vector3>* gradients = nullptr);
+
+    // Where does each ray origins[q] + t dirs[q] first meet the level set phi = isoval of the LAST computeDistance() call?  Cast on the device against the
+    // trilinear interpolant evaluateFunction evaluates (shm_grid_raycast; rules in include/shm_grid.h): t per ray in units of dirs[q] (not normalised), NaN
+    // for no hit within [tMin, tMax] and the box.  With gradients != nullptr it receives the interpolant's gradient at each hit (NaN x 3 for no hit):
+    // dirs[q] . gradient < 0 says the ray entered the surface, > 0 that it left.  Stands for the picture Polyscope ray-casts in the demo (src/main.cpp:121-123).
+    std::vector<double> castRays(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double isoval = 0., double tMin = 0.,
+                                 double tMax = std::numeric_limits<double>::infinity(), std::vector<Vector3>* gradients = nullptr);
 
     // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
     // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).

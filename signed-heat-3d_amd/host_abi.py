@@ -41,6 +41,7 @@ def load_host_library():
                                     C.POINTER(C.c_int64)]
     lib.shmh_compute_distance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(ShmStats)]
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shmh_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.argtypes = [C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.restype = None
@@ -125,6 +126,20 @@ class HostSolver:
         g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
         self._chk(self._lib.shmh_sample(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None))
         return (phi, g) if grad else phi
+
+    def raycast(self, origins, dirs, isovalue=0.0, t_min=0.0, t_max=float("inf"), grad=False):
+        """castRays of the C++ mirror: where each ray origins[q] + t dirs[q] first meets phi = isovalue of the last compute_distance (shm_grid_raycast).
+        Returns (t [Q], n_hits) or, with grad=True, (t [Q], grad [Q, 3], n_hits), float64; NaN for a ray that does not hit."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("raycast: origins and dirs must both be [Q, 3]")
+        t = np.empty(o.shape[0], dtype=np.float64)
+        g = np.empty((o.shape[0], 3), dtype=np.float64) if grad else None
+        nh = C.c_int64()
+        self._chk(self._lib.shmh_raycast(self._h, o.shape[0], o.ctypes.data, d.ctypes.data, float(isovalue), float(t_min), float(t_max), t.ctypes.data,
+                                         g.ctypes.data if grad else None, C.byref(nh)))
+        return (t, g, nh.value) if grad else (t, nh.value)
 
     def isosurface_indexed(self, isovalue=0.0):
         """isosurfaceIndexed of the C++ mirror: the marching-cubes surface of the last compute_distance, welded and numbered on the device in the
