@@ -385,6 +385,53 @@ shm_status shm_grid_raycast(shm_solver* s, int64_t Q, const double* origins /* [
 shm_status shm_grid_raycast_device(shm_solver* s, int64_t Q, const void* d_origins, const void* d_dirs, double isovalue, double t_min, double t_max, void* d_t,
                                    void* d_grad, int64_t* n_hits);
 
+/* --- redistancing: a signed distance to a level set of the resident phi -----------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the three entry points by their symbols (dlsym).
+ * phi is a Poisson fit to a unit vector field: nothing bounds |grad phi| by 1 (on the 64^3 bunny the central-difference gradient runs from 0.08 to 2.0),
+ *   so phi - c is not the distance to the surface phi = c, and an offset surface taken from phi sits cells away from where its value says.
+ *   shm_grid_redistance solves |grad psi| = 1 with the level set phi = isovalue as boundary data, by the first-order Godunov upwind scheme, on the device
+ *   (a block fast iterative method, csrc/shm_redistance.hip.h), and keeps psi resident beside phi.  (The reference's counterpart is the contour slider's
+ *   offset surfaces, src/main.cpp:160-166.)
+ * Scheme: f = phi - isovalue in fp64 on the handle's own nodes (an SHM_F32 handle reads fp32 nodes and promotes them); h = cell.
+ *   Inside: f < 0, the isosurface's own convention; s = -1 inside, +1 otherwise.
+ *   Cut edge: two axis neighbours, both in the grid and finite, with (f_p < 0) != (f_q < 0).  A node with a cut edge is frozen at u = |f| / g, where
+ *     g = sqrt(gx^2 + gy^2 + gz^2) and g_a is the largest of |f_+a - f| / h, |f - f_-a| / h and |f_+a - f_-a| / (2 h) over the terms whose neighbours exist
+ *     and are finite (gradient-normalised, after Russo and Smereka): g > 0, and u <= h along every cut edge.  Frozen nodes are never updated.
+ *   Every other node starts at +inf and is iterated to the fixed point of u <- min(u, t), t accepted only when t < band.  With a <= b <= c the sorted
+ *     per-axis minima of the two neighbours' u (a missing or non-finite neighbour counts as +inf):
+ *       t = a + h;  if t <= b keep it;
+ *       else t = ((a + b) + sqrt(2 h^2 - (b - a)^2)) / 2;  if t <= c keep it;
+ *       else t = ((a + b + c) + sqrt(3 h^2 - ((b - a)^2 + (c - a)^2 + (c - b)^2))) / 3.
+ *   Arithmetic: fp64, unfused, as shm_grid_sample; u is stored in the handle's precision, rounded once per store (t is rounded, then compared).  The
+ *     discrete solution is unique: psi does not depend on the order of the updates, on local_slabs, or on the call (two calls: bit-identical psi).
+ *   Result: psi = s min(u, band).  Nodes the front never reached hold s band (+-inf with band = +inf).  A node whose phi is not finite is a wall for its
+ *     neighbours, holds NaN and is counted in n_nonfinite.  With no cut edge anywhere: SHM_OK, n_frozen = 0, psi = s band everywhere.
+ * Known limit: psi < 0 exactly where phi < isovalue, so every cell keeps its marching-cubes case, but a vertex moves along its edge: by <= 0.016 cell at the
+ *   smooth offset levels of the 24^3 .. 64^3 fixtures, by up to 0.62 cell at isovalue 0, where phi is kinked at cell scale around the constraint cells.
+ *   Extract the surface from phi; use psi for distances.  The frozen values are first-order: no sub-cell-exact initialisation.
+ * State: valid whenever shm_grid_sample is; SHM_ERR_STATE before a solve, after a test entry point that overwrote phi, and with world > 1 (any local_slabs
+ *   is fine).  phi, Y, both isosurface meshes, the brick extrema and every flag are left as they were.  psi (n^3 values of the handle's precision) stays
+ *   resident until phi is replaced or the handle is destroyed.
+ * Errors: SHM_ERR_INVALID for a NaN or infinite isovalue, or for band <= 0 or NaN (band = +inf is the whole grid).  SHM_ERR_NOCONV, with no psi kept, if
+ *   blocks are still active after 24 ceil(n / 8) + 16 rounds (a round is one launch per checkerboard colour); not observed.
+ * shm_grid_get_redistanced: host buffer, fp64, node order of shm_grid_get_phi.  shm_grid_get_redistanced_device: a device buffer of the handle's precision on
+ *   the handle's device, checked as shm_grid_sample_device checks its buffers: host memory, another device's memory or an allocation smaller than n^3
+ *   values is SHM_ERR_INVALID.  Both return SHM_ERR_STATE before a shm_grid_redistance and after anything that replaced or invalidated phi. */
+typedef struct {
+    int64_t n_frozen;        /* nodes with a cut edge */
+    int64_t n_reached;       /* nodes with |psi| < band */
+    int64_t n_nonfinite;     /* nodes whose phi is not finite (psi = NaN) */
+    int64_t n_block_updates; /* 8^3-block updates over all rounds */
+    int32_t n_rounds;        /* rounds run: the last one left no block active */
+    int32_t reserved;
+    double max_abs;          /* max |psi| over the finite, reached nodes */
+    double isovalue, band;
+    double ms;               /* device time of the call */
+} shm_redistance_stats;
+shm_status shm_grid_redistance(shm_solver* s, double isovalue, double band, shm_redistance_stats* out /* or NULL */);
+shm_status shm_grid_get_redistanced(shm_solver* s, double* psi_out /* [n^3] fp64 */);
+shm_status shm_grid_get_redistanced_device(shm_solver* s, void* d_psi /* [n^3], handle precision */);
+
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */
 shm_status shm_comm_unique_id(void* out128);

@@ -238,6 +238,16 @@ shm_status shm_grid_raycast_device(shm_solver* s, int64_t Q, const void* d_origi
     return guard(s, [&] { s->impl->raycast_device(Q, d_origins, d_dirs, isovalue, t_min, t_max, d_t, d_grad, n_hits); });
 }
 
+shm_status shm_grid_redistance(shm_solver* s, double isovalue, double band, shm_redistance_stats* out) {
+    return guard(s, [&] { s->impl->redistance(isovalue, band, out); });
+}
+shm_status shm_grid_get_redistanced(shm_solver* s, double* psi_out) {
+    return guard(s, [&] { s->impl->get_redistanced(psi_out); });
+}
+shm_status shm_grid_get_redistanced_device(shm_solver* s, void* d_psi) {
+    return guard(s, [&] { s->impl->get_redistanced_device(d_psi); });
+}
+
 shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) {
     return guard(s, [&] { s->impl->audit_step1(count, nodes, dy_out, ratio_out, out); });
 }

@@ -573,6 +573,9 @@ struct SolverBase {
     virtual void audit_step1(int64_t, const int64_t*, double*, double*, shm_step1_audit*) = 0;
     virtual void raycast(int64_t, const double*, const double*, double, double, double, double*, double*, int64_t*) = 0;
     virtual void raycast_device(int64_t, const void*, const void*, double, double, double, void*, void*, int64_t*) = 0;
+    virtual void redistance(double, double, shm_redistance_stats*) = 0;
+    virtual void get_redistanced(double*) = 0;
+    virtual void get_redistanced_device(void*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

@@ -23,6 +23,7 @@
 #include "shm_audit.hip.h"
 #include "shm_iso_indexed.hip.h"
 #include "shm_raycast.hip.h"
+#include "shm_redistance.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -542,6 +543,7 @@ struct Solver final : SolverBase {
         have_conv = have_div = have_phi = have_constraints = false;
         iso_idx_valid = false;
         ray_bricks_valid = false;
+        redist_valid = false;
         audit_src_ready = false;
         // (round 6: the whole-grid solver of the gathered multi-rank solve is created when a solve first takes that path -- ensure_full() -- so that a run whose solves
         // all take the slab-distributed forms never allocates whole-grid arrays on every rank)
@@ -3165,6 +3167,7 @@ struct Solver final : SolverBase {
         if (p.status != SHM_OK) throw Error(p.status, p.error);
         iso_idx_valid = false;   // q is about to be overwritten: the indexed mesh no longer belongs to the resident phi
         ray_bricks_valid = false;
+        redist_valid = false;
         const bool pre = p.precond;
         if (!(o.tol > 0.)) o.tol = sizeof(T) == 8 ? 1e-8 : 1e-5;
         if (o.max_iters <= 0) o.max_iters = 20 * n;
@@ -3324,6 +3327,7 @@ struct Solver final : SolverBase {
         have_phi = false;  // q now holds L u, not phi
         iso_idx_valid = false;
         ray_bricks_valid = false;
+        redist_valid = false;
     }
 
     void get_constraints(int64_t* nodes, double* coeffs, int32_t* m_out) override {
@@ -3784,6 +3788,121 @@ struct Solver final : SolverBase {
         if (n_hits) *n_hits = a;
     }
 
+    // ---- redistancing of the resident phi (shm_redistance.hip.h) ----------------------------------------------------------------------------------------------
+    // Working memory: psi itself (n^3 values of the handle's precision, resident until phi is replaced: redist_valid falls with iso_idx_valid), one flag per
+    // 8^3 block, one "anything active" word per round and the counters.  Nothing of the solver is borrowed or written: phi is read through the slab table.
+    DevArray<T> d_psi;
+    DevArray<RaySlab<T>> d_rd_slabs;
+    DevArray<int> d_rd_active, d_rd_any;
+    DevArray<unsigned long long> d_rd_cnt;
+    std::unique_ptr<Event> rd_ev[2];
+    bool redist_valid = false;
+
+    void redistance(double iso, double band, shm_redistance_stats* out) override {
+        if (!(iso - iso == 0.)) throw Error(SHM_ERR_INVALID, "redistance: the isovalue is not finite");
+        if (!(band > 0.)) throw Error(SHM_ERR_INVALID, "redistance: the band must be positive (+inf: the whole grid)");
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        if (cfg.world != 1)
+            throw Error(SHM_ERR_STATE, "redistance: world > 1 is not supported: a distance crosses the planes of other ranks (gather phi, or use a single-process handle)");
+        HIPCHK(hipSetDevice(cfg.device));
+        redist_valid = false;
+        RedistParams P;
+        P.n = n;
+        P.nb = (n + kRedistTile - 1) / kRedistTile;
+        P.nslabs = (int)slabs.size();
+        P.h = cell;
+        P.iso = iso;
+        P.band = band;
+        const size_t nblocks = (size_t)P.nb * P.nb * P.nb;
+        const int cap = 24 * P.nb + 16;   // rounds: a value crosses at least one block per round, and a causal chain is at most 3 nb blocks long
+        std::vector<RaySlab<T>> tab(slabs.size());
+        for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
+        d_rd_slabs.upload(tab, stream);
+        d_psi.alloc((size_t)n * n * n);
+        d_rd_active.alloc(nblocks);
+        d_rd_any.alloc((size_t)cap);
+        d_rd_cnt.alloc(kRdCounters);
+        for (auto& e : rd_ev)
+            if (!e) e.reset(new Event());
+        rd_ev[0]->record(stream);
+        HIPCHK(hipMemsetAsync(d_rd_active.p, 0, nblocks * sizeof(int), stream));
+        HIPCHK(hipMemsetAsync(d_rd_any.p, 0, (size_t)cap * sizeof(int), stream));
+        HIPCHK(hipMemsetAsync(d_rd_cnt.p, 0, kRdCounters * sizeof(unsigned long long), stream));
+        hipLaunchKernelGGL((redist_init_kernel<T>), dim3((unsigned)nblocks), dim3(kBlock), 0, stream, P, d_rd_slabs.p, d_psi.p, d_rd_active.p, d_rd_cnt.p);
+        HIPCHK(hipGetLastError());
+        unsigned long long c[kRdCounters] = {};
+        HIPCHK(hipMemcpyAsync(c, d_rd_cnt.p, 2 * sizeof c[0], hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        // the rounds: two launches each, kRedistPoll rounds between two looks at their words.  Round r is the last one iff it left no flag set, any[r] == 0;
+        // the rounds enqueued behind it find nothing active.  The loop ends at `cap` whatever the device wrote.
+        int rounds = 0;
+        bool done = c[kRdFrozen] == 0;   // no cut edge anywhere: every node keeps +inf
+        const unsigned sweep_grid = (unsigned)((size_t)((P.nb + 1) / 2) * P.nb * P.nb);
+        for (int r0 = 0; !done && r0 < cap; r0 += kRedistPoll) {
+            const int m = std::min(kRedistPoll, cap - r0);
+            for (int r = r0; r < r0 + m; r++)
+                for (int colour = 0; colour < 2; colour++)
+                    hipLaunchKernelGGL((redist_sweep_kernel<T>), dim3(sweep_grid), dim3(kBlock), 0, stream, P, colour, d_psi.p, d_rd_active.p, d_rd_any.p + r, d_rd_cnt.p);
+            HIPCHK(hipGetLastError());
+            int any[kRedistPoll];
+            HIPCHK(hipMemcpyAsync(any, d_rd_any.p + r0, (size_t)m * sizeof(int), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            for (int a = 0; a < m && !done; a++)
+                if (any[a] == 0) {
+                    rounds = r0 + a + 1;
+                    done = true;
+                }
+        }
+        if (!done) throw Error(SHM_ERR_NOCONV, fmt("redistance: blocks were still active after %d rounds (24 ceil(n/8) + 16); no psi is kept", cap));
+        hipLaunchKernelGGL((redist_final_kernel<T>), dim3(grid_for((size_t)n * n * kBlock, 16384)), dim3(kBlock), 0, stream, P, d_rd_slabs.p, d_psi.p, d_rd_cnt.p);
+        HIPCHK(hipGetLastError());
+        rd_ev[1]->record(stream);
+        HIPCHK(hipMemcpyAsync(c, d_rd_cnt.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        redist_valid = true;
+        if (out) {
+            memset(out, 0, sizeof *out);
+            out->n_frozen = (int64_t)c[kRdFrozen];
+            out->n_reached = (int64_t)c[kRdReached];
+            out->n_nonfinite = (int64_t)c[kRdNonfinite];
+            out->n_block_updates = (int64_t)c[kRdUpdates];
+            out->n_rounds = rounds;
+            memcpy(&out->max_abs, &c[kRdMaxBits], sizeof(double));
+            out->isovalue = iso;
+            out->band = band;
+            out->ms = elapsed(*rd_ev[0], *rd_ev[1]);
+        }
+    }
+    void need_redistanced(const char* who, const void* p) const {
+        if (!redist_valid || !have_phi)
+            throw Error(SHM_ERR_STATE, fmt("%s: no psi of the resident phi (shm_grid_redistance has not run since phi was last replaced)", who));
+        if (!p) throw Error(SHM_ERR_INVALID, fmt("%s: null buffer", who));
+    }
+    void get_redistanced(double* psi_out) override {
+        need_redistanced("get_redistanced", psi_out);
+        HIPCHK(hipSetDevice(cfg.device));
+        const size_t N = (size_t)n * n * n;
+        if (sizeof(T) == 8) {
+            HIPCHK(hipMemcpyAsync(psi_out, d_psi.p, N * sizeof(double), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+        } else {
+            std::vector<T> tmp(N);
+            HIPCHK(hipMemcpyAsync(tmp.data(), d_psi.p, N * sizeof(T), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            for (size_t a = 0; a < N; a++) psi_out[a] = (double)tmp[a];
+        }
+    }
+    void get_redistanced_device(void* d_out) override {
+        const char* who = "get_redistanced_device";
+        need_redistanced(who, d_out);
+        HIPCHK(hipSetDevice(cfg.device));
+        const size_t N = (size_t)n * n * n;
+        check_device_buffer(d_out, N * sizeof(T), "the psi buffer", who, "the n^3 nodes of the grid");
+        HIPCHK(hipMemcpyAsync(d_out, d_psi.p, N * sizeof(T), hipMemcpyDeviceToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+
     // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------
     static constexpr int64_t kAuditChunk = (int64_t)1 << 22;   // nodes per launch: bounds the device buffers (36 B per node) whatever count is
     DevArray<double> d_audit_src;      // [6][S]: pos x, y, z, wnormal x, y, z -- fp64, planar, in the caller's order; uploaded at the first audit of a problem
@@ -3898,6 +4017,7 @@ struct Solver final : SolverBase {
         have_conv = have_div = have_phi = false;
         iso_idx_valid = false;
         ray_bricks_valid = false;
+        redist_valid = false;
     }
 };
 

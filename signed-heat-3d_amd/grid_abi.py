@@ -21,7 +21,8 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
-               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
+               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
+               "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
 class ShmError(RuntimeError):
@@ -69,6 +70,15 @@ class ShmStep1Audit(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ShmRedistanceStats(C.Structure):
+    """shm_redistance_stats of include/shm_grid.h (shm_grid_redistance)."""
+    _fields_ = [("n_frozen", C.c_int64), ("n_reached", C.c_int64), ("n_nonfinite", C.c_int64), ("n_block_updates", C.c_int64), ("n_rounds", C.c_int32),
+                ("reserved", C.c_int32), ("max_abs", C.c_double), ("isovalue", C.c_double), ("band", C.c_double), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 def lib_path():
@@ -124,6 +134,10 @@ def load_library():
     if hasattr(lib, "shm_grid_raycast"):   # added within ABI 5: found by symbol
         lib.shm_grid_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         lib.shm_grid_raycast_device.argtypes = lib.shm_grid_raycast.argtypes
+    if hasattr(lib, "shm_grid_redistance"):   # added within ABI 5: found by symbol
+        lib.shm_grid_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(ShmRedistanceStats)]
+        lib.shm_grid_get_redistanced.argtypes = [C.c_void_p, C.c_void_p]
+        lib.shm_grid_get_redistanced_device.argtypes = [C.c_void_p, C.c_void_p]
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -420,6 +434,29 @@ class GridSolver:
         self._chk(self._lib.shm_grid_raycast_device(self._h, Q, origins.data_ptr() if Q else None, dirs.data_ptr() if Q else None, float(isovalue),
                                                     float(t_min), float(t_max), t.data_ptr() if Q else None, g.data_ptr() if grad and Q else None, C.byref(nh)))
         return (t, g, nh.value) if grad else (t, nh.value)
+
+    def redistance(self, isovalue=0.0, band=float("inf")):
+        """Redistance the resident phi on the device (shm_grid_redistance): psi with |grad psi| = 1 in the first-order upwind sense, psi < 0 exactly where
+        phi < isovalue, frozen at the nodes beside the level set and clamped to +-band (in length units; inf: the whole grid).  psi stays resident until
+        phi is replaced (get_redistanced fetches it); phi and everything derived from it are left as they were.  Returns shm_redistance_stats as a dict."""
+        st = ShmRedistanceStats()
+        self._chk(self._lib.shm_grid_redistance(self._h, float(isovalue), float(band), C.byref(st)))
+        return st.as_dict()
+
+    def get_redistanced(self, device=False):
+        """psi of the last redistance(): [n^3] float64 in get_phi's node order, or with device=True a torch tensor of the handle's dtype on its device,
+        copied device to device (import torch before this library is loaded)."""
+        N = self.n ** 3
+        if not device:
+            psi = np.empty(N, dtype=np.float64)
+            self._chk(self._lib.shm_grid_get_redistanced(self._h, psi.ctypes.data))
+            return psi
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("get_redistanced: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        psi = torch.empty(N, dtype=torch.float64 if self.precision == SHM_F64 else torch.float32, device=torch.device("cuda", self.device))
+        self._chk(self._lib.shm_grid_get_redistanced_device(self._h, psi.data_ptr() if N else None))
+        return psi
 
     def audit_step1(self, nodes=None, count=4096, seed=0, per_node=False):
         """What the Step 1 behind the resident Y cost at sampled nodes (shm_grid_audit_step1): the struct as a dict, plus "nodes", "dy" and "ratio" with

@@ -137,6 +137,16 @@ class SignedHeatGridSolver {
         return t;
     }
 
+    // Redistance the phi of the last computeDistance() on the device (shm_grid_redistance): psi with |grad psi| = 1 in the first-order upwind sense, psi < 0
+    // exactly where phi < isoval, clamped to +-band; at the grid nodes, in computeDistance's order.  phi is left as it was.
+    Vector<double> redistance(double isoval = 0., double band = std::numeric_limits<double>::infinity()) {
+        if (!handle) throw std::runtime_error("redistance: computeDistance has not been called");
+        if (shm_grid_redistance(handle, isoval, band, nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        Vector<double> psi(nx * ny * nz);
+        if (shm_grid_get_redistanced(handle, psi.data()) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        return psi;
+    }
+
   private:
     shm_solver* handle = nullptr;
     bool gridBuilt = false;

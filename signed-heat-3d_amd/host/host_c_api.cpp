@@ -213,6 +213,15 @@ int shmh_raycast(void* hv, int64_t Q, const double* origins, const double* dirs,
     });
 }
 
+// redistance through the C++ class: psi of the last compute_distance's phi at the grid nodes -> psi_out [n^3]; stats may be NULL.
+int shmh_redistance(void* hv, double isoval, double band, double* psi_out, shm_redistance_stats* stats) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        const VectorXd psi = h->solver.redistance(isoval, band, stats);
+        std::memcpy(psi_out, psi.data(), psi.size() * sizeof(double));
+    });
+}
+
 // isosurfaceIndexed through the C++ class, in two calls: vertices == NULL builds the mesh of the last compute_distance and returns the counts; with
 // buffers ([3 nv] doubles, [3 nt] int64) it builds again -- the canonical order makes the second mesh the first -- and copies it out.
 int shmh_isosurface_indexed(void* hv, double isoval, int64_t* nv, int64_t* nt, double* vertices, int64_t* triangles) {

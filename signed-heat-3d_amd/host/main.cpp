@@ -34,12 +34,16 @@ static void usage() {
                  "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n"
                  "      --rays <file>     Rays to cast against a level set of phi: raw little-endian float64, six values per ray (origin xyz, direction xyz)\n"
                  "      --rays-out <file> Raw float64, four values per ray: t of the first hit in units of the direction (NaN: none), then the gradient there\n"
-                 "      --rays-iso <v>    The level the rays are cast against (default 0; independent of --iso)\n";
+                 "      --rays-iso <v>    The level the rays are cast against (default 0; independent of --iso)\n"
+                 "      --redistance      Redistance phi on the device to a signed distance to its level set --iso (|grad psi| = 1, first-order upwind)\n"
+                 "      --band <B>        Width of the band the redistancing fills, a length; nodes beyond it hold +-B (default: the whole grid)\n"
+                 "      --out-psi <file>  Raw float64 psi at the grid nodes, in the order of --out\n";
 }
 
 int main(int argc, char** argv) {
-    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut;
-    double isoval = 0., raysIso = 0.;
+    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut;
+    double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
+    bool redistance = false;
     long long auditCount = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
@@ -74,6 +78,9 @@ int main(int argc, char** argv) {
         else if (s == "--rays") raysPath = need("--rays");
         else if (s == "--rays-out") raysOut = need("--rays-out");
         else if (s == "--rays-iso") raysIso = atof(need("--rays-iso"));
+        else if (s == "--redistance") redistance = true;
+        else if (s == "--band") band = atof(need("--band"));
+        else if (s == "--out-psi") psiOut = need("--out-psi");
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
         else path = s;
     }
@@ -83,6 +90,10 @@ int main(int argc, char** argv) {
     }
     if (raysPath.empty() != raysOut.empty()) {
         std::cerr << "--rays and --rays-out go together." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (redistance != !psiOut.empty()) {
+        std::cerr << "--redistance and --out-psi go together." << std::endl;
         return EXIT_FAILURE;
     }
     if (backend.exactStep1 && backend.referenceStep1) {
@@ -182,6 +193,14 @@ int main(int argc, char** argv) {
             std::ofstream o(raysOut, std::ios::binary);
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
             std::cerr << ro.size() << " rays cast against phi = " << raysIso << ": " << hits << " hits, t and gradient written to " << raysOut << std::endl;
+        }
+        if (redistance) {
+            shm_redistance_stats rs{};
+            const VectorXd psi = solver.redistance(isoval, band, &rs);
+            std::ofstream o(psiOut, std::ios::binary);
+            o.write((const char*)psi.data(), (std::streamsize)(psi.size() * sizeof(double)));
+            std::cerr << "phi redistanced to its level set " << isoval << ": " << rs.n_frozen << " frozen nodes, " << rs.n_reached << " reached, max |psi| " << rs.max_abs
+                      << ", " << rs.n_rounds << " rounds, " << rs.n_block_updates << " block updates, " << rs.ms << " ms; psi written to " << psiOut << std::endl;
         }
     } catch (const std::exception& e) {
         std::cerr << "error: " << e.what() << std::endl;

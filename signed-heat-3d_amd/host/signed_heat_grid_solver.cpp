@@ -148,6 +148,14 @@ std::vector<double> SignedHeatGridSolver::castRays(const std::vector<Vector3>& o
     return t;
 }
 
+VectorXd SignedHeatGridSolver::redistance(double isoval, double band, shm_redistance_stats* stats) {
+    if (!handle) throw std::runtime_error("redistance: computeDistance has not been called");
+    if (shm_grid_redistance(handle, isoval, band, stats) != SHM_OK) throw std::runtime_error(std::string("shm_grid_redistance: ") + shm_grid_last_error(handle));
+    VectorXd psi(nx * ny * nz);
+    if (shm_grid_get_redistanced(handle, psi.data()) != SHM_OK) throw std::runtime_error(std::string("shm_grid_get_redistanced: ") + shm_grid_last_error(handle));
+    return psi;
+}
+
 VectorXd SignedHeatGridSolver::computeDistance(VertexPositionGeometry& geometry, const SignedHeat3DOptions& options) {
     if (options.rebuild || !gridBuilt) {
         const Vector3 c = centroid(geometry);

@@ -56,6 +56,12 @@ class SignedHeatGridSolver {
     std::vector<double> castRays(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double isoval = 0., double tMin = 0.,
                                  double tMax = std::numeric_limits<double>::infinity(), std::vector<Vector3>* gradients = nullptr);
 
+    // Redistance the phi of the LAST computeDistance() call on the device (shm_grid_redistance; scheme, limit and rules in include/shm_grid.h): psi with
+    // |grad psi| = 1 in the first-order upwind sense, psi < 0 exactly where phi < isoval, clamped to +-band (a length; +inf: the whole grid).  Returns psi at
+    // the grid nodes, in computeDistance's node order; stats (optional) receives the call's counts.  What the contour slider's offset surfaces
+    // (src/main.cpp:160-166) assume phi to be.  phi itself is left as it was: extract surfaces from phi, read distances from psi.
+    VectorXd redistance(double isoval = 0., double band = std::numeric_limits<double>::infinity(), shm_redistance_stats* stats = nullptr);
+
     // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
     // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).
     shm_step1_audit auditStep1(size_t count = 4096, uint64_t seed = 0);

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .grid_abi import ShmStats, ShmStep1Audit, load_library
+from .grid_abi import ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -42,6 +42,7 @@ def load_host_library():
     lib.shmh_compute_distance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(ShmStats)]
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
     lib.shmh_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.argtypes = [C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.restype = None
@@ -140,6 +141,14 @@ class HostSolver:
         self._chk(self._lib.shmh_raycast(self._h, o.shape[0], o.ctypes.data, d.ctypes.data, float(isovalue), float(t_min), float(t_max), t.ctypes.data,
                                          g.ctypes.data if grad else None, C.byref(nh)))
         return (t, g, nh.value) if grad else (t, nh.value)
+
+    def redistance(self, isovalue=0.0, band=float("inf")):
+        """redistance of the C++ mirror: the phi of the last compute_distance redistanced on the device to its level set (shm_grid_redistance).
+        Returns (psi [n^3] float64, stats dict)."""
+        psi = np.empty(self.grid_info()["n"] ** 3, dtype=np.float64)
+        st = ShmRedistanceStats()
+        self._chk(self._lib.shmh_redistance(self._h, float(isovalue), float(band), psi.ctypes.data, C.byref(st)))
+        return psi, st.as_dict()
 
     def isosurface_indexed(self, isovalue=0.0):
         """isosurfaceIndexed of the C++ mirror: the marching-cubes surface of the last compute_distance, welded and numbered on the device in the
