@@ -46,7 +46,17 @@
 // (the scheduler's 24 s_nop are gone), the in-launch verdict of the far-rule sample as one word written by compare-and-swap.  176 registers.
 // Round 7 (profiles/NOTES_r07.md): the near body's Newton step folded into the exponent scale -- 11 fp64 instructions per pair behind v_rsq_f64 instead of 12, the near loop 100
 // instructions per source instead of 104 (see yukawa_near); the near list's weights are staged times 1 / |c|.  13.81 VALU instructions per nominal pair (14.20), 176 registers.
+// Round 8 (profiles/NOTES_r08.md): the far list's REMAINDER IS CARRIED from cluster to cluster.  The far loop takes four sources per trip; rounds 3-7 padded every (block, cluster)
+// far list to a multiple of four with zero-weight entries at 1e18, each of which costs what a real source costs.  Now the up to three entries a cluster leaves over stay at the
+// head of the wave's lists, the next cluster's lanes stage behind them (carry + rank), and after the loop the leftovers move to the head (at most three lanes read, then write).
+// The list is padded and run to the end ("drained") at three points only: before a flush of the packed-fp32 sums, behind the last cluster of pass 0 (before the a-posteriori
+// test) and behind the last cluster of the fp32 solve's pass; pass 1 has no far list.  Every accumulator takes the same sources in the same order, the padding adds exact
+// zeros and the flushes come after the same sources: Y is bit-identical to round 7's (tools/step1_identity.py, profiles/r08_carry_identity.txt).  The bookkeeping is one
+// __host__ __device__ function (far_carry_step, shm_far_carry.h) that tests/native/test_far_carry.cpp walks on the host.  The near list runs an exact count and lost its
+// padding entries.  LDS per workgroup: far lists 68 entries per wave as before (64 + carry 3 + at most 1 of padding, where 64 + 4 of padding stood), near list 64 entries
+// (68): 51 904 bytes at NPT = 4 (52 672), 49 728 at NPT = 2.  174 registers.
 #pragma once
+#include "shm_far_carry.h"
 #include "shm_kernels.hip.h"
 
 namespace shm {
@@ -266,14 +276,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
     static_assert(NPT % 2 == 0, "the far tier handles a lane's nodes in packed pairs");
     constexpr int kWaves = kBlock / kWave;
     constexpr int kFarUnroll = SHM_TIER_FAR_UNROLL;
-    constexpr int kPad = kFarUnroll;   // staged entries behind the last real one: zero weight, far away -- they pad the
-    __shared__ double stage64[kWaves][(kTierCluster + kPad) * 6];              // compacted lists to whole groups of sources in flight
+    static_assert(kFarUnroll == kFarGroup, "the carry's bookkeeping (shm_far_carry.h) counts in groups of the far loop's unroll");
+    // Far list entries per wave: a cluster's 64 behind a carry of at most kFarGroup - 1, padded to a whole group only when the list is drained (far_carry_step): at
+    // most 67 + 1 = 68, what the per-cluster padding of rounds 3-7 took (64 + 4).  The near list runs an exact count and has no padding: 64 entries.
+    constexpr int kFarList = kTierCluster + kFarGroup;
+    static_assert((kTierCluster + kFarGroup - 1 + kFarGroup - 1) / kFarGroup * kFarGroup <= kFarList, "carry + cluster + padding fit the far lists");
+    __shared__ double stage64[kWaves][kTierCluster * 6];
     // far list (round 5: three arrays instead of one 32-byte record): A = x', y', wx, wy | B = (z_e - z')^2 for the block's NPT planes -- the planes are the same for
     // every lane, so the classifying lane squares them once per source and the far loop gets d^2 of two nodes by ONE packed add (it used to take a packed add and a
     // packed fma per two nodes, and a subtraction per source) | C = wz, |w|_1.  Weights sit in aligned pairs: either half is broadcast by op_sel (pk_fma_lo / _hi)
-    __shared__ __attribute__((aligned(16))) float farA[kWaves][(kTierCluster + kPad) * 4];
-    __shared__ __attribute__((aligned(16))) float farB[kWaves][(kTierCluster + kPad) * NPT];
-    __shared__ __attribute__((aligned(16))) float farC[kWaves][(kTierCluster + kPad) * 2];
+    __shared__ __attribute__((aligned(16))) float farA[kWaves][kFarList * 4];
+    __shared__ __attribute__((aligned(16))) float farB[kWaves][kFarList * NPT];
+    __shared__ __attribute__((aligned(16))) float farC[kWaves][kFarList * 2];
     // the next cluster's sources travel global -> LDS directly (global_load_lds_dwordx4: three 16-byte pieces of every lane's 48-byte record, each piece
     // landing at wave base + lane * 16), not through 12 registers per lane held across the two loops: those registers are what the per-node L1 sums of the
     // a-posteriori test live in (round 4; the kernel must stay within 184 VGPRs for the set-up kernels to run beside it)
@@ -487,6 +501,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         const float span_c = uniform_f32(2.f * rt_w * lam_l2 - coff - 960.f);   // pass 1: a dropped source is evaluated only where its exponent stays inside the block's span
         // pass 0: near sources in fp64, far ones in packed fp32.  pass 1 (only when the a-posteriori test failed): every source in fp64, from cleared accumulators.
         int far_pending = 0;
+        int carry = 0;   // far list entries left at the head of the lists by the clusters before (wave-uniform, <= kFarGroup - 1; see far_carry_step)
 #pragma unroll 1
         for (int pass = 0; pass < 2; pass++) {
         // the lane's source of cluster c: fetched into the wave's raw LDS region one cluster ahead (issued once cluster c - 1 has been read out of it, in flight
@@ -682,7 +697,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
 #pragma unroll
                     for (int a = 0; a < 6; a++) tile[rnk * 6 + a] = a < 3 ? q[a] : q[a] * P.cexp_inv;   // (the near body returns |c| e^{-lambda r} / r: see yukawa_near)
                 } else if (to32) {
-                    const int rnk = mask_rank(farmask);
+                    const int rnk = carry + mask_rank(farmask);   // behind what the clusters before left over
                     // positions in units of 1 / (lambda log2 e): the far loop then gets lambda r log2 e = d2' rsq(d2') without a multiplication of its own
                     *reinterpret_cast<float4*>(&tA[rnk * 4]) = float4{q32[0] * lam_l2, q32[1] * lam_l2, q32[3], q32[4]};
                     const float dz0 = qz0 - q32[2] * lam_l2;
@@ -698,15 +713,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                 }
             }
             const int nnear = __builtin_popcountll(nearmask), nfar = __builtin_popcountll(farmask);
-            if (lane < kPad) {
-#pragma unroll
-                for (int a = 0; a < 6; a++) tile[(nnear + lane) * 6 + a] = a < 3 ? P.pad_pos[a] : 0.0;   // the padding entry: >= one grid side from every node, zero weight
+            // The far loop takes kFarGroup sources per trip.  What this cluster leaves over stays in the lists for the next one instead of being padded to a whole group
+            // (round 8; the bookkeeping is far_carry_step, shm_far_carry.h): padding -- zero weight, far away -- is written only where the list is drained, before a flush
+            // of the packed-fp32 sums and behind the last cluster of the pass.
+            const FarCarryStep fs = far_carry_step(carry, nfar, far_pending, CHECK ? P.tier_flush : 0, c_next >= P.n_clusters);
+            if (lane < fs.pad) {
+                const int at = carry + nfar + lane;
                 // (the far list holds SCALED positions; an unscaled padding point would land inside the grid, where coff - r' > 0 can overflow exp2f
                 // and 0 * inf = NaN reaches the sums.  1e18 in the scaled x and y, 1e36 as the squared z offsets: d2 ~ 3e36 is finite, r' = 1.7e18 > coff always, 2^(coff - r') = 0)
-                *reinterpret_cast<float4*>(&tA[(nfar + lane) * 4]) = float4{1.0e18f, 1.0e18f, 0.f, 0.f};
+                *reinterpret_cast<float4*>(&tA[at * 4]) = float4{1.0e18f, 1.0e18f, 0.f, 0.f};
 #pragma unroll
-                for (int e = 0; e < NPT; e++) tB[(nfar + lane) * NPT + e] = 1.0e36f;
-                *reinterpret_cast<float2*>(&tC[(nfar + lane) * 2]) = float2{0.f, 0.f};
+                for (int e = 0; e < NPT; e++) tB[at * NPT + e] = 1.0e36f;
+                *reinterpret_cast<float2*>(&tC[at * 2]) = float2{0.f, 0.f};
             }
             cnt_near += (unsigned)nnear;
             cnt_far += (unsigned)nfar;
@@ -746,7 +764,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
             // (written stage by stage over the kFarUnroll x NPT / 2 packed pairs in flight: the order the scheduler starts from keeps every transcendental's consumer a full
             // stage behind it.  Round 6: with the per-source form the fp32 solve's loop came out with 24 s_nop of trans-use hazards -- 142 instructions where round 5's
             // build had 116 -- once unrelated code around it changed; this form does not depend on the scheduler finding the interleaving.)
-            for (int i0f = 0; i0f < nfar; i0f += kFarUnroll) {
+            for (int i0f = 0; i0f < fs.run; i0f += kFarUnroll) {
                 constexpr int kP = kFarUnroll * (NPT / 2);
                 float2v wxy[kFarUnroll], pcw[kFarUnroll], d2[kP], rinv[kP], g[kP];
                 float dxy2[kFarUnroll];
@@ -788,9 +806,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
             if constexpr (CHECK) {
                 // the packed-fp32 sums go to the fp64 accumulators every P.tier_flush far sources (0: never): an fp32 accumulator that has taken N terms carries ~6e-8 sqrt(N) of its
                 // partial sums, which the test's price of a far TERM does not know about
-                far_pending += nfar;
-                if (P.tier_flush > 0 && far_pending >= P.tier_flush) {
-                    far_pending = 0;
+                // (the list was drained first: the sums hold every far source up to this cluster, as they did when every cluster was padded on its own)
+                far_pending = fs.pending;
+                if (fs.flush) {
                     const double e0f = far_scale();
 #pragma unroll
                     for (int e = 0; e < NPT; e++) {
@@ -802,6 +820,25 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                     for (int e = 0; e < NPT / 2; e++) fx[e] = fy[e] = fz[e] = float2v{0.f, 0.f};
                 }
             }
+            // the leftover entries move to the head of the lists: at most kFarGroup - 1 lanes read, then write (a wave's LDS accesses execute in order; fs.run >=
+            // kFarGroup > fs.carry: the two ranges do not overlap)
+            if (fs.carry > 0 && fs.run > 0) {
+                if (lane < fs.carry) {
+                    const int from = fs.run + lane;
+                    const float4 ca = *reinterpret_cast<const float4*>(&tA[from * 4]);
+                    const float2 cc2 = *reinterpret_cast<const float2*>(&tC[from * 2]);
+                    if constexpr (NPT == 4) {
+                        const float4 cb = *reinterpret_cast<const float4*>(&tB[from * 4]);
+                        *reinterpret_cast<float4*>(&tB[lane * 4]) = cb;
+                    } else {
+                        const float2 cb = *reinterpret_cast<const float2*>(&tB[from * 2]);
+                        *reinterpret_cast<float2*>(&tB[lane * 2]) = cb;
+                    }
+                    *reinterpret_cast<float4*>(&tA[lane * 4]) = ca;
+                    *reinterpret_cast<float2*>(&tC[lane * 2]) = cc2;
+                }
+            }
+            carry = fs.carry;
             c = c_next;
             cdrop_cur = cdrop_next;
         }

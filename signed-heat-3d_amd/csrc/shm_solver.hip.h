@@ -749,7 +749,6 @@ struct Solver final : SolverBase {
             P.k0 = sl.k0;
             for (int a = 0; a < 3; a++) P.bbox_min[a] = bbox_min[a] - conv_ctr[a];   // Step 1 works in grid-centred coordinates (see set_problem)
             P.cell = cell;
-            for (int a = 0; a < 3; a++) P.pad_pos[a] = P.bbox_min[a] - (double)n * cell;
             P.lambda = lambda;
             P.cexp = -lambda * 2954.639443740597;  // 2048 / ln 2
             P.cexp_inv = 1.0 / std::fabs(P.cexp);
