@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/shm_grid.h"
+#include "shm_constraints.h"   // Row
 
 namespace shm {
 
@@ -245,14 +246,6 @@ static float elapsed(Event& a, Event& b) {
     HIPCHK(hipEventElapsedTime(&ms, a.e, b.e));
     return ms;
 }
-
-// One constraint row (trilinearCoefficients, signed_heat_grid_solver.cpp:433-464).
-struct Row {
-    int64_t nodes[8];
-    double coeffs[8];
-    int cell[3];   // (i, j, k) of the cell and the trilinear parameters of the sample point in it: the separable form of coeffs
-    double t[3];   // that the explicit Schur complement (shm_schur.hip.h) is assembled from
-};
 
 
 // ---- Step-1 work per z-plane, estimated on the host with the kernels' own culling / tier rules (per source, on a sample of node blocks) ----------------

@@ -11,11 +11,11 @@
 
 #include <type_traits>
 
+#include "shm_constraints.h"   // kWave, kGJ, ShiftItem
 #include "shm_mc_table.h"
 
 namespace shm {
 
-constexpr int kWave = 64;       // CDNA wavefront
 constexpr int kBlock = 256;     // 4 waves = one per SIMD
 constexpr int kMaxPartials = 8192;
 
@@ -1016,12 +1016,6 @@ __global__ __launch_bounds__(kBlock) void scatter_nodes_kernel(int nnodes, const
 // z-plane of its cell the bilinear value (x lerp then y lerp) times area*(1-tz | tz); the owner of the
 // plane evaluates it, so slabs sum to the reference's nested lerp.  phi = -x here.
 // =================================================================================================
-struct ShiftItem {
-    uint32_t node;  // local index (ghost layout) of the (i,j) corner in the plane
-    float pad;
-    double tx, ty, weight;  // weight = area * (1-tz) or area * tz
-};
-
 template <typename T>
 __global__ __launch_bounds__(kBlock) void shift_partial_kernel(int nitems, const ShiftItem* __restrict__ items, int n, const T* __restrict__ x,
                                                                double* __restrict__ partials) {
@@ -1290,7 +1284,6 @@ __global__ __launch_bounds__(kBlock) void convert_kernel(size_t count, const TS*
 // Large matrices (>= 64 blocks) run two-level: outer blocks of four pivot blocks whose rank-64 updates touch only the cross of tiles
 // the next inner steps read, followed by ONE rank-256 update of everything else (see GjTiles).
 // =================================================================================================
-constexpr int kGJ = 64;
 
 // Batched form of the blocked Gauss-Jordan kernels below (round 4: the boxes of the two-level inverse, shm_twolevel.hip.h -- one workgroup per box walking its
 // matrix in global memory took 45 ms for a 280-row box; the blocked kernels do all boxes at once in 3 launches per 64 rows of the LARGEST box).  blockIdx.y = box a:

@@ -6,6 +6,8 @@
 //   * Eigen assembly of L, A, the KKT matrix and its sparse LU (solveSquare)  :80-108 / :186-214
 //     -> matrix-free projected CG on null(A) with a dense (A A^T)^-1
 //   * the shift                                   :110-111 / :216-217
+// What the host assembles for the constraint set-up (rows, shift items, G, B, slab lists, the two-level partition: shm::build_rows() ... shm::active_tiles())
+// is plain C++ in shm_constraints.h; Solver::build_constraints() below is the schedule around it.
 // One process drives one GPU; the grid is cut into z-slabs (rank-major).  A process may own several
 // slabs (loop-back transport, used to exercise the slab logic on one GPU); across processes the halo
 // planes and the reduction vectors travel over RCCL (xGMI) on the solver's own stream.
@@ -1002,79 +1004,21 @@ struct Solver final : SolverBase {
     }
 
     // ------------------------------------------------------------------------------------------
-    // Constraint rows (:80-98 / :186-204), sequential over the sources like the reference.
+    // Constraint rows (:80-98 / :186-204) and everything else the host assembles from the sources and the rows: shm_constraints.h (plain C++, run without a
+    // GPU by tests/native/test_constraints.cpp).  Here: the schedule, the uploads and the launches.
     void build_rows() {
-        rows.clear();
-        std::unordered_set<uint64_t> used;
-        used.reserve((size_t)S * 2);
-        const double h = cell;
-        for (int64_t s = 0; s < S; s++) {
-            const double* b = &h_pos[3 * s];
-            const size_t i = (size_t)std::floor((b[0] - bbox_min[0]) / h);
-            const size_t j = (size_t)std::floor((b[1] - bbox_min[1]) / h);
-            const size_t k = (size_t)std::floor((b[2] - bbox_min[2]) / h);
-            const uint64_t cid = i + j * (uint64_t)n + k * (uint64_t)n * n;
-            if (!used.insert(cid).second) continue;
-            Row r;
-            const double tx = (b[0] - (i * h + bbox_min[0])) / h;
-            const double ty = (b[1] - (j * h + bbox_min[1])) / h;
-            const double tz = (b[2] - (k * h + bbox_min[2])) / h;
-            auto ix = [&](size_t a, size_t bb, size_t c) { return (int64_t)(a + bb * (size_t)n + c * (size_t)n * n); };
-            r.nodes[0] = ix(i, j, k);
-            r.nodes[1] = ix(i + 1, j, k);
-            r.nodes[2] = ix(i, j + 1, k);
-            r.nodes[3] = ix(i, j, k + 1);
-            r.nodes[4] = ix(i + 1, j + 1, k);
-            r.nodes[5] = ix(i + 1, j, k + 1);
-            r.nodes[6] = ix(i, j + 1, k + 1);
-            r.nodes[7] = ix(i + 1, j + 1, k + 1);
-            r.coeffs[0] = (1. - tx) * (1. - ty) * (1. - tz);
-            r.coeffs[1] = tx * (1. - ty) * (1. - tz);
-            r.coeffs[2] = (1. - tx) * ty * (1. - tz);
-            r.coeffs[3] = (1. - tx) * (1. - ty) * tz;
-            r.coeffs[4] = tx * ty * (1. - tz);
-            r.coeffs[5] = tx * (1. - ty) * tz;
-            r.coeffs[6] = (1. - tx) * ty * tz;
-            r.coeffs[7] = tx * ty * tz;
-            r.cell[0] = (int)i; r.cell[1] = (int)j; r.cell[2] = (int)k;
-            r.t[0] = tx; r.t[1] = ty; r.t[2] = tz;
-            rows.push_back(r);
-        }
+        shm::build_rows(S, h_pos.data(), bbox_min, cell, n, rows);
         m = (int)rows.size();
         mp = ((m + kGJ - 1) / kGJ) * kGJ;
     }
 
-    // shift items: every source contributes one bilinear evaluation per z-plane of its cell (:405-431); the owner of the
-    // plane evaluates it, so the slabs sum to the reference's nested lerp.
     void build_shift_items(hipStream_t stream) {
-        const size_t plane = (size_t)n * n;
         shift_host.resize(slabs.size());  // host copies outlive the asynchronous uploads
         for (size_t si = 0; si < slabs.size(); si++) {
             Slab<T>& sl = slabs[si];
-            std::vector<ShiftItem>& items = shift_host[si];
-            items.clear();
-            for (int64_t s = 0; s < S; s++) {
-                const double* b = &h_pos[3 * s];
-                const int i = (int)std::floor((b[0] - bbox_min[0]) / cell);
-                const int j = (int)std::floor((b[1] - bbox_min[1]) / cell);
-                const int k = (int)std::floor((b[2] - bbox_min[2]) / cell);
-                const double tx = (b[0] - (i * cell + bbox_min[0])) / cell;
-                const double ty = (b[1] - (j * cell + bbox_min[1])) / cell;
-                const double tz = (b[2] - (k * cell + bbox_min[2])) / cell;
-                for (int dz = 0; dz < 2; dz++) {
-                    const int kz = k + dz;
-                    if (kz < sl.k0 || kz >= sl.k1) continue;
-                    ShiftItem it;
-                    it.node = (uint32_t)((size_t)i + (size_t)j * n + (size_t)(kz - sl.k0 + 1) * plane);
-                    it.pad = 0.f;
-                    it.tx = tx;
-                    it.ty = ty;
-                    it.weight = h_area[s] * (dz == 0 ? (1. - tz) : tz);
-                    items.push_back(it);
-                }
-            }
-            sl.n_shift = (int)items.size();
-            sl.shift_items.upload(items, stream);
+            shift_items_for_slab(S, h_pos.data(), h_area.data(), bbox_min, cell, n, sl.k0, sl.k1, shift_host[si]);
+            sl.n_shift = (int)shift_host[si].size();
+            sl.shift_items.upload(shift_host[si], stream);
         }
     }
     // device tables of the per-slab reduction buffers for the loop-back sum ([0,ns): red, [ns,2ns): pq)
@@ -1149,8 +1093,8 @@ struct Solver final : SolverBase {
         return estimate_step1_ms_tiered() * share;
     }
 
-    // Per-slab CSR pieces, shift items, G = A A^T (sparse triplets -> dense on device -> inverted) and B = A K A^T.
-    // Order: everything the inversion needs first (rows, G), then the Gauss-Jordan kernels are enqueued, and the rest of the host
+    // Per-slab CSR pieces, shift items, G = A A^T (sparse triplets -> dense on device -> inverted) and B = A K A^T: the host assembles (shm_constraints.h), this
+    // function keeps the order.  Everything the inversion needs first (rows, G), then the Gauss-Jordan kernels are enqueued, and the rest of the host
     // work (per-slab lists, B, active-tile lists) runs while the GPU inverts; uploads come last (a pageable copy waits for the stream).
     // `in`, `p`: the inputs and the plan of this set-up (plan_solve's for a solve, the defaults -- no dual solve requested -- for the test entry points)
     void build_constraints(const PlanIn& in, const Plan& p) {
@@ -1167,113 +1111,28 @@ struct Solver final : SolverBase {
         }
         build_rows();
         lap("rows");
-        const size_t plane = (size_t)n * n;
         plan_rows(plan_in, m, [&]() { return step1_hidden_ms(plan_in.conv_est_total_ms); }, plan);
         log("[shm] plan: %s, m=%d, form %s%s, precond %d, green table %s, G^-1 %s, prio %d; direct weighed: set-up alone ~%.1f ms, Step 1 ~%.1f ms",
             plan_path_name(plan.path), m, plan.dual_form == SHM_DUAL_DIRECT ? "direct" : plan.dual_form == SHM_DUAL_EXPLICIT_S_CG ? "explicit-S CG" : "through grid",
             plan.explicit_S ? " (S assembled)" : "", (int)plan.precond, plan.green_early ? "early" : "late", plan.two_level ? "two-level" : "dense", plan.setup_prio,
             plan.est_setup_ms, plan.est_step1_ms);
-        // Direct dual solve: no G, no B, and none of the host tables below that only they and the sparse sweeps of the iterative dual solver need (entries sorted by
-        // node, node -> rows hash, active tiles)
+        // Direct dual solve: no G, no B, and none of the host tables that only they and the sparse sweeps of the iterative dual solver need (entries sorted by
+        // node, node -> rows hash, active tiles): the index is built over no rows
         const bool dual_direct = plan.dual_form == SHM_DUAL_DIRECT;
-        const bool need_node_tables = !dual_direct;
-        // ---- G = A A^T and B = A K A^T from the (node, row, coef) entries sorted by node: rows meet exactly at shared nodes.
-        //      Sorted vectors instead of hash maps: the host part of the set-up is on the critical path of small / multi-GPU runs.
-        struct Ent { int64_t node; int row; double coef; };
-        std::vector<Ent> ents(need_node_tables ? (size_t)8 * m : 0);
-        for (int r = 0; r < m && need_node_tables; r++)
-            for (int e = 0; e < 8; e++) ents[(size_t)8 * r + e] = {rows[r].nodes[e], r, rows[r].coeffs[e]};
-        std::sort(ents.begin(), ents.end(), [](const Ent& x, const Ent& y) { return x.node != y.node ? x.node < y.node : x.row < y.row; });
-        std::vector<int64_t> unode;       // distinct touched nodes, ascending
-        std::vector<int> ustart;          // their entry ranges in `ents`
-        for (size_t e = 0; e < ents.size(); e++)
-            if (e == 0 || ents[e].node != ents[e - 1].node) {
-                unode.push_back(ents[e].node);
-                ustart.push_back((int)e);
-            }
-        ustart.push_back((int)ents.size());
+        std::vector<Row> no_rows;
+        const NodeIndex index(dual_direct ? no_rows : rows);
         lap("sorted entries");
-        // row by row with a dense scatter-accumulate scratch (value + owner stamp per column): no sorting, no hashing; the
-        // column order inside a CSR row is irrelevant for the mat-vec
-        // node -> group through a small open-addressing table (binary searching 56 stencil nodes per row dominated the set-up)
-        size_t hbits = 4;
-        while (((size_t)1 << hbits) < 4 * unode.size() + 16) hbits++;
-        const size_t hmask = ((size_t)1 << hbits) - 1;
-        std::vector<int64_t> hkey((size_t)1 << hbits, -1);
-        std::vector<int> hval((size_t)1 << hbits, -1);
-        auto hslot = [&](int64_t node) { return (size_t)(((uint64_t)node * 0x9E3779B97F4A7C15ULL) >> (64 - hbits)) & hmask; };
-        for (size_t u = 0; u < unode.size(); u++) {
-            size_t h = hslot(unode[u]);
-            while (hkey[h] >= 0) h = (h + 1) & hmask;
-            hkey[h] = unode[u];
-            hval[h] = (int)u;
-        }
-        auto group_of = [&](int64_t node) -> int {
-            size_t h = hslot(node);
-            while (hkey[h] >= 0) {
-                if (hkey[h] == node) return hval[h];
-                h = (h + 1) & hmask;
-            }
-            return -1;
-        };
-        std::vector<double> accv((size_t)m, 0.);
-        std::vector<int> stamp((size_t)m, -1), cols;
-        auto add = [&](int tag, int col, double v) {
-            if (stamp[(size_t)col] != tag) {
-                stamp[(size_t)col] = tag;
-                accv[(size_t)col] = v;
-                cols.push_back(col);
-            } else {
-                accv[(size_t)col] += v;
-            }
-        };
-        // G = A A^T in CSR on the host (rows sharing a node with row r), then either scattered into the dense m x m matrix that the blocked
-        // Gauss-Jordan inverts in place, or -- large m -- split into boxes and a separator (two-level inverse, shm_twolevel.hip.h)
-        std::vector<int> gptr((size_t)m + 1, 0), gcol;
-        std::vector<double> gval;
-        gcol.reserve((size_t)m * 32);
-        gval.reserve((size_t)m * 32);
-        std::vector<int> ugs((size_t)8 * m);
-        for (int r = 0; r < m && !dual_direct; r++) {
-            cols.clear();
-            for (int e = 0; e < 8; e++) {
-                const int ug = group_of(rows[r].nodes[e]);
-                ugs[(size_t)8 * r + e] = ug;
-                for (int y = ustart[ug]; y < ustart[ug + 1]; y++) add(2 * r, ents[y].row, rows[r].coeffs[e] * ents[y].coef);
-            }
-            for (int c : cols) {
-                gcol.push_back(c);
-                gval.push_back(accv[(size_t)c]);
-            }
-            gptr[(size_t)r + 1] = (int)gcol.size();
-        }
+        // G in CSR, then either scattered into the dense m x m matrix that the blocked Gauss-Jordan inverts in place, or -- large m -- split into boxes and a
+        // separator (two-level inverse, shm_twolevel.hip.h)
+        const Csr G = dual_direct ? Csr((size_t)m) : assemble_G(rows, index);   // (direct: m empty rows, read by nobody)
         lap("G rows");
         DevArray<uint64_t> d_tidx;  // alive until the final synchronisation below
         DevArray<double> d_tval;
-        tl.on = plan.two_level && build_two_level(gptr, gcol, gval, d_tidx, d_tval);
-        std::vector<uint64_t> tidx;  // alive (like d_tidx / d_tval) until the final synchronisation below
-        std::vector<double> tval;
+        Triplets dense;             // alive as long
+        tl.on = plan.two_level && build_two_level(G, d_tidx, d_tval);
         if (!tl.on && !dual_direct) {
-            tidx.reserve(gcol.size() + (size_t)(mp - m));
-            tval.reserve(gcol.size() + (size_t)(mp - m));
-            for (int r = 0; r < m; r++)
-                for (int e = gptr[(size_t)r]; e < gptr[(size_t)r + 1]; e++) {
-                    tidx.push_back((uint64_t)r * (uint64_t)mp + (uint64_t)gcol[(size_t)e]);
-                    tval.push_back(gval[(size_t)e]);
-                }
-            for (int a = m; a < mp; a++) {  // identity tail keeps the padded matrix SPD
-                tidx.push_back((uint64_t)a * mp + a);
-                tval.push_back(1.0);
-            }
-            ginv_rows = m;
-            ginv_ld = mp;
-            Ginv.alloc((size_t)mp * mp);
-            HIPCHK(hipMemsetAsync(Ginv.p, 0, (size_t)mp * mp * sizeof(double), stream));
-            d_tidx.upload(tidx, stream);
-            d_tval.upload(tval, stream);
-            hipLaunchKernelGGL(scatter_triplets_kernel, dim3(grid_for(tidx.size(), 4096)), dim3(kBlock), 0, stream, (size_t)tidx.size(), d_tidx.p,
-                               d_tval.p, Ginv.p);
-            HIPCHK(hipGetLastError());
+            dense = dense_triplets(G, m, mp);
+            upload_and_scatter_G(dense, m, mp, d_tidx, d_tval);
         }
         prepare_schur();
         if (dual_direct) {
@@ -1287,75 +1146,12 @@ struct Solver final : SolverBase {
         }
 
         // ---- host work that the inversion does not need, while the GPU inverts
-        std::vector<int> bptr(m + 1, 0), bcol;
-        std::vector<double> bval;
-        bcol.reserve((size_t)m * 128);
-        bval.reserve((size_t)m * 128);
-        {
-            const double ih2 = 1. / (cell * cell);
-            const int64_t nn = n, pl = (int64_t)n * n;
-            for (int r = 0; r < m && !dual_direct; r++) {  // B = A K A^T: K a_r lives on the 8 corners and their in-grid neighbours
-                cols.clear();
-                for (int e = 0; e < 8; e++) {
-                    const int64_t c = rows[r].nodes[e];
-                    const double cf = rows[r].coeffs[e];
-                    const int64_t k = c / pl, j = (c - k * pl) / nn, i = c - k * pl - j * nn;
-                    const int64_t nb[6] = {i > 0 ? c - 1 : -1, i < nn - 1 ? c + 1 : -1, j > 0 ? c - nn : -1, j < nn - 1 ? c + nn : -1,
-                                           k > 0 ? c - pl : -1, k < nn - 1 ? c + pl : -1};
-                    int deg = 0;
-                    for (int q = 0; q < 6; q++) {
-                        if (nb[q] < 0) continue;
-                        deg++;
-                        const int ub = group_of(nb[q]);
-                        if (ub < 0) continue;  // K a_r reaches a node no constraint row touches
-                        for (int y = ustart[ub]; y < ustart[ub + 1]; y++) add(2 * r + 1, ents[y].row, -cf * ih2 * ents[y].coef);
-                    }
-                    const int ug = ugs[(size_t)8 * r + e];
-                    for (int y = ustart[ug]; y < ustart[ug + 1]; y++) add(2 * r + 1, ents[y].row, deg * cf * ih2 * ents[y].coef);
-                }
-                for (int c : cols) {
-                    bcol.push_back(c);
-                    bval.push_back(accv[(size_t)c]);
-                }
-                bptr[r + 1] = (int)bcol.size();
-            }
-        }
+        const Csr B = dual_direct ? Csr((size_t)m) : assemble_B(rows, index, n, cell);   // (direct: m empty rows, uploaded as the empty B; have_B stays false)
         lap("B rows");
-        struct SlabLists {
-            std::vector<int> row_ptr, node_ptr, ent_row;
-            std::vector<uint32_t> ent_node, node_id;
-            std::vector<double> ent_coef, nent_coef;
-        };
         std::vector<SlabLists> lists(slabs.size());
         for (size_t si = 0; si < slabs.size(); si++) {
-            Slab<T>& sl = slabs[si];
-            SlabLists& L = lists[si];
-            const int64_t lo = (int64_t)sl.k0 * (int64_t)plane, hi = (int64_t)sl.k1 * (int64_t)plane;
-            const int64_t shiftoff = (int64_t)plane - lo;  // global node -> local ghost-layout index
-            L.row_ptr.assign(m + 1, 0);
-            std::vector<std::pair<uint32_t, std::pair<int, double>>> by_node;
-            for (int r = 0; r < m; r++) {
-                for (int e = 0; e < 8; e++) {
-                    const int64_t g = rows[r].nodes[e];
-                    if (g < lo || g >= hi) continue;
-                    const uint32_t l = (uint32_t)(g + shiftoff);
-                    L.ent_node.push_back(l);
-                    L.ent_coef.push_back(rows[r].coeffs[e]);
-                    by_node.push_back({l, {r, rows[r].coeffs[e]}});
-                }
-                L.row_ptr[r + 1] = (int)L.ent_node.size();
-            }
-            std::stable_sort(by_node.begin(), by_node.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-            for (size_t a = 0; a < by_node.size(); a++) {
-                if (a == 0 || by_node[a].first != by_node[a - 1].first) {
-                    L.node_id.push_back(by_node[a].first);
-                    L.node_ptr.push_back((int)a);
-                }
-                L.ent_row.push_back(by_node[a].second.first);
-                L.nent_coef.push_back(by_node[a].second.second);
-            }
-            L.node_ptr.push_back((int)by_node.size());
-            sl.n_touched = (int)L.node_id.size();
+            lists[si] = slab_lists(rows, slabs[si].k0, slabs[si].k1, (size_t)n * n);
+            slabs[si].n_touched = (int)lists[si].node_id.size();
         }
         lap("per-slab lists");
         // ---- uploads (queued behind the inversion on the set-up stream)
@@ -1376,11 +1172,11 @@ struct Solver final : SolverBase {
             sl.touched_save.alloc((size_t)std::max(sl.n_touched, 1));
         }
         lap("slab uploads");
-        if (total_slabs == 1 && fft_available() && need_node_tables) build_active_tiles(unode);   // (the sparse sweeps exist for the FFT transforms only)
+        if (total_slabs == 1 && fft_available() && !dual_direct) build_active_tiles(index.unode);   // (the sparse sweeps exist for the FFT transforms only)
         lap("active tiles");
-        Bptr.upload(bptr, stream);
-        Bcol.upload(bcol, stream);
-        Bval.upload(bval, stream);
+        Bptr.upload(B.ptr, stream);
+        Bcol.upload(B.col, stream);
+        Bval.upload(B.val, stream);
         have_B = !dual_direct;
         lap("B uploaded");
         upload_red_tables(stream);
@@ -1392,228 +1188,69 @@ struct Solver final : SolverBase {
         have_constraints = true;
     }
 
-    // Two-level split of G (shm_twolevel.hip.h): boxes of `box`^3 cells, separator = cells with a coordinate that is a multiple of `box`.
-    // Returns false (caller falls back to the dense inverse) when a box would not fit the kernels' LDS staging even at box = 8.
-    bool build_two_level(const std::vector<int>& gptr, const std::vector<int>& gcol, const std::vector<double>& gval, DevArray<uint64_t>& d_tidx,
-                         DevArray<double>& d_tval) {
+    // The matrix the blocked Gauss-Jordan inverts in place (G itself, or the separator block of the two-level split), from its triplets: Ginv = 0, then scattered
+    void upload_and_scatter_G(const Triplets& t, int nrows, int ld, DevArray<uint64_t>& d_tidx, DevArray<double>& d_tval) {
+        hipStream_t stream = stream2;
+        ginv_rows = nrows;
+        ginv_ld = ld;
+        Ginv.alloc((size_t)ld * ld);
+        HIPCHK(hipMemsetAsync(Ginv.p, 0, (size_t)ld * ld * sizeof(double), stream));
+        d_tidx.upload(t.idx, stream);
+        d_tval.upload(t.val, stream);
+        hipLaunchKernelGGL(scatter_triplets_kernel, dim3(grid_for(t.idx.size(), 4096)), dim3(kBlock), 0, stream, (size_t)t.idx.size(), d_tidx.p, d_tval.p, Ginv.p);
+        HIPCHK(hipGetLastError());
+    }
+
+    // Two-level split of G (shm_twolevel.hip.h): partitioned on the host (two_level_partition); if it fits, uploaded, the boxes inverted and the Schur complement
+    // formed in Ginv.  Returns false (caller falls back to the dense inverse) when a box would not fit the kernels' LDS staging even at box = 4.
+    bool build_two_level(const Csr& G, DevArray<uint64_t>& d_tidx, DevArray<double>& d_tval) {
         hipStream_t stream = stream2;
         static const int box_env = knob("SHM_TL_BOX") ? atoi(knob("SHM_TL_BOX")) : 0;
-        const int64_t nn = n, pl = (int64_t)n * n;
-        std::vector<int> ci((size_t)m), cj((size_t)m), ck((size_t)m);
-        for (int r = 0; r < m; r++) {
-            const int64_t c = rows[(size_t)r].nodes[0];
-            ck[(size_t)r] = (int)(c / pl);
-            cj[(size_t)r] = (int)((c - (int64_t)ck[(size_t)r] * pl) / nn);
-            ci[(size_t)r] = (int)(c - (int64_t)ck[(size_t)r] * pl - (int64_t)cj[(size_t)r] * nn);
-        }
-        std::vector<int> boxid, slot, ptrI, ptrS, rowsI, colsS, sepRow, colour_of;
-        std::vector<size_t> offD, offE;
-        int P = 0, nS = 0, tl_maxs = 0, tl_maxc = 0;
-        for (int b : {box_env > 1 ? box_env : 16, 8, 4}) {
-            tl.box = b;
-            // box key -> compact id in order of first appearance (deterministic)
-            std::unordered_map<uint64_t, int> ids;
-            boxid.assign((size_t)m, -1);
-            slot.assign((size_t)m, -1);
-            sepRow.clear();
-            colour_of.clear();
-            std::vector<int> cnt;
-            for (int r = 0; r < m; r++) {
-                const int i = ci[(size_t)r], j = cj[(size_t)r], k = ck[(size_t)r];
-                if (i % b == 0 || j % b == 0 || k % b == 0) {
-                    slot[(size_t)r] = (int)sepRow.size();
-                    sepRow.push_back(r);
-                    continue;
-                }
-                const uint64_t key = (uint64_t)(i / b) | ((uint64_t)(j / b) << 20) | ((uint64_t)(k / b) << 40);
-                auto it = ids.find(key);
-                int id;
-                if (it == ids.end()) {
-                    id = (int)ids.size();
-                    ids.emplace(key, id);
-                    cnt.push_back(0);
-                    colour_of.push_back(((i / b) & 1) | (((j / b) & 1) << 1) | (((k / b) & 1) << 2));
-                } else id = it->second;
-                boxid[(size_t)r] = id;
-                cnt[(size_t)id]++;
-            }
-            P = (int)cnt.size();
-            nS = (int)sepRow.size();
-            if (P == 0 || nS == 0) return false;
-            ptrI.assign((size_t)P + 1, 0);
-            for (int a = 0; a < P; a++) ptrI[(size_t)a + 1] = ptrI[(size_t)a] + cnt[(size_t)a];
-            rowsI.assign((size_t)ptrI[(size_t)P], 0);
-            std::vector<int> fill(ptrI.begin(), ptrI.end() - 1);
-            for (int r = 0; r < m; r++)
-                if (boxid[(size_t)r] >= 0) {
-                    slot[(size_t)r] = fill[(size_t)boxid[(size_t)r]] - ptrI[(size_t)boxid[(size_t)r]];  // local index inside the box
-                    rowsI[(size_t)fill[(size_t)boxid[(size_t)r]]++] = r;
-                }
-            // separator columns of every box, in order of first appearance along its rows
-            ptrS.assign((size_t)P + 1, 0);
-            colsS.clear();
-            std::vector<int> mark((size_t)nS, -1);
-            int maxs = 0, maxc = 0;
-            for (int a = 0; a < P; a++) {
-                for (int t = ptrI[(size_t)a]; t < ptrI[(size_t)a + 1]; t++) {
-                    const int r = rowsI[(size_t)t];
-                    for (int e = gptr[(size_t)r]; e < gptr[(size_t)r + 1]; e++) {
-                        const int c = gcol[(size_t)e];
-                        if (boxid[(size_t)c] >= 0) continue;
-                        if (mark[(size_t)slot[(size_t)c]] != a) {
-                            mark[(size_t)slot[(size_t)c]] = a;
-                            colsS.push_back(slot[(size_t)c]);
-                        }
-                    }
-                }
-                ptrS[(size_t)a + 1] = (int)colsS.size();
-                maxs = std::max(maxs, cnt[(size_t)a]);
-                maxc = std::max(maxc, ptrS[(size_t)a + 1] - ptrS[(size_t)a]);
-            }
-            tl_maxs = maxs;
-            tl_maxc = maxc;
-            if (maxs <= kTlMaxBox && maxc <= kTlMaxBox) break;
-            if (b == 4) return false;
-        }
-        tl.P = P;
-        tl.nS = nS;
-        tl.nI = (int)rowsI.size();
-        tl.nSp = ((nS + kGJ - 1) / kGJ) * kGJ;
-        tl.ysz = (int)colsS.size();
-        // dense blocks D_a, E_a and the separator block F (as triplets of the padded Schur matrix)
-        offD.assign((size_t)P, 0);
-        offE.assign((size_t)P, 0);
-        size_t szD = 0, szE = 0;
-        for (int a = 0; a < P; a++) {
-            const size_t sa = (size_t)(ptrI[(size_t)a + 1] - ptrI[(size_t)a]), ca = (size_t)(ptrS[(size_t)a + 1] - ptrS[(size_t)a]);
-            offD[(size_t)a] = szD;
-            offE[(size_t)a] = szE;
-            szD += (size_t)tl_ld((int)sa) * (size_t)tl_ld((int)sa);   // D_a padded to whole 64-row blocks (the batched blocked Gauss-Jordan)
-            szE += sa * ca;
-        }
-        tl.szD = szD;
-        tl.szE = szE;
-        std::vector<double> hD(szD, 0.), hE(std::max<size_t>(szE, 1), 0.);
-        std::vector<uint64_t> tidx;
-        std::vector<double> tval;
-        std::vector<int> lcol((size_t)nS, -1);  // separator slot -> local column of the box being filled
-        for (int a = 0; a < P; a++) {
-            const int s0 = ptrI[(size_t)a], sa = ptrI[(size_t)a + 1] - s0, c0 = ptrS[(size_t)a], ca = ptrS[(size_t)a + 1] - c0;
-            for (int l = 0; l < ca; l++) lcol[(size_t)colsS[(size_t)(c0 + l)]] = l;
-            for (int t = sa; t < tl_ld(sa); t++) hD[offD[(size_t)a] + (size_t)t * (size_t)tl_ld(sa) + (size_t)t] = 1.0;   // identity on the padded diagonal
-            for (int t = 0; t < sa; t++) {
-                const int r = rowsI[(size_t)(s0 + t)];
-                for (int e = gptr[(size_t)r]; e < gptr[(size_t)r + 1]; e++) {
-                    const int c = gcol[(size_t)e];
-                    if (boxid[(size_t)c] >= 0) hD[offD[(size_t)a] + (size_t)t * (size_t)tl_ld(sa) + (size_t)slot[(size_t)c]] = gval[(size_t)e];  // same box (interiors of different boxes never couple)
-                    else hE[offE[(size_t)a] + (size_t)t * ca + (size_t)lcol[(size_t)slot[(size_t)c]]] = gval[(size_t)e];
-                }
-            }
-        }
-        for (int g = 0; g < nS; g++) {
-            const int r = sepRow[(size_t)g];
-            for (int e = gptr[(size_t)r]; e < gptr[(size_t)r + 1]; e++) {
-                const int c = gcol[(size_t)e];
-                if (boxid[(size_t)c] >= 0) continue;
-                tidx.push_back((uint64_t)g * (uint64_t)tl.nSp + (uint64_t)slot[(size_t)c]);
-                tval.push_back(gval[(size_t)e]);
-            }
-        }
-        for (int g = nS; g < tl.nSp; g++) {
-            tidx.push_back((uint64_t)g * tl.nSp + g);
-            tval.push_back(1.0);
-        }
-        // per separator row: the y-buffer slots of the boxes that border it, ascending (fixed summation order)
-        std::vector<int> adj_ptr((size_t)nS + 1, 0), adj_idx(colsS.size());
-        for (int v : colsS) adj_ptr[(size_t)v + 1]++;
-        for (int g = 0; g < nS; g++) adj_ptr[(size_t)g + 1] += adj_ptr[(size_t)g];
-        {
-            std::vector<int> fillp(adj_ptr.begin(), adj_ptr.end() - 1);
-            for (int y = 0; y < (int)colsS.size(); y++) adj_idx[(size_t)fillp[(size_t)colsS[(size_t)y]]++] = y;
-        }
-        // boxes by colour (parity of the box coordinates): boxes of one colour border disjoint separator rows
-        std::vector<int> clist;
-        for (int col = 0; col < 8; col++) {
-            tl.colour_ptr[col] = (int)clist.size();
-            for (int a = 0; a < P; a++)
-                if (colour_of[(size_t)a] == col) clist.push_back(a);
-        }
-        tl.colour_ptr[8] = (int)clist.size();
+        const TwoLevelPartition part = two_level_partition(rows, G, box_env);
+        tl.box = part.box;
+        if (!part.fits) return false;
+        const int P = tl.P = part.P;
+        tl.nS = part.nS;
+        tl.nI = part.nI;
+        tl.nSp = part.nSp;
+        tl.ysz = (int)part.colsS.size();
+        const size_t szD = tl.szD = part.szD, szE = tl.szE = part.szE;
+        tl.nChunks = (int)part.chunkBox.size();
+        tl.nTChunks = (int)part.tBox.size();
+        tl.nbMax = part.nbMax;
+        std::copy(part.colour_ptr, part.colour_ptr + 9, tl.colour_ptr);
+        std::copy(part.schur_ptr, part.schur_ptr + 9, tl.schur_ptr);
         // ---- device: upload, invert the boxes, Schur complement into Ginv
-        tl.ptrI.upload(ptrI, stream);
-        tl.ptrS.upload(ptrS, stream);
-        tl.rowsI.upload(rowsI, stream);
-        {   // row -> box map and the (box, 64-column chunk) list of the row- / column-parallel application kernels
-            std::vector<int> rowBox(rowsI.size()), chunkBox, chunkCol;
-            for (int a = 0; a < P; a++) {
-                for (int t = ptrI[(size_t)a]; t < ptrI[(size_t)a + 1]; t++) rowBox[(size_t)t] = a;
-                for (int l0 = 0; l0 < ptrS[(size_t)a + 1] - ptrS[(size_t)a]; l0 += kWave) {
-                    chunkBox.push_back(a);
-                    chunkCol.push_back(l0);
-                }
-            }
-            tl.nChunks = (int)chunkBox.size();
-            tl.rowBox.upload(rowBox, stream);
-            tl.chunkBox.upload(chunkBox, stream);
-            tl.chunkCol.upload(chunkCol, stream);
-            // set-up lists: (box, 16 rows of T) for all boxes; (box, 16 rows of the Schur update) per colour; offsets of the boxes' Gauss-Jordan panels
-            std::vector<int> tBox, tRow, sBox, sRow;
-            std::vector<size_t> offW((size_t)P, 0);
-            size_t szW = 0;
-            tl.nbMax = 0;
-            for (int a = 0; a < P; a++) {
-                const int sa = ptrI[(size_t)a + 1] - ptrI[(size_t)a];
-                for (int r0 = 0; r0 < sa; r0 += kTlRowsPerWg) {
-                    tBox.push_back(a);
-                    tRow.push_back(r0);
-                }
-                offW[(size_t)a] = szW;
-                szW += (size_t)kGJ * (size_t)tl_ld(sa);
-                tl.nbMax = std::max(tl.nbMax, tl_ld(sa) / kGJ);
-            }
-            tl.nTChunks = (int)tBox.size();
-            for (int col = 0; col < 8; col++) {
-                tl.schur_ptr[col] = (int)sBox.size();
-                for (int a = 0; a < P; a++) {
-                    if (colour_of[(size_t)a] != col) continue;
-                    for (int p0 = 0; p0 < ptrS[(size_t)a + 1] - ptrS[(size_t)a]; p0 += kTlRowsPerWg) {
-                        sBox.push_back(a);
-                        sRow.push_back(p0);
-                    }
-                }
-            }
-            tl.schur_ptr[8] = (int)sBox.size();
-            tl.tBox.upload(tBox, stream);
-            tl.tRow.upload(tRow, stream);
-            tl.sBox.upload(sBox, stream);
-            tl.sRow.upload(sRow, stream);
-            tl.offW.upload(offW, stream);
-            tl.gjP.alloc((size_t)P * kGJ * kGJ);
-            tl.gjR.alloc(std::max<size_t>(szW, 1));
-            tl.gjC.alloc(std::max<size_t>(szW, 1));
-        }
-        tl.colsS.upload(colsS, stream);
-        tl.sepRow.upload(sepRow, stream);
-        tl.adj_ptr.upload(adj_ptr, stream);
-        tl.adj_idx.upload(adj_idx, stream);
-        tl.colour_list.upload(clist, stream);
-        tl.offD.upload(offD, stream);
-        tl.offE.upload(offE, stream);
-        tl.D.upload(hD, stream);
-        tl.E.upload(hE, stream);
+        tl.ptrI.upload(part.ptrI, stream);
+        tl.ptrS.upload(part.ptrS, stream);
+        tl.rowsI.upload(part.rowsI, stream);
+        tl.rowBox.upload(part.rowBox, stream);
+        tl.chunkBox.upload(part.chunkBox, stream);
+        tl.chunkCol.upload(part.chunkCol, stream);
+        tl.tBox.upload(part.tBox, stream);
+        tl.tRow.upload(part.tRow, stream);
+        tl.sBox.upload(part.sBox, stream);
+        tl.sRow.upload(part.sRow, stream);
+        tl.offW.upload(part.offW, stream);
+        tl.gjP.alloc((size_t)P * kGJ * kGJ);
+        tl.gjR.alloc(std::max<size_t>(part.szW, 1));
+        tl.gjC.alloc(std::max<size_t>(part.szW, 1));
+        tl.colsS.upload(part.colsS, stream);
+        tl.sepRow.upload(part.sepRow, stream);
+        tl.adj_ptr.upload(part.adj_ptr, stream);
+        tl.adj_idx.upload(part.adj_idx, stream);
+        tl.colour_list.upload(part.colour_list, stream);
+        tl.offD.upload(part.offD, stream);
+        tl.offE.upload(part.offE, stream);
+        tl.D.upload(part.hD, stream);
+        tl.E.upload(part.hE, stream);
         tl.Tm.alloc(std::max<size_t>(szE, 1));
         tl.tbuf.alloc((size_t)tl.nI);
-        tl.ybuf.alloc(std::max<size_t>(colsS.size(), 1));
+        tl.ybuf.alloc(std::max<size_t>(part.colsS.size(), 1));
         tl.vS.alloc((size_t)tl.nSp);
         tl.uS.alloc((size_t)tl.nSp);
         HIPCHK(hipMemsetAsync(tl.vS.p, 0, (size_t)tl.nSp * sizeof(double), stream));
-        ginv_rows = nS;
-        ginv_ld = tl.nSp;
-        Ginv.alloc((size_t)tl.nSp * tl.nSp);
-        HIPCHK(hipMemsetAsync(Ginv.p, 0, (size_t)tl.nSp * tl.nSp * sizeof(double), stream));
-        d_tidx.upload(tidx, stream);
-        d_tval.upload(tval, stream);
-        hipLaunchKernelGGL(scatter_triplets_kernel, dim3(grid_for(tidx.size(), 4096)), dim3(kBlock), 0, stream, (size_t)tidx.size(), d_tidx.p, d_tval.p, Ginv.p);
+        upload_and_scatter_G(part.F, tl.nS, tl.nSp, d_tidx, d_tval);
         gjFlag.alloc(2);   // [0]: blocked Gauss-Jordan (enqueue_gj_invert), [1]: the boxes' inverses; both read by finish_invert_G()
         HIPCHK(hipMemsetAsync(gjFlag.p + 1, 0, sizeof(int), stream));
         {   // all boxes' D_a^-1 at once: the blocked Gauss-Jordan of enqueue_gj_invert(), batched over the boxes (blockIdx.y)
@@ -1646,7 +1283,7 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
         // (no synchronisation here: the uploads above were staged, and a non-positive pivot of a box is reported by finish_invert_G() with the others --
         // waiting for the set-up stream at this point stalls the rest of the host set-up behind a Step-1 kernel that leaves it no SIMD)
-        log("[shm] two-level inverse of A A^T: box %d, %d boxes (%d interior rows, largest box %d rows x %d separator columns), separator %d rows", tl.box, P, tl.nI, tl_maxs, tl_maxc, nS);
+        log("[shm] two-level inverse of A A^T: box %d, %d boxes (%d interior rows, largest box %d rows x %d separator columns), separator %d rows", tl.box, P, tl.nI, part.maxs, part.maxc, tl.nS);
         return true;
     }
 
@@ -1862,28 +1499,7 @@ struct Solver final : SolverBase {
         // its own work
         if (!plan.green_early) enqueue_green_table(st);
         // rows in Morton order of their cells: the 16 x 16 tiles of the assembly then read neighbouring table entries
-        std::vector<std::pair<uint64_t, int>> key((size_t)m);
-        auto spread = [](uint64_t v) {
-            v &= 0x1fffff;
-            v = (v | v << 32) & 0x1f00000000ffffULL;
-            v = (v | v << 16) & 0x1f0000ff0000ffULL;
-            v = (v | v << 8) & 0x100f00f00f00f00fULL;
-            v = (v | v << 4) & 0x10c30c30c30c30c3ULL;
-            v = (v | v << 2) & 0x1249249249249249ULL;
-            return v;
-        };
-        for (int r = 0; r < m; r++) key[(size_t)r] = {spread((uint64_t)rows[r].cell[0]) | spread((uint64_t)rows[r].cell[1]) << 1 | spread((uint64_t)rows[r].cell[2]) << 2, r};
-        std::sort(key.begin(), key.end());
-        h_rowX.resize(4 * (size_t)m);
-        h_rowT.resize(3 * (size_t)m);
-        for (int q = 0; q < m; q++) {
-            const int r = key[(size_t)q].second;
-            for (int a = 0; a < 3; a++) {
-                h_rowX[4 * (size_t)q + a] = rows[r].cell[a];
-                h_rowT[3 * (size_t)q + a] = rows[r].t[a];
-            }
-            h_rowX[4 * (size_t)q + 3] = r;   // the row this sorted slot stands for
-        }
+        schur_row_order(rows, h_rowX, h_rowT);
         d_rowX.upload(h_rowX, st);
         d_rowT.upload(h_rowT, st);
         Sdense.alloc((size_t)mp * mp);
@@ -2574,30 +2190,14 @@ struct Solver final : SolverBase {
     void build_active_tiles(const std::vector<int64_t>& touched_nodes) {
         Slab<T>& sl = slabs[0];
         const int L = dct_lines_for(log2n_of(n), (int)sizeof(TP));
-        const int64_t nn = n, pl = (int64_t)n * n;
-        std::vector<int> ax, planes;
-        for (int64_t g : touched_nodes) {
-            const int64_t k = g / pl, j = (g - k * pl) / nn;
-            ax.push_back((int)((k * nn + j) / L));
-            planes.push_back((int)k);
-        }
-        std::sort(ax.begin(), ax.end());
-        ax.erase(std::unique(ax.begin(), ax.end()), ax.end());
-        std::sort(planes.begin(), planes.end());
-        planes.erase(std::unique(planes.begin(), planes.end()), planes.end());
-        std::vector<int> ay;
-        const int tiles_a = n / L;
-        for (int z : planes)
-            for (int xc = 0; xc < tiles_a; xc++) ay.push_back(xc + z * tiles_a);
-        std::vector<unsigned> zm((size_t)(n + 31) / 32, 0u);
-        for (int z : planes) zm[(size_t)z >> 5] |= 1u << (z & 31);
-        sl.act_z.upload(zm, stream2);
-        sl.n_act_planes = (int)planes.size();
-        sl.act_planes.upload(planes, stream2);
-        sl.n_act_x = (int)ax.size();
-        sl.n_act_y = (int)ay.size();
-        sl.act_x.upload(ax, stream2);
-        sl.act_y.upload(ay, stream2);
+        const ActiveTiles at = active_tiles(touched_nodes, n, L);
+        sl.act_z.upload(at.zmask, stream2);
+        sl.n_act_planes = (int)at.planes.size();
+        sl.act_planes.upload(at.planes, stream2);
+        sl.n_act_x = (int)at.ax.size();
+        sl.n_act_y = (int)at.ay.size();
+        sl.act_x.upload(at.ax, stream2);
+        sl.act_y.upload(at.ay, stream2);
         sl.S1.alloc(sl.nown);
         sl.S2.alloc(sl.nown);
         sl.S4.alloc(sl.nown);

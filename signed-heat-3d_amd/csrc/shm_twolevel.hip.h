@@ -37,11 +37,9 @@ struct TlBoxes {               // device views shared by the kernels below (all 
 // boxes of rocker at 512^3, 45 ms for the 280-row boxes of the same mesh at 256^3) and formed T_a and the Schur update with one workgroup per box as well
 // (3.8 / 41 ms) -- together the 6 ms of set-up an fp32 solve of configs[2] waits for after its Step 1, 41 ms for configs[4], and 88 ms behind an 84 ms Step 1
 // for rocker at 256^3 in fp64.
-constexpr int kTlMaxBox = 2048;  // rows / separator columns of a box (the application kernels stage them in LDS)
-__host__ __device__ __forceinline__ int tl_ld(int s) { return (s + 63) / 64 * 64; }
+// (kTlMaxBox, tl_ld and kTlRowsPerWg: shm_constraints.h, where the host builds the boxes)
 
 // T_a = D_a^-1 E_a for all boxes: a workgroup per (box, 16 rows of T), a wave per 4 rows, lanes = consecutive columns (coalesced rows of E)
-constexpr int kTlRowsPerWg = 16;
 static __global__ __launch_bounds__(kBlock) void tl_T_kernel(TlBoxes B, const int* __restrict__ chunkBox, const int* __restrict__ chunkRow, const double* __restrict__ Dinv,
                                                       const double* __restrict__ E, double* __restrict__ Tm, int prio) {
     if (prio) __builtin_amdgcn_s_setprio(3);   // beside the tiered Step 1 (see gj_panels_kernel)
