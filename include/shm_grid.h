@@ -236,8 +236,11 @@ shm_status shm_grid_get_field_planes(shm_solver* s, shm_field f, int32_t k_begin
 shm_status shm_grid_apply_laplacian(shm_solver* s, const double* u, double* out);
 /* Constraint rows (signed_heat_grid_solver.cpp:80-98): nodes/coeffs hold 8*S entries; *m rows written. */
 shm_status shm_grid_get_constraints(shm_solver* s, int64_t* nodes, double* coeffs, int32_t* m);
-/* The explicit Schur complement S = A K^+ A^T the dual solver iterates on when the problem qualifies (one slab; n = 2^k <= 512 and m <= 4096 (direct solve), or m <= 16384 in the fp64 solve with shm_opts.step1_arith = SHM_STEP1_AUTO where the library estimates the dense mat-vec cheaper than its sparse sweeps through the grid; any other n: m <= 16384): m x m
- * doubles, row-major; *m rows.  SHM_ERR_STATE when the solver applies S through the grid instead.  Test entry point (world==1). */
+/* The explicit Schur complement S = A K^+ A^T of the dual solver, as a solve with default options would assemble it: m x m doubles, row-major; *m rows.
+ * One slab.  n not a power of two (the transforms are dense DCT products): always, for every m <= 16384.  n = 2^k in [16, 512]: where the library estimates
+ * the dense mat-vec cheaper than its sparse sweeps through the grid and the assembly hidden behind Step 1 (plan_explicit_S, csrc/shm_plan.h; m <= 16384
+ * beside the tiered Step 1, 8192 otherwise), or wherever it fits under the experiment knob SHM_DUAL_DENSE_S_ALWAYS.  SHM_ERR_STATE when S would be applied
+ * through the grid instead: several slabs, n = 2^k where the estimate says so or n > 512, or too many rows.  Test entry point (world==1). */
 shm_status shm_grid_get_schur(shm_solver* s, double* out, int32_t* m);
 /* v <- v - A^T (A A^T)^-1 A v on the device (the projector inside the CG); v: n^3 doubles, world==1. */
 shm_status shm_grid_apply_projector(shm_solver* s, double* v);

@@ -2946,7 +2946,7 @@ struct Solver final : SolverBase {
         HIPCHK(hipSetDevice(cfg.device));
         build_constraints(plan_inputs(nullptr), Plan());
         *m_out = m;
-        if (!have_S) throw Error(SHM_ERR_STATE, "no explicit Schur complement for this problem (several slabs, n not a power of two or > 512, or too many rows)");
+        if (!have_S) throw Error(SHM_ERR_STATE, "no explicit Schur complement for this problem (several slabs, more than 16384 rows, or n = 2^k where the plan applies S through the grid: n > 512, or the estimate of plan_explicit_S without SHM_DUAL_DENSE_S_ALWAYS)");
         HIPCHK(hipMemcpy2DAsync(out, (size_t)m * sizeof(double), Sdense.p, (size_t)mp * sizeof(double), (size_t)m * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, stream2));
         HIPCHK(hipStreamSynchronize(stream2));
     }

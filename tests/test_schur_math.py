@@ -1,6 +1,8 @@
 """The identities behind csrc/shm_schur.hip.h, checked in numpy at n = 8 (no GPU, no product code): the Neumann Green's function of the 7-point Laplacian
 is the sum of eight images of one cosine table on the integer lattice, and the Schur complement entry of two trilinear rows is a 6 x 6 x 6 weighted sum of
-table entries.  (The device kernels themselves are held to the operator they replace in tests/test_gpu_parity.py::test_explicit_schur_complement_is_A_Kplus_AT.)"""
+table entries.  (The device kernels themselves are held entry by entry, at grid and tile edges, to an fp64 host reference that shares no transform with them in
+tests/test_schur_edges.py -- which holds that reference to a dense pseudo-inverse and to the table formula below -- and to the operator they replace in
+tests/test_gpu_parity.py::test_explicit_schur_complement_is_A_Kplus_AT.)"""
 import numpy as np
 
 N_SIDE, H = 8, 0.37

@@ -327,6 +327,27 @@ def _on_grid_sources(seed):
     return d, on_nodes
 
 
+def _sources_in_cells(n, cells, t, seed, cell=2.0 ** -3, bbox_min=(-1.0, -1.0, -1.0), lam_cells=0.45):
+    """One source per chosen cell: cells (m, 3) integer (i, j, k) in [0, n - 2], distinct, and local coordinates t (m, 3) in [0, 1) -- set_problem admits no
+    source on the top faces, so a node of index n - 1 is reached as t = 1 - 2^-30 in cell n - 2.  bbox_min and cell are powers of two (or sums of few), and t is
+    expected to have few bits, so that bbox_min + (cells + t) * cell is exact and the library's locate_source gives back exactly (cells, t): every row, fold and
+    weight of a test is then the one the test chose.  Random unit normals, areas within a factor 3, lambda = lam_cells / cell.  Returns set_problem arguments."""
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, 3)
+    t = np.asarray(t, dtype=np.float64).reshape(-1, 3)
+    m = cells.shape[0]
+    assert t.shape[0] == m and cells.min() >= 0 and cells.max() <= n - 2 and t.min() >= 0.0 and t.max() < 1.0
+    assert len({tuple(c) for c in cells.tolist()}) == m, "one source per cell: the cells must be distinct"
+    bbox_min = np.asarray(bbox_min, dtype=np.float64)
+    pos = bbox_min + (cells + t) * cell
+    back = np.floor((pos - bbox_min) / cell)                                           # locate_source, shm_constraints.h
+    assert np.array_equal(back, cells) and np.array_equal((pos - (back * cell + bbox_min)) / cell, t), "the positions do not give back the chosen cells and t exactly"
+    rng = np.random.default_rng(seed)
+    u = rng.normal(size=(m, 3))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    area = cell * cell * (0.5 + rng.random(m))
+    return dict(pos=pos, wnormal=u * area[:, None], area=area, lam=lam_cells / cell, n=int(n), bbox_min=bbox_min, cell=float(cell))
+
+
 def test_step1_sources_exactly_on_nodes_and_faces(shm, oracle_c):
     """Y: the nodes under a source come out non-finite exactly where the oracle's do (w e^0 / 0), including under a source whose weight's fp32 square underflows
     (the kernel's `valid` mask used to read that source as padding and leave its node finite); the rest within the bounds.  Constraint rows bit-exact against
