@@ -311,6 +311,52 @@ shm_status shm_grid_isosurface_indexed(shm_solver* s, double isovalue, int64_t* 
 shm_status shm_grid_get_isosurface_indexed(shm_solver* s, double* vertices /* [3*nv] */, int64_t* triangles /* [3*nt] */);
 shm_status shm_grid_get_isosurface_indexed_device(shm_solver* s, void* d_vertices /* [3*nv], handle precision */, void* d_triangles /* [3*nt] int64 */);
 
+/* --- connected components of the indexed isosurface: label, measure, filter -----------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the four entry points by their symbols (dlsym).
+ * At isovalue 0 the mesh of shm_grid_isosurface_indexed is not one surface: phi is kinked at cell scale around the constraint cells, and the zero set carries
+ *   closed specks of 8 - 40 triangles beside the shell (14 components on the 24^3 bunny, one at 0.25 max phi).  These entry points label the resident mesh's
+ *   components, measure them and compact the mesh to a chosen subset without leaving the device (kernels in csrc/shm_iso_components.hip.h).
+ * Component: a maximal set of vertices joined through triangles; identity is by index, not by position.  root[v] is the smallest vertex id of v's component, a
+ *   vertex in no triangle is a component of its own, and root is a function of the triangle list alone: whatever order the threads run in, two calls give
+ *   bit-identical labels (a lock-free union-find whose links only ever point to smaller ids, then a pass that points every vertex at its root; no thread waits
+ *   for another).  Ids are 64-bit throughout.
+ * shm_grid_label_mesh_device: any indexed mesh in device buffers; needs only a handle (no problem, no phi).  d_triangles: int64 [3*nt] on the handle's device;
+ *   d_root: int64 [nv] out; *n_components: how many roots.  Both pointers are checked as shm_grid_sample_device checks its own (host memory, another device's
+ *   memory or an allocation that is too small is SHM_ERR_INVALID), and a pass over the triangles checks every index BEFORE any is used: an index outside
+ *   [0, nv) is SHM_ERR_INVALID with d_root not written.  nv < 0, nt < 0, a count above 2^40 or NULL with a positive count is SHM_ERR_INVALID.  nv = 0 is valid,
+ *   and so is nt = 0 (nv components of one vertex each); repeated corners (a,a,b), (a,a,a) and duplicate triangles are valid.  Synchronous.
+ * shm_grid_isosurface_components: labels the mesh of the last shm_grid_isosurface_indexed, ranks the roots ascending (a flag and a scan) and fills one record
+ *   per component on the device.  Every number is a function of the mesh alone: counts are integer sums; lo / hi are minima / maxima taken on an
+ *   order-preserving integer image of the doubles; touches_box is an OR of exact comparisons (a vertex's off-axis coordinates are idx*cell + bbox_min with no
+ *   further term); area and volume are fixed-point sums in int64, so they do not depend on the order of the adds:
+ *     area   = qA * sum_t llrint(A_t / qA),  qA = cell^2 2^-32,  A_t = |(b-a) x (c-a)| / 2                      (fp64, unfused)
+ *     volume = qV * sum_t llrint(V_t / qV),  qV = cell^3 2^-20,  V_t = (a-o) . ((b-o) x (c-o)) / 6,  o = bbox_min
+ *   cross(u, w) = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0); squares and dot products are summed (x + y) + z.  The volume is positive for a blob of inside
+ *   (normals towards increasing phi), negative for an enclosed pocket of outside, and meaningful only when touches_box == 0.  A triangle lies inside one cell,
+ *   so A_t stays below 2^33 and |V_t| below 2^31 quanta for n <= 1024, and the sums hold 2^30 triangles.
+ * shm_grid_get_isosurface_components: copies the records and, optionally, the rank of every triangle's and every vertex's component to host buffers.
+ * shm_grid_isosurface_keep_components: compacts the resident mesh to the components with keep[c] != 0.  Vertices and triangles keep their relative order (the
+ *   result is still in the canonical order), indices are renumbered by a prefix scan of the kept flags, positions stay bit-identical.  Both indexed getters
+ *   then return the filtered mesh; the records are dropped (call shm_grid_isosurface_components again for the survivors: it returns the same integers);
+ *   shm_grid_isosurface_indexed rebuilds the full mesh.
+ * State: _components needs a valid indexed mesh (SHM_ERR_STATE before a build and after anything that replaced or invalidated phi); _get_ and _keep_ need a
+ *   valid labelling (SHM_ERR_STATE before _components, after a rebuild and after a _keep_).  An empty mesh is SHM_OK with 0 components, and NULL is accepted where
+ *   a count is 0.  world > 1 is SHM_ERR_STATE for all three (a component crosses ranks); any local_slabs is accepted.  phi, Y, psi, the brick extrema, the mesh of
+ *   shm_grid_isosurface and every other flag are left as they were. */
+typedef struct {
+    int64_t first_vertex;          /* smallest vertex id = the component's name; records ascend in it */
+    int64_t n_vertices, n_triangles;
+    double  area, volume;          /* fixed-point sums, above */
+    double  lo[3], hi[3];          /* min / max of its vertices' positions, bitwise those of the resident fp64 vertices */
+    int32_t touches_box;           /* 1: some vertex has a coordinate == bbox_min[a] or == (n-1)*cell + bbox_min[a] */
+    int32_t reserved;
+} shm_iso_component;               /* 96 bytes */
+shm_status shm_grid_label_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_triangles /* [3*nt] int64 */, void* d_root /* [nv] int64 */, int64_t* n_components);
+shm_status shm_grid_isosurface_components(shm_solver* s, int64_t* n_components);
+shm_status shm_grid_get_isosurface_components(shm_solver* s, shm_iso_component* comps /* [nc] */, int64_t* tri_component /* [nt] or NULL */,
+                                              int64_t* vertex_component /* [nv] or NULL */);
+shm_status shm_grid_isosurface_keep_components(shm_solver* s, const uint8_t* keep /* [nc] */, int64_t* n_vertices, int64_t* n_triangles);
+
 /* --- audit of Step 1 at sampled grid nodes ---------------------------------------------------------------------------------------------------------------
  * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
  * What it answers: what did the Step 1 that produced the resident Y cost in accuracy, at these nodes?  For every node of the list the device re-evaluates

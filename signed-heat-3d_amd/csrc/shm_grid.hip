@@ -222,6 +222,19 @@ shm_status shm_grid_get_isosurface_indexed_device(shm_solver* s, void* d_vertice
     return guard(s, [&] { s->impl->get_isosurface_indexed_device(d_vertices, d_triangles); });
 }
 
+shm_status shm_grid_label_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_triangles, void* d_root, int64_t* n_components) {
+    return guard(s, [&] { s->impl->label_mesh_device(nv, nt, d_triangles, d_root, n_components); });
+}
+shm_status shm_grid_isosurface_components(shm_solver* s, int64_t* n_components) {
+    return guard(s, [&] { s->impl->isosurface_components(n_components); });
+}
+shm_status shm_grid_get_isosurface_components(shm_solver* s, shm_iso_component* comps, int64_t* tri_component, int64_t* vertex_component) {
+    return guard(s, [&] { s->impl->get_isosurface_components(comps, tri_component, vertex_component); });
+}
+shm_status shm_grid_isosurface_keep_components(shm_solver* s, const uint8_t* keep, int64_t* n_vertices, int64_t* n_triangles) {
+    return guard(s, [&] { s->impl->isosurface_keep_components(keep, n_vertices, n_triangles); });
+}
+
 shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered) {
     return guard(s, [&] { s->impl->sample(Q, pts, phi_out, grad_out, n_answered); });
 }

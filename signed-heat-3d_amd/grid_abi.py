@@ -21,6 +21,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
+               "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
@@ -81,6 +82,33 @@ class ShmRedistanceStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class ShmIsoComponent(C.Structure):
+    """shm_iso_component of include/shm_grid.h (shm_grid_isosurface_components): 96 bytes."""
+    _fields_ = [("first_vertex", C.c_int64), ("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("area", C.c_double), ("volume", C.c_double),
+                ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("touches_box", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same record as a numpy structured dtype: what GridSolver.isosurface_components returns an array of
+ISO_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_triangles", "<i8"), ("area", "<f8"), ("volume", "<f8"),
+                                ("lo", "<f8", (3,)), ("hi", "<f8", (3,)), ("touches_box", "<i4"), ("reserved", "<i4")])
+assert ISO_COMPONENT_DTYPE.itemsize == C.sizeof(ShmIsoComponent) == 96
+
+
+def largest_components_mask(comps, keep_largest=None, min_triangles=None):
+    """The mask isosurface_indexed(keep_largest=, min_triangles=) keeps: the keep_largest components with the most triangles (ties: the smaller
+    first_vertex first) among those with at least min_triangles triangles."""
+    nc = len(comps)
+    mask = np.ones(nc, dtype=np.uint8)
+    if min_triangles is not None:
+        mask &= (comps["n_triangles"] >= int(min_triangles)).astype(np.uint8)
+    if keep_largest is not None:
+        order = np.lexsort((comps["first_vertex"], -comps["n_triangles"]))   # n_triangles descending, then first_vertex ascending
+        top = np.zeros(nc, dtype=np.uint8)
+        top[order[:max(0, int(keep_largest))]] = 1
+        mask &= top
+    return mask
+
+
 def lib_path():
     """In-tree library; SHM_GRID_LIB selects another build of it (tools/dct_variants.sh A/B runs)."""
     return os.environ.get("SHM_GRID_LIB") or os.path.join(_HERE, "lib", "libshm_grid.so")
@@ -127,6 +155,11 @@ def load_library():
         lib.shm_grid_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.shm_grid_get_isosurface_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.shm_grid_get_isosurface_indexed_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "shm_grid_label_mesh_device"):   # added within ABI 5: found by symbol
+        lib.shm_grid_label_mesh_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.shm_grid_isosurface_components.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        lib.shm_grid_get_isosurface_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.shm_grid_isosurface_keep_components.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     if hasattr(lib, "shm_grid_audit_step1"):   # added within ABI 5: found by symbol (another build named by SHM_GRID_LIB may predate it)
         lib.shm_grid_audit_step1.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmStep1Audit)]
         lib.shm_audit_sample_nodes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p]
@@ -344,27 +377,79 @@ class GridSolver:
         self._chk(self._lib.shm_grid_get_isosurface(self._h, V.ctypes.data, F.ctypes.data))
         return V, F
 
-    def isosurface_indexed(self, isovalue=0.0, device=False):
+    def isosurface_indexed(self, isovalue=0.0, device=False, keep_largest=None, min_triangles=None):
         """The marching-cubes surface of isosurface(), welded and numbered on the device in a canonical order (shm_grid_isosurface_indexed): vertices
         ascend in 3 * (i + j n + k n^2) + axis of their grid edge, triangles in (cell, position in the case's table entry) -- isosurface()'s triangle
         order, so the two differ by a renumbering of the vertices.  Returns (V [nv, 3] float64, F [nt, 3] int64) as numpy arrays; with device=True,
         torch tensors on this handle's device, V float64 for SHM_F64 and float32 for SHM_F32 (the fp64 position rounded once), F int64, copied
-        device to device from the resident mesh.  As for sample_device, import torch before this library is loaded."""
+        device to device from the resident mesh.  As for sample_device, import torch before this library is loaded.
+        keep_largest=K and / or min_triangles=T filter the mesh on the device before it is fetched (isosurface_components + isosurface_keep): the K
+        components with the most triangles (ties: the smaller first_vertex) among those with at least T triangles, still in the canonical order."""
         nv, nt = C.c_int64(), C.c_int64()
         self._chk(self._lib.shm_grid_isosurface_indexed(self._h, float(isovalue), C.byref(nv), C.byref(nt)))
+        if keep_largest is not None or min_triangles is not None:
+            nv.value, nt.value = self.isosurface_keep(largest_components_mask(self.isosurface_components(), keep_largest, min_triangles))
+        return self.get_isosurface_indexed(nv.value, nt.value, device)
+
+    def get_isosurface_indexed(self, nv, nt, device=False):
+        """The resident indexed mesh of nv vertices and nt triangles (the counts the last build or isosurface_keep returned), as isosurface_indexed returns it."""
         if not device:
-            V = np.empty((nv.value, 3), dtype=np.float64)
-            F = np.empty((nt.value, 3), dtype=np.int64)
-            self._chk(self._lib.shm_grid_get_isosurface_indexed(self._h, V.ctypes.data if nv.value else None, F.ctypes.data if nt.value else None))
+            V = np.empty((nv, 3), dtype=np.float64)
+            F = np.empty((nt, 3), dtype=np.int64)
+            self._chk(self._lib.shm_grid_get_isosurface_indexed(self._h, V.ctypes.data if nv else None, F.ctypes.data if nt else None))
             return V, F
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("isosurface_indexed: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
         dev = torch.device("cuda", self.device)
-        V = torch.empty((nv.value, 3), dtype=torch.float64 if self.precision == SHM_F64 else torch.float32, device=dev)
-        F = torch.empty((nt.value, 3), dtype=torch.int64, device=dev)
-        self._chk(self._lib.shm_grid_get_isosurface_indexed_device(self._h, V.data_ptr() if nv.value else None, F.data_ptr() if nt.value else None))
+        V = torch.empty((nv, 3), dtype=torch.float64 if self.precision == SHM_F64 else torch.float32, device=dev)
+        F = torch.empty((nt, 3), dtype=torch.int64, device=dev)
+        self._chk(self._lib.shm_grid_get_isosurface_indexed_device(self._h, V.data_ptr() if nv else None, F.data_ptr() if nt else None))
         return V, F
+
+    def label_mesh_device(self, triangles, nv):
+        """Connected components of any indexed mesh in device memory (shm_grid_label_mesh_device): triangles is a contiguous torch int64 tensor of
+        3 nt indices ([nt, 3] or flat) on this handle's device, nv the number of vertices.  Returns (root, n_components): root [nv] int64 on that
+        device, root[v] the smallest vertex id of v's component.  An index outside [0, nv) raises ShmError (SHM_ERR_INVALID)."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("label_mesh_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        if triangles.dtype != torch.int64 or not triangles.is_contiguous() or triangles.numel() % 3:
+            raise ValueError("label_mesh_device: triangles must be a contiguous int64 tensor of 3 nt indices")
+        nt = triangles.numel() // 3
+        root = torch.empty(int(nv), dtype=torch.int64, device=triangles.device)
+        if triangles.is_cuda:
+            torch.cuda.current_stream(triangles.device).synchronize()   # the triangles may still be in flight on torch's stream
+        nc = C.c_int64()
+        self._chk(self._lib.shm_grid_label_mesh_device(self._h, int(nv), nt, triangles.data_ptr() if nt else None, root.data_ptr() if nv else None, C.byref(nc)))
+        return root, nc.value
+
+    def isosurface_components(self, labels=False):
+        """Label and measure the connected components of the resident indexed mesh on the device (shm_grid_isosurface_components): a numpy structured
+        array (ISO_COMPONENT_DTYPE, the fields of shm_iso_component), one record per component, ascending in first_vertex.  With labels=True returns
+        (records, tri_component [nt], vertex_component [nv]): the rank of every triangle's and every vertex's component."""
+        nc = C.c_int64()
+        self._chk(self._lib.shm_grid_isosurface_components(self._h, C.byref(nc)))
+        comps = np.zeros(nc.value, dtype=ISO_COMPONENT_DTYPE)
+        if not labels:
+            self._chk(self._lib.shm_grid_get_isosurface_components(self._h, comps.ctypes.data if nc.value else None, None, None))
+            return comps
+        # the counts of the resident mesh are the sums of the records' counts: fetch the records first, then the labels
+        self._chk(self._lib.shm_grid_get_isosurface_components(self._h, comps.ctypes.data if nc.value else None, None, None))
+        nv, nt = int(comps["n_vertices"].sum()), int(comps["n_triangles"].sum())
+        tc = np.empty(nt, dtype=np.int64)
+        vc = np.empty(nv, dtype=np.int64)
+        self._chk(self._lib.shm_grid_get_isosurface_components(self._h, comps.ctypes.data if nc.value else None, tc.ctypes.data if nt else None,
+                                                               vc.ctypes.data if nv else None))
+        return comps, tc, vc
+
+    def isosurface_keep(self, mask):
+        """Compact the resident indexed mesh to the components with mask[c] != 0 (shm_grid_isosurface_keep_components; mask as long as the last
+        isosurface_components()).  Returns (nv, nt) of the filtered mesh; get_isosurface_indexed(nv, nt) fetches it."""
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
+        nv, nt = C.c_int64(), C.c_int64()
+        self._chk(self._lib.shm_grid_isosurface_keep_components(self._h, mask.ctypes.data if mask.size else None, C.byref(nv), C.byref(nt)))
+        return nv.value, nt.value
 
     def sample(self, points, grad=False):
         """phi of the resident (shifted) phi at points [Q, 3] by the reference's trilinear evaluateFunction (shm_grid_sample): returns (phi [Q],

@@ -241,6 +241,39 @@ int shmh_isosurface_indexed(void* hv, double isoval, int64_t* nv, int64_t* nt, d
     });
 }
 
+// isosurfaceComponents through the C++ class: builds the indexed mesh of the last compute_distance at isoval, labels it and returns the count; with comps
+// ([nc] records) it copies them out as well.
+int shmh_isosurface_components(void* hv, double isoval, int64_t* nc, shm_iso_component* comps) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> v;
+        std::vector<std::array<size_t, 3>> f;
+        h->solver.isosurfaceIndexed(isoval, v, f);
+        const std::vector<shm_iso_component> c = h->solver.isosurfaceComponents();
+        if (nc) *nc = (int64_t)c.size();
+        if (comps && !c.empty()) std::memcpy(comps, c.data(), c.size() * sizeof(shm_iso_component));
+    });
+}
+
+// The filtering overload of isosurfaceIndexed, in shmh_isosurface_indexed's two calls (keep_largest / min_triangles < 0: no bound).
+int shmh_isosurface_indexed_filtered(void* hv, double isoval, int64_t keep_largest, int64_t min_triangles, int64_t* nv, int64_t* nt, double* vertices,
+                                     int64_t* triangles) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> v;
+        std::vector<std::array<size_t, 3>> f;
+        h->solver.isosurfaceIndexed(isoval, v, f, keep_largest, min_triangles);
+        if (nv) *nv = (int64_t)v.size();
+        if (nt) *nt = (int64_t)f.size();
+        if (vertices)
+            for (size_t a = 0; a < v.size(); a++)
+                for (int b = 0; b < 3; b++) vertices[3 * a + b] = v[a][b];
+        if (triangles)
+            for (size_t a = 0; a < f.size(); a++)
+                for (int b = 0; b < 3; b++) triangles[3 * a + b] = (int64_t)f[a][(size_t)b];
+    });
+}
+
 // auditStep1 through the C++ class: the Step 1 of the last compute_distance at a stratified sample of `count` nodes.
 int shmh_audit_step1(void* hv, int64_t count, uint64_t seed, shm_step1_audit* out) {
     Host* h = (Host*)hv;

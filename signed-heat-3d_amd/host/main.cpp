@@ -30,6 +30,8 @@ static void usage() {
                  "      --iso <value>     Contour phi at this value (default 0) and export the isosurface\n"
                  "      --export <file>   OBJ file of the isosurface (the demo writes ../export/isosurface.obj)\n"
                  "      --iso-indexed     Build the exported isosurface on the device in the canonical order (vertices by grid edge, triangles by cell)\n"
+                 "      --keep-largest <K> With --iso-indexed: keep the K connected components with the most triangles (filtered on the device)\n"
+                 "      --min-triangles <T> With --iso-indexed: drop the components with fewer than T triangles; either flag prints one line per component\n"
                  "      --query <file>    Points to evaluate phi at: raw little-endian float64 xyz triples\n"
                  "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n"
                  "      --rays <file>     Rays to cast against a level set of phi: raw little-endian float64, six values per ray (origin xyz, direction xyz)\n"
@@ -44,7 +46,7 @@ int main(int argc, char** argv) {
     std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut;
     double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
     bool redistance = false;
-    long long auditCount = -1;
+    long long auditCount = -1, keepLargest = -1, minTriangles = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
     bool verbose = false, isoIndexed = false;
@@ -73,6 +75,8 @@ int main(int argc, char** argv) {
         else if (s == "--iso") isoval = atof(need("--iso"));
         else if (s == "--export") exportPath = need("--export");
         else if (s == "--iso-indexed") isoIndexed = true;
+        else if (s == "--keep-largest") keepLargest = atoll(need("--keep-largest"));
+        else if (s == "--min-triangles") minTriangles = atoll(need("--min-triangles"));
         else if (s == "--query") queryPath = need("--query");
         else if (s == "--query-out") queryOut = need("--query-out");
         else if (s == "--rays") raysPath = need("--rays");
@@ -98,6 +102,10 @@ int main(int argc, char** argv) {
     }
     if (backend.exactStep1 && backend.referenceStep1) {
         std::cerr << "--exact-step1 and --reference-step1 exclude each other." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if ((keepLargest >= 0 || minTriangles >= 0) && !isoIndexed) {
+        std::cerr << "--keep-largest and --min-triangles filter the mesh of --iso-indexed." << std::endl;
         return EXIT_FAILURE;
     }
     if (path.empty()) {
@@ -142,7 +150,16 @@ int main(int argc, char** argv) {
         if (!exportPath.empty()) {
             std::vector<Vector3> iv;
             std::vector<std::array<size_t, 3>> jf;
-            if (isoIndexed) solver.isosurfaceIndexed(isoval, iv, jf);
+            if (isoIndexed && (keepLargest >= 0 || minTriangles >= 0)) {
+                std::vector<shm_iso_component> comps;
+                solver.isosurfaceIndexed(isoval, iv, jf, keepLargest, minTriangles, &comps);
+                for (size_t c = 0; c < comps.size(); c++) {
+                    char line[256];
+                    snprintf(line, sizeof line, "component %zu: first_vertex %lld nv %lld nt %lld area %.9g volume %.9g touches_box %d", c, (long long)comps[c].first_vertex,
+                             (long long)comps[c].n_vertices, (long long)comps[c].n_triangles, comps[c].area, comps[c].volume, (int)comps[c].touches_box);
+                    std::cerr << line << std::endl;
+                }
+            } else if (isoIndexed) solver.isosurfaceIndexed(isoval, iv, jf);
             else solver.isosurface(isoval, iv, jf);
             writeSurfaceMesh(iv, jf, exportPath);
             std::cerr << "Isosurface written to " << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;

@@ -102,6 +102,58 @@ void SignedHeatGridSolver::isosurfaceIndexed(double isoval, std::vector<Vector3>
     for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
 }
 
+void SignedHeatGridSolver::fetchIndexed(int64_t nv, int64_t nt, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces) {
+    std::vector<double> v((size_t)3 * nv);
+    std::vector<int64_t> f((size_t)3 * nt);
+    if (shm_grid_get_isosurface_indexed(handle, nv ? v.data() : nullptr, nt ? f.data() : nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+    vertices.resize((size_t)nv);
+    faces.resize((size_t)nt);
+    for (int64_t a = 0; a < nv; a++) vertices[(size_t)a] = Vector3{v[3 * a], v[3 * a + 1], v[3 * a + 2]};
+    for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
+}
+
+std::vector<shm_iso_component> SignedHeatGridSolver::isosurfaceComponents(std::vector<int64_t>* triComponent, std::vector<int64_t>* vertexComponent) {
+    if (!handle) throw std::runtime_error("isosurfaceComponents: computeDistance has not been called");
+    int64_t nc = 0;
+    if (shm_grid_isosurface_components(handle, &nc) != SHM_OK) throw std::runtime_error(std::string("shm_grid_isosurface_components: ") + shm_grid_last_error(handle));
+    std::vector<shm_iso_component> comps((size_t)nc);
+    if (shm_grid_get_isosurface_components(handle, nc ? comps.data() : nullptr, nullptr, nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+    if (triComponent || vertexComponent) {
+        int64_t nv = 0, nt = 0;   // the mesh's counts are the sums of the records' counts
+        for (const shm_iso_component& c : comps) {
+            nv += c.n_vertices;
+            nt += c.n_triangles;
+        }
+        if (triComponent) triComponent->resize((size_t)nt);
+        if (vertexComponent) vertexComponent->resize((size_t)nv);
+        if (shm_grid_get_isosurface_components(handle, nc ? comps.data() : nullptr, triComponent && nt ? triComponent->data() : nullptr,
+                                               vertexComponent && nv ? vertexComponent->data() : nullptr) != SHM_OK)
+            throw std::runtime_error(shm_grid_last_error(handle));
+    }
+    return comps;
+}
+
+void SignedHeatGridSolver::isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces, int64_t keepLargest,
+                                             int64_t minTriangles, std::vector<shm_iso_component>* components) {
+    if (!handle) throw std::runtime_error("isosurfaceIndexed: computeDistance has not been called");
+    int64_t nv = 0, nt = 0;
+    if (shm_grid_isosurface_indexed(handle, isoval, &nv, &nt) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_isosurface_indexed: ") + shm_grid_last_error(handle));
+    const std::vector<shm_iso_component> comps = isosurfaceComponents();
+    std::vector<size_t> order;
+    for (size_t c = 0; c < comps.size(); c++)
+        if (minTriangles < 0 || comps[c].n_triangles >= minTriangles) order.push_back(c);
+    // most triangles first; records ascend in first_vertex, so a stable sort breaks ties by the smaller first_vertex
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return comps[a].n_triangles > comps[b].n_triangles; });
+    if (keepLargest >= 0 && order.size() > (size_t)keepLargest) order.resize((size_t)keepLargest);
+    std::vector<uint8_t> keep(comps.size(), 0);
+    for (size_t c : order) keep[c] = 1;
+    if (shm_grid_isosurface_keep_components(handle, keep.empty() ? nullptr : keep.data(), &nv, &nt) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_isosurface_keep_components: ") + shm_grid_last_error(handle));
+    fetchIndexed(nv, nt, vertices, faces);
+    if (components) *components = comps;
+}
+
 shm_step1_audit SignedHeatGridSolver::auditStep1(size_t count, uint64_t seed) {
     if (!handle) throw std::runtime_error("auditStep1: computeDistance has not been called");
     std::vector<int64_t> nodes(std::min(count, nx * ny * nz));

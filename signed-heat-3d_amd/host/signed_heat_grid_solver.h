@@ -43,6 +43,15 @@ class SignedHeatGridSolver {
     // The same surface welded and numbered on the device in a canonical order (shm_grid_isosurface_indexed): vertices ascend in 3*(i + j n + k n^2) + axis
     // of their grid edge, faces keep isosurface()'s order, so the two differ by a renumbering of the vertices.  No host sort, no host weld.
     void isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces);
+    // Connected components of the mesh of the LAST isosurfaceIndexed() call, labelled and measured on the device (shm_grid_isosurface_components; the
+    // record and its fixed-point area / volume in include/shm_grid.h): one record per component, ascending in first_vertex.  With the optional vectors, the
+    // rank of every triangle's and every vertex's component.  At isovalue 0 the surface carries closed specks beside the shell: this is how to see them.
+    std::vector<shm_iso_component> isosurfaceComponents(std::vector<int64_t>* triComponent = nullptr, std::vector<int64_t>* vertexComponent = nullptr);
+    // isosurfaceIndexed with "keep the shell, drop the floaters" done on the device before the mesh is fetched (shm_grid_isosurface_keep_components): of the
+    // components with at least minTriangles triangles (< 0: no bound) the keepLargest with the most triangles (< 0: all; ties: the smaller first_vertex).
+    // The mesh stays in the canonical order.  components (optional) receives the records of the unfiltered mesh.
+    void isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces, int64_t keepLargest, int64_t minTriangles,
+                           std::vector<shm_iso_component>* components = nullptr);
 
     // Stands for the reference's private evaluateFunction(u, q) (signed_heat_grid_solver.cpp:405-431), here public and batched: the trilinear value of the phi of
     // the LAST computeDistance() call at every point of q, evaluated on the device (shm_grid_sample; box, NaN and gradient rules in include/shm_grid.h).
@@ -90,6 +99,7 @@ class SignedHeatGridSolver {
     shm_stats stats{};
 
     void ensureHandle();
+    void fetchIndexed(int64_t nv, int64_t nt, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces);
     void buildGrid(const Vector3& c, double r, const SignedHeat3DOptions& options);
     VectorXd solveOnDevice(bool scrub, const SignedHeat3DOptions& options);
 };

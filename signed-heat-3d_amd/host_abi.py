@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .grid_abi import ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
+from .grid_abi import ISO_COMPONENT_DTYPE, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -44,6 +44,8 @@ def load_host_library():
     lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
     lib.shmh_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+    lib.shmh_isosurface_components.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.c_void_p]
+    lib.shmh_isosurface_indexed_filtered.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.argtypes = [C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.restype = None
     _LIB = lib
@@ -150,15 +152,31 @@ class HostSolver:
         self._chk(self._lib.shmh_redistance(self._h, float(isovalue), float(band), psi.ctypes.data, C.byref(st)))
         return psi, st.as_dict()
 
-    def isosurface_indexed(self, isovalue=0.0):
+    def isosurface_indexed(self, isovalue=0.0, keep_largest=None, min_triangles=None):
         """isosurfaceIndexed of the C++ mirror: the marching-cubes surface of the last compute_distance, welded and numbered on the device in the
-        canonical order (shm_grid_isosurface_indexed).  Returns (V [nv, 3] float64, F [nt, 3] int64)."""
+        canonical order (shm_grid_isosurface_indexed).  Returns (V [nv, 3] float64, F [nt, 3] int64).  With keep_largest / min_triangles, the overload
+        that filters the mesh's connected components on the device first (the keep_largest with the most triangles among those of at least min_triangles)."""
         nv, nt = C.c_int64(), C.c_int64()
-        self._chk(self._lib.shmh_isosurface_indexed(self._h, float(isovalue), C.byref(nv), C.byref(nt), None, None))
+        if keep_largest is None and min_triangles is None:
+            call = lambda *a: self._lib.shmh_isosurface_indexed(self._h, float(isovalue), *a)   # noqa: E731
+        else:
+            kl, mt = -1 if keep_largest is None else int(keep_largest), -1 if min_triangles is None else int(min_triangles)
+            call = lambda *a: self._lib.shmh_isosurface_indexed_filtered(self._h, float(isovalue), kl, mt, *a)   # noqa: E731
+        self._chk(call(C.byref(nv), C.byref(nt), None, None))
         V = np.empty((nv.value, 3), dtype=np.float64)
         F = np.empty((nt.value, 3), dtype=np.int64)
-        self._chk(self._lib.shmh_isosurface_indexed(self._h, float(isovalue), None, None, V.ctypes.data, F.ctypes.data))
+        self._chk(call(None, None, V.ctypes.data, F.ctypes.data))
         return V, F
+
+    def isosurface_components(self, isovalue=0.0):
+        """isosurfaceComponents of the C++ mirror on the indexed mesh at `isovalue`: a numpy structured array of shm_iso_component records
+        (grid_abi.ISO_COMPONENT_DTYPE), one per connected component, ascending in first_vertex."""
+        nc = C.c_int64()
+        self._chk(self._lib.shmh_isosurface_components(self._h, float(isovalue), C.byref(nc), None))
+        comps = np.zeros(nc.value, dtype=ISO_COMPONENT_DTYPE)
+        if nc.value:
+            self._chk(self._lib.shmh_isosurface_components(self._h, float(isovalue), C.byref(nc), comps.ctypes.data))
+        return comps
 
     def audit_step1(self, count=4096, seed=0):
         """auditStep1 of the C++ mirror: the Step 1 of the last compute_distance audited on the device at a stratified sample of `count` nodes
