@@ -457,7 +457,11 @@ shm_status shm_grid_raycast_device(shm_solver* s, int64_t Q, const void* d_origi
  *     neighbours, holds NaN and is counted in n_nonfinite.  With no cut edge anywhere: SHM_OK, n_frozen = 0, psi = s band everywhere.
  * Known limit: psi < 0 exactly where phi < isovalue, so every cell keeps its marching-cubes case, but a vertex moves along its edge: by <= 0.016 cell at the
  *   smooth offset levels of the 24^3 .. 64^3 fixtures, by up to 0.62 cell at isovalue 0, where phi is kinked at cell scale around the constraint cells.
- *   Extract the surface from phi; use psi for distances.  The frozen values are first-order: no sub-cell-exact initialisation.
+ *   Extract the surface from phi; use psi for distances.  psi is first-order everywhere, not only at the frozen nodes: a sub-cell-exact initialisation of the
+ *   frozen layer alone (the exact distance to the marching-cubes triangles there, the sweeps unchanged) was prototyped in numpy and does not help -- on a sphere
+ *   the whole-field error stays at 0.74 cell (n = 24) and 0.90 cell (n = 33) with either initialisation, because the sweeps dominate it, and the zero set of psi
+ *   moves further from phi's (0.56 against 0.34 cell on the 24^3 bunny at isovalue 0).  What helps is the exact distance at every node of a band:
+ *   shm_grid_redistance_exact below.
  * State: valid whenever shm_grid_sample is; SHM_ERR_STATE before a solve, after a test entry point that overwrote phi, and with world > 1 (any local_slabs
  *   is fine).  phi, Y, both isosurface meshes, the brick extrema and every flag are left as they were.  psi (n^3 values of the handle's precision) stays
  *   resident until phi is replaced or the handle is destroyed.
@@ -480,6 +484,54 @@ typedef struct {
 shm_status shm_grid_redistance(shm_solver* s, double isovalue, double band, shm_redistance_stats* out /* or NULL */);
 shm_status shm_grid_get_redistanced(shm_solver* s, double* psi_out /* [n^3] fp64 */);
 shm_status shm_grid_get_redistanced_device(shm_solver* s, void* d_psi /* [n^3], handle precision */);
+
+/* --- exact narrow-band distance to the contoured surface, and offset meshes ----------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * shm_grid_redistance_exact: psi = the signed Euclidean distance from every node to the marching-cubes surface of the resident phi, inside a band; it lands in
+ *   the resident slot of shm_grid_redistance, so shm_grid_get_redistanced / _device serve it unchanged (the slot holds whichever call ran last).  Inside the
+ *   band its error is the mesh's own deviation from the level set, which is second order in the cell (sphere: 0.054 cell at R = 6.9 cell, 0.033 at 11.2), where
+ *   the first-order psi is off by 0.16 / 0.38 / 0.74 cell at 2 / 4 / 8 cells from the surface.  Kernels in csrc/shm_redistance_exact.hip.h.
+ * M is the indexed marching-cubes mesh of the resident phi at `isovalue`, the one shm_grid_isosurface_indexed(isovalue) builds.  The call BUILDS it, through
+ *   that path, and leaves it resident and unfiltered: a side effect (shm_grid_redistance leaves the meshes alone; this call does not).  Distances are taken
+ *   to M's vertices exactly as resident, bitwise the doubles shm_grid_get_isosurface_indexed returns.
+ * Node positions are idx*cell + bbox_min per axis, the isosurface kernels' own expression.
+ * Pair distance (csrc/shm_tri_dist.h), fp64 without contraction, dot products summed (x + y) + z, A, B, C the triangle's corners minus the node position:
+ *   for each of the segments AB, BC, CA as (P, Q):  e = Q - P, ee = e.e;  t = clamp(-(P.e) / ee, 0, 1) if ee > 0, else 0;  c = P + t e;  the candidate is c.c;
+ *   for the face:  N = (B - A) x (C - A), nn = N.N, s = A.N;  the candidate is s^2 / nn and counts only if nn > 0 and, with q = (s / nn) N,
+ *     ((B - q) x (C - q)).N, ((C - q) x (A - q)).N and ((A - q) x (B - q)).N are all >= 0;
+ *   d^2 is the smallest candidate.  A zero-area triangle costs nothing special; they occur (whenever phi at a node equals the isovalue, the vertices of that
+ *   node's cut edges coincide).
+ * Result: u = T(sqrt(min over all triangles of d^2)), rounded once to the handle's precision T.  A node is reached iff u < band.  psi = s u at reached nodes and
+ *   s band elsewhere, s = -1 where phi < isovalue and +1 otherwise.  T o sqrt is monotone, so the minimum is taken over the per-pair T(sqrt(d^2)) (on the bit
+ *   pattern of the non-negative value), and the minimum commutes: psi is a function of phi, the isovalue and the band alone, two calls give bit-identical psi,
+ *   and any local_slabs works.  A node whose phi is not finite holds NaN and a cell with a non-finite corner contributes no triangle (neither can be injected
+ *   through this ABI; the rule is held by the numpy restatement, tests/redistance_exact_ref.py).
+ * Band: finite, positive and <= 16 cell, else SHM_ERR_INVALID (the work grows with (band / cell)^3 per surface cell; the cap keeps a call bounded).  With no
+ *   triangle the call returns SHM_OK, n_reached = 0 and psi = s band.
+ * Culling: a triangle lies in its cell's closed box, so the nodes offered a cell's triangles are those of [c - r, c + 1 + r]^3, r = ceil(band / cell), clipped
+ *   to the grid, whose distance to the cell's box -- exact in index space, integer gaps gx, gy, gz -- has (gx^2 + gy^2 + gz^2) cell^2 < band^2 (1 + 2^-18);
+ *   the slack keeps the cull a superset of the pairs that can be accepted under rounding.  n_candidate_pairs counts these (cell, node) pairs.
+ * State: the rules of shm_grid_redistance -- SHM_ERR_STATE before a solve, after a test entry point that overwrote phi, and with world > 1.  SHM_ERR_INVALID
+ *   for a NaN or infinite isovalue.  phi, Y, the mesh of shm_grid_isosurface, the brick extrema and every flag are left as they were; a call refused for its
+ *   arguments leaves psi and the indexed mesh alone.
+ * shm_grid_isosurface_indexed_psi: the indexed marching-cubes mesh of the resident psi (from either redistance call) at `distance`: the passes, case table,
+ *   inside rule (v < distance), vertex arithmetic and canonical order of shm_grid_isosurface_indexed.  The mesh goes into the resident indexed-mesh slot:
+ *   both indexed getters, shm_grid_isosurface_components, its getter and shm_grid_isosurface_keep_components work on it unchanged, and a later
+ *   shm_grid_isosurface_indexed or shm_grid_redistance_exact replaces it again.
+ *   |distance| + cell <= band must hold (always true for band = +inf), else SHM_ERR_INVALID: an edge cut at d has psi_a < d <= psi_b <= psi_a + cell < d + cell,
+ *   so both ends are unclamped and the vertex is interpolated between true values.  That holds for the exact psi, which is 1-Lipschitz; for the first-order psi
+ *   the same condition is enforced as the rule.  SHM_ERR_INVALID for a non-finite distance; SHM_ERR_STATE without a valid psi or with world > 1.  phi, psi, Y
+ *   and the brick extrema are untouched. */
+typedef struct {
+    int64_t n_vertices, n_triangles;   /* the mesh the distances were taken to */
+    int64_t n_reached;                 /* nodes with |psi| < band */
+    int64_t n_candidate_pairs;         /* (cell, node) pairs that passed the geometric cull: a function of the mesh and the band alone */
+    double max_abs;                    /* max |psi| over the reached nodes */
+    double isovalue, band;
+    double ms;                         /* device time of the call (the mesh build included) */
+} shm_redistance_exact_stats;
+shm_status shm_grid_redistance_exact(shm_solver* s, double isovalue, double band, shm_redistance_exact_stats* out /* or NULL */);
+shm_status shm_grid_isosurface_indexed_psi(shm_solver* s, double distance, int64_t* n_vertices, int64_t* n_triangles);
 
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */

@@ -254,6 +254,12 @@ shm_status shm_grid_raycast_device(shm_solver* s, int64_t Q, const void* d_origi
 shm_status shm_grid_redistance(shm_solver* s, double isovalue, double band, shm_redistance_stats* out) {
     return guard(s, [&] { s->impl->redistance(isovalue, band, out); });
 }
+shm_status shm_grid_redistance_exact(shm_solver* s, double isovalue, double band, shm_redistance_exact_stats* out) {
+    return guard(s, [&] { s->impl->redistance_exact(isovalue, band, out); });
+}
+shm_status shm_grid_isosurface_indexed_psi(shm_solver* s, double distance, int64_t* n_vertices, int64_t* n_triangles) {
+    return guard(s, [&] { s->impl->isosurface_indexed_psi(distance, n_vertices, n_triangles); });
+}
 shm_status shm_grid_get_redistanced(shm_solver* s, double* psi_out) {
     return guard(s, [&] { s->impl->get_redistanced(psi_out); });
 }

@@ -573,6 +573,8 @@ struct SolverBase {
     virtual void redistance(double, double, shm_redistance_stats*) = 0;
     virtual void get_redistanced(double*) = 0;
     virtual void get_redistanced_device(void*) = 0;
+    virtual void redistance_exact(double, double, shm_redistance_exact_stats*) = 0;
+    virtual void isosurface_indexed_psi(double, int64_t*, int64_t*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

@@ -27,6 +27,7 @@
 #include "shm_iso_components.hip.h"
 #include "shm_raycast.hip.h"
 #include "shm_redistance.hip.h"
+#include "shm_redistance_exact.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -3169,11 +3170,23 @@ struct Solver final : SolverBase {
         if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
         HIPCHK(hipSetDevice(cfg.device));
         halo_exchange(ARR_Q);  // phi lives in q; cells of the top owned plane need the plane above (collective with world > 1)
+        iso_idx_build(iso, false);
+        if (nv_out) *nv_out = iso_idx_nv;
+        if (nt_out) *nt_out = iso_idx_nt;
+    }
+    // The passes of shm_iso_indexed.hip.h over the slabs' phi or, from_psi, over the resident psi: one n^3 array without a ghost plane, walked as a single
+    // plane range by the kernels' psi instantiations.  iso_P / iso_tile_base keep the launch geometry of the last build (redistance_exact's cell pass reuses it).
+    std::vector<IsoIdxParams> iso_P;
+    std::vector<size_t> iso_tile_base;
+    void iso_idx_build(double iso, bool from_psi) {
         iso_idx_valid = false;
         cmp_valid = false;   // a labelling belongs to the mesh it was made of
         iso_idx_nv = iso_idx_nt = 0;
-        const int kb = slabs.front().k0, ke = slabs.back().k1;
+        const int kb = from_psi ? 0 : slabs.front().k0, ke = from_psi ? n : slabs.back().k1;
         const int ktop = std::min(ke, n - 1);   // last plane that carries vertices; cells are k in [kb, ktop)
+        const size_t nlaunch = from_psi ? 1 : slabs.size();
+        iso_P.assign(nlaunch, IsoIdxParams());
+        iso_tile_base.assign(nlaunch + 1, 0);
         if (ktop > kb) {
             if (iso_idx_n != n) {
                 d_iso_rec.release();
@@ -3182,12 +3195,12 @@ struct Solver final : SolverBase {
                 iso_idx_n = n;
             }
             const size_t plane = (size_t)n * n;
-            std::vector<IsoIdxParams> P(slabs.size());
-            std::vector<size_t> tile_base(slabs.size() + 1, 0);
-            for (size_t s = 0; s < slabs.size(); s++) {
+            std::vector<IsoIdxParams>& P = iso_P;
+            std::vector<size_t>& tile_base = iso_tile_base;
+            for (size_t s = 0; s < nlaunch; s++) {
                 IsoIdxParams& p = P[s];
-                p.n = n; p.k0 = slabs[s].k0; p.kb = kb; p.ktop = ktop;
-                p.nplanes = s + 1 < slabs.size() ? slabs[s].nzl : ktop - slabs[s].k0 + 1;
+                p.n = n; p.k0 = from_psi ? 0 : slabs[s].k0; p.kb = kb; p.ktop = ktop;
+                p.nplanes = from_psi ? ktop + 1 : (s + 1 < slabs.size() ? slabs[s].nzl : ktop - slabs[s].k0 + 1);
                 for (int a = 0; a < 3; a++) p.bbox_min[a] = bbox_min[a];
                 p.cell = cell; p.iso = iso;
                 tile_base[s + 1] = tile_base[s] + (plane * (size_t)p.nplanes + kIsoTile - 1) / kIsoTile;
@@ -3201,8 +3214,11 @@ struct Solver final : SolverBase {
             unsigned long long* off_v = d_iso_off.p;
             unsigned long long* off_t = d_iso_off.p + ntiles + 1;
             auto tiles = [&](size_t s) { return dim3((unsigned)(tile_base[s + 1] - tile_base[s])); };
-            for (size_t s = 0; s < slabs.size(); s++)
-                hipLaunchKernelGGL((iso_idx_count_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, tot_v + tile_base[s], tot_t + tile_base[s]);
+            if (from_psi)
+                hipLaunchKernelGGL((iso_idx_count_psi_kernel<T>), tiles(0), dim3(kBlock), 0, stream, P[0], (const T*)d_psi.p, tot_v, tot_t);
+            else
+                for (size_t s = 0; s < slabs.size(); s++)
+                    hipLaunchKernelGGL((iso_idx_count_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, tot_v + tile_base[s], tot_t + tile_base[s]);
             hipLaunchKernelGGL((iso_idx_scan_kernel<kIsoScanBlock>), dim3(1), dim3(kIsoScanBlock), 0, stream, ntiles, tot_v, tot_t, off_v, off_t);
             HIPCHK(hipGetLastError());
             unsigned long long total[2] = {0, 0};
@@ -3212,10 +3228,15 @@ struct Solver final : SolverBase {
             if (total[0] > 0) {
                 d_iso_V.alloc((size_t)total[0] * 3);
                 d_iso_F.alloc(std::max<size_t>(1, (size_t)total[1] * 3));
-                for (size_t s = 0; s < slabs.size(); s++)
-                    hipLaunchKernelGGL((iso_idx_verts_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, off_v + tile_base[s], d_iso_rec.p, d_iso_V.p);
-                for (size_t s = 0; s < slabs.size(); s++)   // after every slab's records: a slab's top layer reads the next slab's
-                    hipLaunchKernelGGL((iso_idx_tris_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, off_t + tile_base[s], d_iso_rec.p, d_iso_F.p);
+                if (from_psi) {
+                    hipLaunchKernelGGL((iso_idx_verts_psi_kernel<T>), tiles(0), dim3(kBlock), 0, stream, P[0], (const T*)d_psi.p, off_v, d_iso_rec.p, d_iso_V.p);
+                    hipLaunchKernelGGL((iso_idx_tris_psi_kernel<T>), tiles(0), dim3(kBlock), 0, stream, P[0], (const T*)d_psi.p, off_t, d_iso_rec.p, d_iso_F.p);
+                } else {
+                    for (size_t s = 0; s < slabs.size(); s++)
+                        hipLaunchKernelGGL((iso_idx_verts_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, off_v + tile_base[s], d_iso_rec.p, d_iso_V.p);
+                    for (size_t s = 0; s < slabs.size(); s++)   // after every slab's records: a slab's top layer reads the next slab's
+                        hipLaunchKernelGGL((iso_idx_tris_kernel<T>), tiles(s), dim3(kBlock), 0, stream, P[s], slabs[s].q.p, off_t + tile_base[s], d_iso_rec.p, d_iso_F.p);
+                }
                 HIPCHK(hipGetLastError());
                 HIPCHK(hipStreamSynchronize(stream));
             }
@@ -3223,6 +3244,20 @@ struct Solver final : SolverBase {
             iso_idx_nt = (int64_t)total[1];
         }
         iso_idx_valid = true;
+    }
+    // The indexed mesh of the resident psi at an offset (shm_grid_isosurface_indexed_psi): it replaces the resident indexed mesh.
+    void isosurface_indexed_psi(double distance, int64_t* nv_out, int64_t* nt_out) override {
+        const char* who = "isosurface_indexed_psi";
+        if (!(distance - distance == 0.)) throw Error(SHM_ERR_INVALID, fmt("%s: the distance is not finite", who));
+        need_problem();
+        if (cfg.world != 1) throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: psi exists on single-process handles only", who));
+        if (!redist_valid || !have_phi)
+            throw Error(SHM_ERR_STATE, fmt("%s: no psi of the resident phi (neither shm_grid_redistance nor shm_grid_redistance_exact has run since phi was last replaced)", who));
+        if (!(fabs(distance) + cell <= redist_band))
+            throw Error(SHM_ERR_INVALID, fmt("%s: |distance| + cell = %.17g exceeds the band %.17g psi was computed with: an edge cut there could have a clamped end", who,
+                                             fabs(distance) + cell, redist_band));
+        HIPCHK(hipSetDevice(cfg.device));
+        iso_idx_build(distance, true);
         if (nv_out) *nv_out = iso_idx_nv;
         if (nt_out) *nt_out = iso_idx_nt;
     }
@@ -3561,6 +3596,7 @@ struct Solver final : SolverBase {
     DevArray<unsigned long long> d_rd_cnt;
     std::unique_ptr<Event> rd_ev[2];
     bool redist_valid = false;
+    double redist_band = 0.;   // the band of the psi in d_psi, from whichever redistance call ran last
 
     void redistance(double iso, double band, shm_redistance_stats* out) override {
         if (!(iso - iso == 0.)) throw Error(SHM_ERR_INVALID, "redistance: the isovalue is not finite");
@@ -3625,6 +3661,7 @@ struct Solver final : SolverBase {
         HIPCHK(hipMemcpyAsync(c, d_rd_cnt.p, sizeof c, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         redist_valid = true;
+        redist_band = band;
         if (out) {
             memset(out, 0, sizeof *out);
             out->n_frozen = (int64_t)c[kRdFrozen];
@@ -3665,6 +3702,88 @@ struct Solver final : SolverBase {
         check_device_buffer(d_out, N * sizeof(T), "the psi buffer", who, "the n^3 nodes of the grid");
         HIPCHK(hipMemcpyAsync(d_out, d_psi.p, N * sizeof(T), hipMemcpyDeviceToDevice, stream));
         HIPCHK(hipStreamSynchronize(stream));
+    }
+
+    // ---- exact narrow-band distance to the indexed mesh (shm_redistance_exact.hip.h) -----------------------------------------------------------------------------
+    // psi lands in d_psi, the slot of shm_grid_redistance: the getters serve whichever call ran last.  Working memory beside it: one int64 per triangle (the
+    // cell it came from) and the counters.  The indexed mesh is rebuilt at the isovalue and left resident and unfiltered: a documented side effect.
+    DevArray<int64_t> d_rdx_cell;
+    DevArray<unsigned long long> d_rdx_cnt;
+    std::unique_ptr<Event> rdx_ev[4];
+
+    void redistance_exact(double iso, double band, shm_redistance_exact_stats* out) override {
+        const char* who = "redistance_exact";
+        if (!(iso - iso == 0.)) throw Error(SHM_ERR_INVALID, fmt("%s: the isovalue is not finite", who));
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        if (cfg.world != 1)
+            throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: a distance crosses the planes of other ranks (gather phi, or use a single-process handle)", who));
+        if (!(band > 0.) || !(band <= kRdxMaxBandCells * cell))
+            throw Error(SHM_ERR_INVALID, fmt("%s: the band must be finite, positive and at most %d cells (the work grows with (band / cell)^3 per surface cell)", who, kRdxMaxBandCells));
+        HIPCHK(hipSetDevice(cfg.device));
+        redist_valid = false;
+        for (auto& e : rdx_ev)
+            if (!e) e.reset(new Event());
+        rdx_ev[0]->record(stream);
+        halo_exchange(ARR_Q);
+        iso_idx_build(iso, false);   // M: the mesh shm_grid_isosurface_indexed(iso) builds
+        const int64_t nv = iso_idx_nv, nt = iso_idx_nt;
+        RdxParams P;
+        P.n = n;
+        P.r = (int)std::ceil(band / cell);
+        P.nslabs = (int)slabs.size();
+        for (int a = 0; a < 3; a++) P.bbox_min[a] = bbox_min[a];
+        P.cell = cell;
+        P.iso = iso;
+        P.band = band;
+        P.cull2 = band * band * (1. + 0x1p-18) / (cell * cell);
+        const size_t N = (size_t)n * n * n;
+        std::vector<RaySlab<T>> tab(slabs.size());
+        for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
+        d_rd_slabs.upload(tab, stream);
+        d_psi.alloc(N);
+        d_rdx_cnt.alloc(kRdxCounters);
+        HIPCHK(hipMemsetAsync(d_rdx_cnt.p, 0, kRdxCounters * sizeof(unsigned long long), stream));
+        hipLaunchKernelGGL((rdx_init_kernel<T>), dim3(grid_for(N, 16384)), dim3(kBlock), 0, stream, N, d_psi.p);
+        rdx_ev[1]->record(stream);
+        // timing knobs of tools/redistance_exact_bench.py (psi is wrong under either): everything but the scatter pass; the scatter pass without its atomics
+        static const bool skip_scatter = knob("SHM_RDX_NO_SCATTER") != nullptr, no_atomic = knob("SHM_RDX_NO_ATOMIC") != nullptr;
+        if (nt > 0) {
+            d_rdx_cell.alloc((size_t)nt);
+            const unsigned long long* off_t = d_iso_off.p + iso_tile_base.back() + 1;
+            for (size_t s = 0; s < slabs.size(); s++)
+                hipLaunchKernelGGL((rdx_cells_kernel<T>), dim3((unsigned)(iso_tile_base[s + 1] - iso_tile_base[s])), dim3(kBlock), 0, stream, iso_P[s], slabs[s].q.p,
+                                   off_t + iso_tile_base[s], d_rdx_cell.p);
+            const dim3 sgrid(grid_for((size_t)nt * (kWave / 2), 8 * num_cus));
+            if (no_atomic)
+                hipLaunchKernelGGL((rdx_scatter_kernel<T, false>), sgrid, dim3(kBlock), 0, stream, P, nt, d_iso_V.p, d_iso_F.p, d_rdx_cell.p,
+                                   (typename RdxWord<T>::type*)d_psi.p, d_rdx_cnt.p);
+            else if (!skip_scatter)
+                hipLaunchKernelGGL((rdx_scatter_kernel<T, true>), sgrid, dim3(kBlock), 0, stream, P, nt, d_iso_V.p, d_iso_F.p, d_rdx_cell.p,
+                                   (typename RdxWord<T>::type*)d_psi.p, d_rdx_cnt.p);
+        }
+        rdx_ev[2]->record(stream);
+        hipLaunchKernelGGL((rdx_final_kernel<T>), dim3(grid_for((size_t)n * n * kBlock, 16384)), dim3(kBlock), 0, stream, P, d_rd_slabs.p, d_psi.p, d_rdx_cnt.p);
+        HIPCHK(hipGetLastError());
+        rdx_ev[3]->record(stream);
+        unsigned long long c[kRdxCounters] = {};
+        HIPCHK(hipMemcpyAsync(c, d_rdx_cnt.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        redist_valid = true;
+        redist_band = band;
+        log("[shm] redistance_exact: %lld triangles, %llu candidate pairs; scatter %.3f of %.3f ms", (long long)nt, c[kRdxPairs], elapsed(*rdx_ev[1], *rdx_ev[2]),
+            elapsed(*rdx_ev[0], *rdx_ev[3]));
+        if (out) {
+            memset(out, 0, sizeof *out);
+            out->n_vertices = nv;
+            out->n_triangles = nt;
+            out->n_reached = (int64_t)c[kRdxReached];
+            out->n_candidate_pairs = (int64_t)c[kRdxPairs];
+            memcpy(&out->max_abs, &c[kRdxMaxBits], sizeof(double));
+            out->isovalue = iso;
+            out->band = band;
+            out->ms = elapsed(*rdx_ev[0], *rdx_ev[3]);
+        }
     }
 
     // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------

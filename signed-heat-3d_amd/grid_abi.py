@@ -23,7 +23,8 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
-               "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
+               "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
+               "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
 class ShmError(RuntimeError):
@@ -80,6 +81,15 @@ class ShmRedistanceStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class ShmRedistanceExactStats(C.Structure):
+    """shm_redistance_exact_stats of include/shm_grid.h (shm_grid_redistance_exact)."""
+    _fields_ = [("n_vertices", C.c_int64), ("n_triangles", C.c_int64), ("n_reached", C.c_int64), ("n_candidate_pairs", C.c_int64), ("max_abs", C.c_double),
+                ("isovalue", C.c_double), ("band", C.c_double), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class ShmIsoComponent(C.Structure):
@@ -171,6 +181,9 @@ def load_library():
         lib.shm_grid_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(ShmRedistanceStats)]
         lib.shm_grid_get_redistanced.argtypes = [C.c_void_p, C.c_void_p]
         lib.shm_grid_get_redistanced_device.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(lib, "shm_grid_redistance_exact"):   # added within ABI 5: found by symbol
+        lib.shm_grid_redistance_exact.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(ShmRedistanceExactStats)]
+        lib.shm_grid_isosurface_indexed_psi.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -246,7 +259,7 @@ class GridSolver:
         rc = self._lib.shm_grid_create(C.byref(cfg), C.byref(self._h))
         if rc != 0:
             raise ShmError(rc, self._lib.shm_grid_last_error(None).decode())
-        self.n = 0
+        self.n, self.cell = 0, 0.0
         self.world, self.rank, self.local_slabs = world, rank, local_slabs
         self.device, self.precision = device, precision
         self._keep = None
@@ -275,7 +288,7 @@ class GridSolver:
         g = _Grid(int(n), (C.c_double * 3)(*[float(v) for v in bbox_min]), float(cell))
         self._keep = (pos, wnormal, area)
         self._chk(self._lib.shm_grid_set_problem(self._h, C.byref(src), C.byref(g)))
-        self.n, self.S = int(n), S
+        self.n, self.S, self.cell = int(n), S, float(cell)
 
     def owned_planes(self):
         """z-planes [k0, k1) this handle owns under the slab plan in force (shm_grid_owned_planes: the weighted plan is not the equal-plane one)."""
@@ -527,6 +540,31 @@ class GridSolver:
         st = ShmRedistanceStats()
         self._chk(self._lib.shm_grid_redistance(self._h, float(isovalue), float(band), C.byref(st)))
         return st.as_dict()
+
+    def redistance_exact(self, isovalue=0.0, band=None):
+        """The exact narrow-band distance on the device (shm_grid_redistance_exact): psi = the signed Euclidean distance from every node to the indexed
+        marching-cubes mesh of the resident phi at isovalue where it is below band (length units; at most 16 cells, the default 4 cells), +-band elsewhere.
+        Side effect: the resident indexed mesh becomes that of isovalue, unfiltered.  psi replaces redistance()'s in the resident slot (get_redistanced
+        fetches it).  Returns shm_redistance_exact_stats as a dict."""
+        if not hasattr(self._lib, "shm_grid_redistance_exact"):
+            raise RuntimeError("redistance_exact: this build of libshm_grid.so does not export shm_grid_redistance_exact")
+        st = ShmRedistanceExactStats()
+        if band is None:
+            band = 4.0 * self.cell
+        self._chk(self._lib.shm_grid_redistance_exact(self._h, float(isovalue), float(band), C.byref(st)))
+        return st.as_dict()
+
+    def isosurface_indexed_psi(self, distance, device=False, keep_largest=None, min_triangles=None):
+        """The offset surface psi = distance of the resident psi (from redistance or redistance_exact), contoured on the device like isosurface_indexed
+        (shm_grid_isosurface_indexed_psi): same order, same return values, same filters.  |distance| + cell <= band of the psi must hold.  The mesh
+        replaces the resident indexed mesh."""
+        if not hasattr(self._lib, "shm_grid_isosurface_indexed_psi"):
+            raise RuntimeError("isosurface_indexed_psi: this build of libshm_grid.so does not export shm_grid_isosurface_indexed_psi")
+        nv, nt = C.c_int64(), C.c_int64()
+        self._chk(self._lib.shm_grid_isosurface_indexed_psi(self._h, float(distance), C.byref(nv), C.byref(nt)))
+        if keep_largest is not None or min_triangles is not None:
+            nv.value, nt.value = self.isosurface_keep(largest_components_mask(self.isosurface_components(), keep_largest, min_triangles))
+        return self.get_isosurface_indexed(nv.value, nt.value, device)
 
     def get_redistanced(self, device=False):
         """psi of the last redistance(): [n^3] float64 in get_phi's node order, or with device=True a torch tensor of the handle's dtype on its device,

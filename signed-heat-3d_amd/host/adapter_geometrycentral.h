@@ -147,6 +147,29 @@ class SignedHeatGridSolver {
         return psi;
     }
 
+    // The exact narrow-band distance (shm_grid_redistance_exact): psi = the signed Euclidean distance to the marching-cubes surface of the last computeDistance()'s
+    // phi at isoval where it is below band (a length, at most 16 cells), +-band elsewhere.  The device's indexed mesh becomes that of isoval.
+    Vector<double> redistanceExact(double isoval, double band, shm_redistance_exact_stats* stats = nullptr) {
+        if (!handle) throw std::runtime_error("redistanceExact: computeDistance has not been called");
+        if (shm_grid_redistance_exact(handle, isoval, band, stats) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        Vector<double> psi(nx * ny * nz);
+        if (shm_grid_get_redistanced(handle, psi.data()) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        return psi;
+    }
+    // The offset surface psi = distance of the last redistance() / redistanceExact(), in isosurfaceIndexed's canonical order (shm_grid_isosurface_indexed_psi).
+    void isosurfaceIndexedOffset(double distance, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces) {
+        if (!handle) throw std::runtime_error("isosurfaceIndexedOffset: computeDistance has not been called");
+        int64_t nv = 0, nt = 0;
+        if (shm_grid_isosurface_indexed_psi(handle, distance, &nv, &nt) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        std::vector<double> v((size_t)3 * nv);
+        std::vector<int64_t> f((size_t)3 * nt);
+        if (shm_grid_get_isosurface_indexed(handle, nv ? v.data() : nullptr, nt ? f.data() : nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
+        vertices.resize((size_t)nv);
+        faces.resize((size_t)nt);
+        for (int64_t a = 0; a < nv; a++) vertices[(size_t)a] = Vector3{v[3 * a], v[3 * a + 1], v[3 * a + 2]};
+        for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
+    }
+
   private:
     shm_solver* handle = nullptr;
     bool gridBuilt = false;

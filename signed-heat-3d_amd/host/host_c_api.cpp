@@ -222,6 +222,34 @@ int shmh_redistance(void* hv, double isoval, double band, double* psi_out, shm_r
     });
 }
 
+// redistanceExact through the C++ class: the exact narrow-band psi -> psi_out [n^3]; stats may be NULL.
+int shmh_redistance_exact(void* hv, double isoval, double band, double* psi_out, shm_redistance_exact_stats* stats) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        const VectorXd psi = h->solver.redistanceExact(isoval, band, stats);
+        std::memcpy(psi_out, psi.data(), psi.size() * sizeof(double));
+    });
+}
+
+// isosurfaceIndexedOffset through the C++ class, in shmh_isosurface_indexed's two calls (keep_largest / min_triangles < 0: no bound).
+int shmh_isosurface_indexed_offset(void* hv, double distance, int64_t keep_largest, int64_t min_triangles, int64_t* nv, int64_t* nt, double* vertices,
+                                   int64_t* triangles) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> v;
+        std::vector<std::array<size_t, 3>> f;
+        h->solver.isosurfaceIndexedOffset(distance, v, f, keep_largest, min_triangles);
+        if (nv) *nv = (int64_t)v.size();
+        if (nt) *nt = (int64_t)f.size();
+        if (vertices)
+            for (size_t a = 0; a < v.size(); a++)
+                for (int b = 0; b < 3; b++) vertices[3 * a + b] = v[a][b];
+        if (triangles)
+            for (size_t a = 0; a < f.size(); a++)
+                for (int b = 0; b < 3; b++) triangles[3 * a + b] = (int64_t)f[a][(size_t)b];
+    });
+}
+
 // isosurfaceIndexed through the C++ class, in two calls: vertices == NULL builds the mesh of the last compute_distance and returns the counts; with
 // buffers ([3 nv] doubles, [3 nt] int64) it builds again -- the canonical order makes the second mesh the first -- and copies it out.
 int shmh_isosurface_indexed(void* hv, double isoval, int64_t* nv, int64_t* nt, double* vertices, int64_t* triangles) {

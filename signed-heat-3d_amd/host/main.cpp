@@ -39,13 +39,16 @@ static void usage() {
                  "      --rays-iso <v>    The level the rays are cast against (default 0; independent of --iso)\n"
                  "      --redistance      Redistance phi on the device to a signed distance to its level set --iso (|grad psi| = 1, first-order upwind)\n"
                  "      --band <B>        Width of the band the redistancing fills, a length; nodes beyond it hold +-B (default: the whole grid)\n"
+                 "      --redistance-exact Instead of --redistance: psi = the exact distance to the marching-cubes surface at --iso inside --band (required, at most 16 cells)\n"
+                 "      --offset <D>      With --iso-indexed and a redistance flag: export the offset surface psi = D instead of phi = --iso (|D| + cell <= --band)\n"
                  "      --out-psi <file>  Raw float64 psi at the grid nodes, in the order of --out\n";
 }
 
 int main(int argc, char** argv) {
     std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut;
     double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
-    bool redistance = false;
+    bool redistance = false, redistanceExact = false, haveOffset = false;
+    double offset = 0.;
     long long auditCount = -1, keepLargest = -1, minTriangles = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
@@ -83,6 +86,8 @@ int main(int argc, char** argv) {
         else if (s == "--rays-out") raysOut = need("--rays-out");
         else if (s == "--rays-iso") raysIso = atof(need("--rays-iso"));
         else if (s == "--redistance") redistance = true;
+        else if (s == "--redistance-exact") redistanceExact = true;
+        else if (s == "--offset") { offset = atof(need("--offset")); haveOffset = true; }
         else if (s == "--band") band = atof(need("--band"));
         else if (s == "--out-psi") psiOut = need("--out-psi");
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
@@ -96,8 +101,20 @@ int main(int argc, char** argv) {
         std::cerr << "--rays and --rays-out go together." << std::endl;
         return EXIT_FAILURE;
     }
-    if (redistance != !psiOut.empty()) {
-        std::cerr << "--redistance and --out-psi go together." << std::endl;
+    if (redistance && redistanceExact) {
+        std::cerr << "--redistance and --redistance-exact exclude each other." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if ((redistance || redistanceExact) != !psiOut.empty()) {
+        std::cerr << "--redistance / --redistance-exact and --out-psi go together." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (redistanceExact && !(band < std::numeric_limits<double>::infinity())) {
+        std::cerr << "--redistance-exact needs a finite --band." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (haveOffset && (!isoIndexed || !(redistance || redistanceExact))) {
+        std::cerr << "--offset contours the psi of --redistance / --redistance-exact and needs --iso-indexed." << std::endl;
         return EXIT_FAILURE;
     }
     if (backend.exactStep1 && backend.referenceStep1) {
@@ -147,12 +164,30 @@ int main(int argc, char** argv) {
             f.write((const char*)phi.data(), (std::streamsize)(phi.size() * sizeof(double)));
             std::cerr << "phi (" << solver.gridSize() << "^3 float64) written to " << out << std::endl;
         }
+        if (redistance) {
+            shm_redistance_stats rs{};
+            const VectorXd psi = solver.redistance(isoval, band, &rs);
+            std::ofstream o(psiOut, std::ios::binary);
+            o.write((const char*)psi.data(), (std::streamsize)(psi.size() * sizeof(double)));
+            std::cerr << "phi redistanced to its level set " << isoval << ": " << rs.n_frozen << " frozen nodes, " << rs.n_reached << " reached, max |psi| " << rs.max_abs
+                      << ", " << rs.n_rounds << " rounds, " << rs.n_block_updates << " block updates, " << rs.ms << " ms; psi written to " << psiOut << std::endl;
+        }
+        if (redistanceExact) {
+            shm_redistance_exact_stats rs{};
+            const VectorXd psi = solver.redistanceExact(isoval, band, &rs);
+            std::ofstream o(psiOut, std::ios::binary);
+            o.write((const char*)psi.data(), (std::streamsize)(psi.size() * sizeof(double)));
+            std::cerr << "exact distance to the surface phi = " << isoval << " (" << rs.n_vertices << " vertices, " << rs.n_triangles << " triangles) within " << band << ": "
+                      << rs.n_reached << " reached, max |psi| " << rs.max_abs << ", " << rs.n_candidate_pairs << " candidate pairs, " << rs.ms << " ms; psi written to "
+                      << psiOut << std::endl;
+        }
         if (!exportPath.empty()) {
             std::vector<Vector3> iv;
             std::vector<std::array<size_t, 3>> jf;
-            if (isoIndexed && (keepLargest >= 0 || minTriangles >= 0)) {
+            if (isoIndexed && (haveOffset || keepLargest >= 0 || minTriangles >= 0)) {
                 std::vector<shm_iso_component> comps;
-                solver.isosurfaceIndexed(isoval, iv, jf, keepLargest, minTriangles, &comps);
+                if (haveOffset) solver.isosurfaceIndexedOffset(offset, iv, jf, keepLargest, minTriangles, &comps);
+                else solver.isosurfaceIndexed(isoval, iv, jf, keepLargest, minTriangles, &comps);
                 for (size_t c = 0; c < comps.size(); c++) {
                     char line[256];
                     snprintf(line, sizeof line, "component %zu: first_vertex %lld nv %lld nt %lld area %.9g volume %.9g touches_box %d", c, (long long)comps[c].first_vertex,
@@ -162,7 +197,7 @@ int main(int argc, char** argv) {
             } else if (isoIndexed) solver.isosurfaceIndexed(isoval, iv, jf);
             else solver.isosurface(isoval, iv, jf);
             writeSurfaceMesh(iv, jf, exportPath);
-            std::cerr << "Isosurface written to " << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
+            std::cerr << (haveOffset ? "Offset surface written to " : "Isosurface written to ") << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
         }
         if (!queryPath.empty()) {
             std::ifstream f(queryPath, std::ios::binary | std::ios::ate);
@@ -210,14 +245,6 @@ int main(int argc, char** argv) {
             std::ofstream o(raysOut, std::ios::binary);
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
             std::cerr << ro.size() << " rays cast against phi = " << raysIso << ": " << hits << " hits, t and gradient written to " << raysOut << std::endl;
-        }
-        if (redistance) {
-            shm_redistance_stats rs{};
-            const VectorXd psi = solver.redistance(isoval, band, &rs);
-            std::ofstream o(psiOut, std::ios::binary);
-            o.write((const char*)psi.data(), (std::streamsize)(psi.size() * sizeof(double)));
-            std::cerr << "phi redistanced to its level set " << isoval << ": " << rs.n_frozen << " frozen nodes, " << rs.n_reached << " reached, max |psi| " << rs.max_abs
-                      << ", " << rs.n_rounds << " rounds, " << rs.n_block_updates << " block updates, " << rs.ms << " ms; psi written to " << psiOut << std::endl;
         }
     } catch (const std::exception& e) {
         std::cerr << "error: " << e.what() << std::endl;

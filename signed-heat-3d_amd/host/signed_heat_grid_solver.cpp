@@ -139,6 +139,12 @@ void SignedHeatGridSolver::isosurfaceIndexed(double isoval, std::vector<Vector3>
     int64_t nv = 0, nt = 0;
     if (shm_grid_isosurface_indexed(handle, isoval, &nv, &nt) != SHM_OK)
         throw std::runtime_error(std::string("shm_grid_isosurface_indexed: ") + shm_grid_last_error(handle));
+    keepLargestComponents(keepLargest, minTriangles, nv, nt, components);
+    fetchIndexed(nv, nt, vertices, faces);
+}
+
+// "keep the shell, drop the floaters" on the device's resident indexed mesh: labels it, keeps the chosen components and returns the counts of what is left.
+void SignedHeatGridSolver::keepLargestComponents(int64_t keepLargest, int64_t minTriangles, int64_t& nv, int64_t& nt, std::vector<shm_iso_component>* components) {
     const std::vector<shm_iso_component> comps = isosurfaceComponents();
     std::vector<size_t> order;
     for (size_t c = 0; c < comps.size(); c++)
@@ -150,8 +156,17 @@ void SignedHeatGridSolver::isosurfaceIndexed(double isoval, std::vector<Vector3>
     for (size_t c : order) keep[c] = 1;
     if (shm_grid_isosurface_keep_components(handle, keep.empty() ? nullptr : keep.data(), &nv, &nt) != SHM_OK)
         throw std::runtime_error(std::string("shm_grid_isosurface_keep_components: ") + shm_grid_last_error(handle));
-    fetchIndexed(nv, nt, vertices, faces);
     if (components) *components = comps;
+}
+
+void SignedHeatGridSolver::isosurfaceIndexedOffset(double distance, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces, int64_t keepLargest,
+                                                   int64_t minTriangles, std::vector<shm_iso_component>* components) {
+    if (!handle) throw std::runtime_error("isosurfaceIndexedOffset: computeDistance has not been called");
+    int64_t nv = 0, nt = 0;
+    if (shm_grid_isosurface_indexed_psi(handle, distance, &nv, &nt) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_isosurface_indexed_psi: ") + shm_grid_last_error(handle));
+    if (keepLargest >= 0 || minTriangles >= 0) keepLargestComponents(keepLargest, minTriangles, nv, nt, components);
+    fetchIndexed(nv, nt, vertices, faces);
 }
 
 shm_step1_audit SignedHeatGridSolver::auditStep1(size_t count, uint64_t seed) {
@@ -203,6 +218,15 @@ std::vector<double> SignedHeatGridSolver::castRays(const std::vector<Vector3>& o
 VectorXd SignedHeatGridSolver::redistance(double isoval, double band, shm_redistance_stats* stats) {
     if (!handle) throw std::runtime_error("redistance: computeDistance has not been called");
     if (shm_grid_redistance(handle, isoval, band, stats) != SHM_OK) throw std::runtime_error(std::string("shm_grid_redistance: ") + shm_grid_last_error(handle));
+    VectorXd psi(nx * ny * nz);
+    if (shm_grid_get_redistanced(handle, psi.data()) != SHM_OK) throw std::runtime_error(std::string("shm_grid_get_redistanced: ") + shm_grid_last_error(handle));
+    return psi;
+}
+
+VectorXd SignedHeatGridSolver::redistanceExact(double isoval, double band, shm_redistance_exact_stats* stats) {
+    if (!handle) throw std::runtime_error("redistanceExact: computeDistance has not been called");
+    if (shm_grid_redistance_exact(handle, isoval, band, stats) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_redistance_exact: ") + shm_grid_last_error(handle));
     VectorXd psi(nx * ny * nz);
     if (shm_grid_get_redistanced(handle, psi.data()) != SHM_OK) throw std::runtime_error(std::string("shm_grid_get_redistanced: ") + shm_grid_last_error(handle));
     return psi;

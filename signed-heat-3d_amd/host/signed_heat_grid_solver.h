@@ -70,6 +70,15 @@ class SignedHeatGridSolver {
     // the grid nodes, in computeDistance's node order; stats (optional) receives the call's counts.  What the contour slider's offset surfaces
     // (src/main.cpp:160-166) assume phi to be.  phi itself is left as it was: extract surfaces from phi, read distances from psi.
     VectorXd redistance(double isoval = 0., double band = std::numeric_limits<double>::infinity(), shm_redistance_stats* stats = nullptr);
+    // The exact narrow-band distance (shm_grid_redistance_exact; contract in include/shm_grid.h): psi = the signed Euclidean distance from every node to the
+    // marching-cubes surface of the LAST computeDistance()'s phi at isoval where it is below band (a length, at most 16 cells), +-band elsewhere.  Second-order
+    // accurate inside the band, where redistance() is first-order.  Side effect: the device's indexed mesh becomes that of isoval, unfiltered.
+    VectorXd redistanceExact(double isoval, double band, shm_redistance_exact_stats* stats = nullptr);
+    // The offset surface psi = distance of the psi of the last redistance() / redistanceExact(), contoured on the device in isosurfaceIndexed's canonical order
+    // (shm_grid_isosurface_indexed_psi; |distance| + cell <= band of that psi).  keepLargest / minTriangles (< 0: no bound) filter its components as the
+    // isosurfaceIndexed overload does.
+    void isosurfaceIndexedOffset(double distance, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces, int64_t keepLargest = -1,
+                                 int64_t minTriangles = -1, std::vector<shm_iso_component>* components = nullptr);
 
     // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
     // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).
@@ -99,6 +108,7 @@ class SignedHeatGridSolver {
     shm_stats stats{};
 
     void ensureHandle();
+    void keepLargestComponents(int64_t keepLargest, int64_t minTriangles, int64_t& nv, int64_t& nt, std::vector<shm_iso_component>* components);
     void fetchIndexed(int64_t nv, int64_t nt, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces);
     void buildGrid(const Vector3& c, double r, const SignedHeat3DOptions& options);
     VectorXd solveOnDevice(bool scrub, const SignedHeat3DOptions& options);

@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .grid_abi import ISO_COMPONENT_DTYPE, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
+from .grid_abi import ISO_COMPONENT_DTYPE, ShmRedistanceExactStats, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -43,6 +43,9 @@ def load_host_library():
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
+    if hasattr(lib, "shmh_redistance_exact"):
+        lib.shmh_redistance_exact.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceExactStats)]
+        lib.shmh_isosurface_indexed_offset.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_isosurface_components.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.c_void_p]
     lib.shmh_isosurface_indexed_filtered.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
@@ -151,6 +154,25 @@ class HostSolver:
         st = ShmRedistanceStats()
         self._chk(self._lib.shmh_redistance(self._h, float(isovalue), float(band), psi.ctypes.data, C.byref(st)))
         return psi, st.as_dict()
+
+    def redistance_exact(self, isovalue, band):
+        """redistanceExact of the C++ mirror (shm_grid_redistance_exact): returns (psi [n^3] float64, stats dict)."""
+        psi = np.empty(self.grid_info()["n"] ** 3, dtype=np.float64)
+        st = ShmRedistanceExactStats()
+        self._chk(self._lib.shmh_redistance_exact(self._h, float(isovalue), float(band), psi.ctypes.data, C.byref(st)))
+        return psi, st.as_dict()
+
+    def isosurface_indexed_offset(self, distance, keep_largest=None, min_triangles=None):
+        """isosurfaceIndexedOffset of the C++ mirror (shm_grid_isosurface_indexed_psi): the offset surface psi = distance of the last redistance /
+        redistance_exact, as isosurface_indexed returns its mesh."""
+        nv, nt = C.c_int64(), C.c_int64()
+        kl, mt = -1 if keep_largest is None else int(keep_largest), -1 if min_triangles is None else int(min_triangles)
+        call = lambda *a: self._lib.shmh_isosurface_indexed_offset(self._h, float(distance), kl, mt, *a)   # noqa: E731
+        self._chk(call(C.byref(nv), C.byref(nt), None, None))
+        V = np.empty((nv.value, 3), dtype=np.float64)
+        F = np.empty((nt.value, 3), dtype=np.int64)
+        self._chk(call(None, None, V.ctypes.data, F.ctypes.data))
+        return V, F
 
     def isosurface_indexed(self, isovalue=0.0, keep_largest=None, min_triangles=None):
         """isosurfaceIndexed of the C++ mirror: the marching-cubes surface of the last compute_distance, welded and numbered on the device in the

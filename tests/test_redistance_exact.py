@@ -1,0 +1,560 @@
+"""The exact narrow-band distance to the contoured surface and the offset meshes (shm_grid_redistance_exact, shm_grid_isosurface_indexed_psi, include/shm_grid.h;
+kernels in csrc/shm_redistance_exact.hip.h and csrc/shm_iso_indexed.hip.h), through the kernels, the C ABI, the Python bindings, the C++ host mirror and the CLI.
+
+Reference: tests/redistance_exact_ref.py, the numpy restatement of the contract, fed the device's own phi (cast to the handle's precision) and the device's own
+fetched mesh -- never the code under test.  psi is held to
+    TOL = n eps_T max|psi|      (redistance_ref.tol, the project's own)
+in fp64.  In fp32 the last operation of both sides is one rounding of sqrt(d^2) to fp32, so the two agree bit for bit except where the fp64 values before the
+rounding differ in their last bits across a rounding boundary: at most a 1e-3 share of the reached nodes may differ, and then by one fp32 ulp.
+The +-band pattern (unreached nodes, empty meshes) is compared exactly.  Non-finite phi cannot be injected through the ABI: that rule is held by the restatement
+and by a CPU test of it.
+
+Run as a script (`test_redistance_exact.py worker <world> <uid hex> <case> <dir>`) this file is the worker of test_two_ranks_are_refused, as tests/test_redistance.py."""
+import ctypes as C
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+# before the library is loaded: see tests/test_sample.py
+try:
+    import torch  # noqa: F401
+except ImportError:
+    torch = None
+
+from conftest import ROOT, load_golden
+
+import components_ref as cref
+import iso_ref
+import redistance_exact_ref as ref
+import redistance_ref as ref1
+
+SHM_ERR_INVALID, SHM_ERR_STATE = 1, 7
+INF = float("inf")
+BANDS = (0.75, 2.5, 16.0)   # in cells: less than one layer, a few layers, larger than half the grid at n = 16 (every node box clipped at every face)
+
+
+def dt(precision):
+    return np.float64 if precision == 64 else np.float32
+
+
+def node_beside(phi, n, iso0=0.0):
+    """Flat index of a node beside the surface phi = iso0: the first outside node (phi >= iso0) whose +x neighbour is inside.  With the isovalue set to phi
+    at this node it stays outside, it is the lower node of a cut edge, and that edge's vertex is tt = 0: the node's own position, bit for bit."""
+    P = phi.reshape(n, n, n)
+    k, j, i = np.nonzero((P[:, :, :-1] >= iso0) & (P[:, :, 1:] < iso0))
+    return int(i[0] + n * (j[0] + n * k[0]))
+
+
+def isovalues(phi, n):
+    """0 (specks, kinks, many components); 0.25 max; above max and below min (no triangle); phi's own value at a node beside the zero surface (zero-length
+    edges, zero-area triangles); 0.6 max (the surface runs into the box, as in tests/test_iso_indexed.py)."""
+    lo, hi = float(phi.min()), float(phi.max())
+    return dict(zero=0.0, quarter_max=0.25 * hi, above=hi + 1.0, below=lo - 1.0, node=float(phi[node_beside(phi, n)]), box=0.6 * hi)
+
+
+# ---- CPU: the restatement and the pair formula ------------------------------------------------------------------------------------------------------------------
+HOST_CASES = [("bunny_small_n16", 0.0), ("bunny_small_n16", 0.25), ("bunny_small_n24", 0.0), ("bunny_small_n24", 0.25), ("polygon_bear_n16", 0.0), ("polygon_bear_n16", 0.25)]
+_HOST = {}
+
+
+def host_case(case, frac):
+    """(d, n, h, phi, iso, X) of a golden, the mesh built once per case."""
+    if (case, frac) not in _HOST:
+        d = load_golden(case)
+        n, h, phi = int(d["n"]), float(d["cell"]), np.asarray(d["phi"], dtype=np.float64)
+        iso = frac * float(phi.max())
+        _HOST[(case, frac)] = (d, n, h, phi, iso, ref.mesh(phi, n, d["bbox_min"], h, iso))
+    return _HOST[(case, frac)]
+
+
+@pytest.mark.parametrize("case,frac", [c for c in HOST_CASES if c[0].endswith("n16")])
+def test_restatement_equals_brute_force(case, frac):
+    """The culled restatement against plain brute force over all triangles, on the 16^3 goldens, at the three bands: the same bits."""
+    d, n, h, phi, iso, X = host_case(case, frac)
+    d2 = ref.brute_force_d2(X, n, d["bbox_min"], h)        # once: the bands share it
+    for b in BANDS:
+        psi, info = ref.exact_distance(X, phi, n, d["bbox_min"], h, iso, b * h)
+        brute, binfo = ref.brute_force(X, phi, n, d["bbox_min"], h, iso, b * h, d2=d2)
+        assert np.array_equal(psi, brute) and info["n_reached"] == binfo["n_reached"] > 0, (case, frac, b)
+        assert np.array_equal(psi < 0, phi < iso)
+
+
+@pytest.mark.parametrize("case,frac", HOST_CASES)
+def test_pair_distance_fp64_against_longdouble(case, frac):
+    """The formula in fp64 against the same formula in np.longdouble: over the nodes with a cut edge, each against the triangles of its incident cells' mesh
+    (every triangle within 2 cells), and over all nodes against brute force on the 16^3 cases.  Measured: <= 3.3e-16 h and <= 3.3e-15 h; asserted <= TOL / 4."""
+    d, n, h, phi, iso, X = host_case(case, frac)
+    P = phi.reshape(n, n, n) < iso
+    cut = np.zeros((n, n, n), dtype=bool)
+    for ax in range(3):
+        a = [slice(None)] * 3
+        b = [slice(None)] * 3
+        a[ax], b[ax] = slice(None, -1), slice(1, None)
+        c = P[tuple(a)] != P[tuple(b)]
+        cut[tuple(a)] |= c
+        cut[tuple(b)] |= c
+    kk, jj, ii = np.nonzero(cut)
+    axes = ref.node_positions(n, d["bbox_min"], h)
+    pos = np.stack([axes[0][ii], axes[1][jj], axes[2][kk]], axis=-1)
+    # the (node, triangle) pairs within two cells of each other, evaluated as pairs in both arithmetics; every cut-edge node has at least one
+    ctr = X.mean(axis=1)
+    ni, ti = [], []
+    for a in range(0, len(pos), 512):
+        u, v = np.nonzero(np.abs(ctr[None, :, :] - pos[a:a + 512, None, :]).max(axis=2) <= 2.0 * h)
+        ni.append(u + a)
+        ti.append(v)
+    ni, ti = np.concatenate(ni), np.concatenate(ti)
+    assert np.unique(ni).size == len(pos)
+    rel = X[ti] - pos[ni][:, None, :]
+    d64 = np.full(len(pos), np.inf)
+    np.minimum.at(d64, ni, ref.tri_dist2(rel[:, 0], rel[:, 1], rel[:, 2]))
+    rl = rel.astype(np.longdouble)
+    d80 = np.full(len(pos), np.inf, dtype=np.longdouble)
+    np.minimum.at(d80, ni, ref.tri_dist2(rl[:, 0], rl[:, 1], rl[:, 2]))
+    worst = float(np.abs(np.sqrt(d64) - np.sqrt(d80).astype(np.float64)).max())
+    psi, info = ref.exact_distance(X, phi, n, d["bbox_min"], h, iso, 16 * h)
+    lim = ref1.tol(n, np.float64, psi) / 4
+    print("%s iso %.3g: %d cut-edge nodes, %d pairs, fp64 against longdouble %.3e h (TOL/4 = %.3e h)" % (case, iso, len(pos), len(ni), worst / h, lim / h))
+    assert worst <= lim
+    if n == 16:
+        # every third node of the grid against ALL triangles in longdouble: the culled fp64 restatement loses nothing to its cull or to its arithmetic
+        nodes = np.arange(0, n ** 3, 3)
+        u80 = np.sqrt(ref.brute_force_d2(X, n, d["bbox_min"], h, work=np.longdouble, nodes=nodes)).astype(np.float64)
+        sel = info["reached"][nodes]
+        err = float(np.abs(info["u"][nodes] - u80)[sel].max())
+        print("%s iso %.3g: %d nodes, culled fp64 against brute-force longdouble %.3e h" % (case, iso, int(sel.sum()), err / h))
+        assert sel.any() and err <= lim
+
+
+def test_degenerate_triangles():
+    """The isovalue set to phi's own value at a node beside the surface: zero-length edges, zero-area triangles.  Every psi is finite, that node reads +0, and
+    the result equals brute force to TOL."""
+    d = load_golden("bunny_small_n16")
+    n, h, phi = int(d["n"]), float(d["cell"]), np.asarray(d["phi"], dtype=np.float64)
+    g = node_beside(phi, n)
+    iso = float(phi[g])
+    X = ref.mesh(phi, n, d["bbox_min"], h, iso)
+    area2 = (np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]) ** 2).sum(axis=1)
+    assert (area2 == 0).any() and (area2 > 0).any()
+    psi, info = ref.exact_distance(X, phi, n, d["bbox_min"], h, iso, 4 * h)
+    brute, _ = ref.brute_force(X, phi, n, d["bbox_min"], h, iso, 4 * h)
+    assert np.isfinite(psi).all() and psi[g] == 0.0 and not np.signbit(psi[g])
+    assert float(np.abs(psi - brute).max()) <= ref1.tol(n, np.float64, psi)
+
+
+def _sphere(n, R):
+    h = 2.0 / (n - 1)
+    bb = np.array([-1.0, -1.0, -1.0])
+    ctr = (0.0131, -0.0212, 0.0173)   # not on a node
+    x = np.arange(n) * h + bb[0]
+    r2 = (x[None, None, :] - ctr[0]) ** 2 + (x[None, :, None] - ctr[1]) ** 2 + (x[:, None, None] - ctr[2]) ** 2
+    return h, bb, (r2 - R * R).reshape(-1), (np.sqrt(r2) - R).reshape(-1)
+
+
+@pytest.mark.parametrize("n,R", [(24, 0.6), (33, 0.7)])
+def test_sphere_second_order(n, R):
+    """f = r^2 - R^2, band 4 h: max |psi - (r - R)| over the band <= h^2 / (2 R) -- edge interpolation of a quadratic, h^2 / (8 R), plus the sagitta of a chord
+    of at most sqrt(3) h, 3 h^2 / (8 R).  Measured: 0.054 h against 0.072 h and 0.034 h against 0.045 h; the first-order scheme: 0.44 h and 0.24 h."""
+    h, bb, f, dist = _sphere(n, R)
+    X = ref.mesh(f, n, bb, h, 0.0)
+    psi, info = ref.exact_distance(X, f, n, bb, h, 0.0, 4 * h)
+    err = float(np.abs(psi - dist)[info["reached"]].max())
+    first, _ = ref1.redistance(f, n, h, 0.0, band=4 * h)
+    err1 = float(np.abs(first - dist)[np.abs(first) < 4 * h].max())
+    print("sphere n %d R %.1f: exact band %.4f h (bound %.4f h), first-order %.4f h" % (n, R, err / h, h / (2 * R), err1 / h))
+    assert err <= h * h / (2 * R)
+    assert err1 > err
+    assert info["n_reached"] > 0 and np.array_equal(psi < 0, f < 0)
+
+
+@pytest.mark.parametrize("case,frac", [("bunny_small_n16", 0.0), ("bunny_small_n24", 0.25)])
+def test_one_lipschitz(case, frac):
+    """|psi_p - psi_q| <= cell + TOL over every grid edge whose two ends are both reached."""
+    d, n, h, phi, iso, X = host_case(case, frac)
+    psi, info = ref.exact_distance(X, phi, n, d["bbox_min"], h, iso, 4 * h)
+    P, Rr = psi.reshape(n, n, n), info["reached"].reshape(n, n, n)
+    lim = h + ref1.tol(n, np.float64, psi)
+    for ax in range(3):
+        a = [slice(None)] * 3
+        b = [slice(None)] * 3
+        a[ax], b[ax] = slice(None, -1), slice(1, None)
+        both = Rr[tuple(a)] & Rr[tuple(b)]
+        assert both.any() and float(np.abs(P[tuple(a)] - P[tuple(b)])[both].max()) <= lim
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_clamp_empty_mesh_and_nonfinite(dtype):
+    d = load_golden("bunny_small_n16")
+    n, h = int(d["n"]), float(d["cell"])
+    phi = np.asarray(d["phi"], dtype=np.float64).astype(dtype).astype(np.float64)
+    bb = d["bbox_min"]
+    iso = 0.25 * float(phi.max())
+    X = ref.mesh(phi, n, bb, h, iso)
+    # the clamp: a smaller band is the larger band's result clipped, and reached means u < band
+    wide, _ = ref.exact_distance(X, phi, n, bb, h, iso, 6 * h, dtype)
+    B = 2.5 * h
+    Bt = float(dtype(B))
+    narrow, info = ref.exact_distance(X, phi, n, bb, h, iso, B, dtype)
+    assert np.array_equal(narrow, np.where(np.abs(wide) < B, wide, np.where(phi < iso, -Bt, Bt)))
+    assert 0 < info["n_reached"] == int((np.abs(wide) < B).sum()) < n ** 3 and info["max_abs"] < B
+    assert np.array_equal(narrow.astype(dtype).astype(np.float64), narrow)
+    # no triangle: psi = s band, nothing reached
+    for lvl, sgn in ((float(phi.max()) + 1.0, -1.0), (float(phi.min()) - 1.0, 1.0)):
+        Xe = ref.mesh(phi, n, bb, h, lvl)
+        psi, info = ref.exact_distance(Xe, phi, n, bb, h, lvl, B, dtype)
+        assert len(Xe) == 0 and info["n_reached"] == 0 and info["max_abs"] == 0.0 and (psi == sgn * Bt).all()
+    # non-finite phi: NaN at the node, and no triangle from a cell with a non-finite corner -- the same as the mesh without those cells' triangles
+    bad = phi.reshape(n, n, n).copy()
+    g = node_beside(phi, n, iso)
+    i, j, k = g % n, (g // n) % n, g // (n * n)
+    bad[k, j, i] = np.nan
+    bad[2, 3, 4] = np.inf
+    Xb = ref.mesh(bad.reshape(-1), n, bb, h, iso)
+    assert np.isfinite(Xb).all() and 0 < len(Xb) < len(X)
+    lo = np.array([i - 1, j - 1, k - 1]) * h + np.asarray(bb)
+    touched = ((X >= lo - 1e-12) & (X <= lo + 2 * h + 1e-12)).all(axis=(1, 2))     # triangles in the eight cells around the NaN node
+    assert len(X) - len(Xb) <= int(touched.sum())
+    psi, info = ref.exact_distance(Xb, bad.reshape(-1), n, bb, h, iso, B, dtype)
+    nf = ~np.isfinite(bad.reshape(-1))
+    assert np.isnan(psi[nf]).all() and np.isfinite(psi[~nf]).all() and not info["reached"][nf].any()
+
+
+# ---- GPU -------------------------------------------------------------------------------------------------------------------------------------------------------
+def need_symbols(shm):
+    """The device tests fail, not skip, on a library without the entry points."""
+    lib = shm.load_library()
+    for name in ("shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi"):
+        assert hasattr(lib, name), "libshm_grid.so does not export %s" % name
+
+
+def solved(shm, case, n, precision=64, slabs=1, **kw):
+    import test_redistance as rd
+    need_symbols(shm)
+    return rd.solved(shm, case, n, precision, slabs, **kw)
+
+
+def device_reference(s, st, d, phi, n, iso, band, precision):
+    """The restatement of the device's own phi and the device's own fetched mesh (resident after redistance_exact, whose stats carry its counts)."""
+    V, F = s.get_isosurface_indexed(st["n_vertices"], st["n_triangles"])
+    X = V[F] if len(F) else np.zeros((0, 3, 3))
+    return ref.exact_distance(X, phi, n, d["bbox_min"], float(d["cell"]), iso, band, dt(precision)), (V, F)
+
+
+def run_exact(s, iso, band):
+    return s.redistance_exact(iso, band)
+
+
+def compare(psi, want, info, precision, n, tag):
+    lim = ref1.tol(n, dt(precision), want)
+    r = info["reached"]
+    assert np.array_equal(psi[~r], want[~r]), tag       # the +-band pattern, exactly
+    diff = np.abs(psi - want)
+    if precision == 64:
+        err = float(diff.max())
+        print("%s: err %.3e TOL %.3e reached %d" % (tag, err, lim, info["n_reached"]))
+        assert err <= lim, (tag, err, lim)
+        return 0.0
+    ulp = np.spacing(np.abs(want).astype(np.float32)).astype(np.float64)
+    off = diff > 0
+    share = float(off.sum()) / max(1, int(r.sum()))
+    print("%s: %d of %d reached nodes differ (share %.2e), all by one fp32 ulp: %s" % (tag, int(off.sum()), int(r.sum()), share, bool((diff[off] <= ulp[off]).all())))
+    assert (diff[off] <= ulp[off]).all() and share <= 1e-3, (tag, share)
+    return share
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", [64, 32])
+@pytest.mark.parametrize("b", BANDS)
+@pytest.mark.parametrize("case,n", [("bunny_small", 16), ("bunny_small", 20), ("bunny_small", 33), ("polygon_bear", 16), ("bunny_pc", 24)])
+def test_parity_with_the_restatement(shm, case, n, precision, b):
+    import test_iso_indexed as iso_t
+    d, s, phi = solved(shm, case, n, precision)
+    h = float(d["cell"])
+    for name, iso in isovalues(phi, n).items():
+        band = b * h
+        st = run_exact(s, iso, band)
+        psi = s.get_redistanced()
+        (want, info), (V, F) = device_reference(s, st, d, phi, n, iso, band, precision)
+        tag = "parity %s %d fp%d %s band %.2f" % (case, n, precision, name, b)
+        compare(psi, want, info, precision, n, tag)
+        assert np.array_equal(psi < 0, phi < iso), tag
+        # the stats are the restatement's
+        lim = ref1.tol(n, dt(precision), want)
+        assert st["n_reached"] == info["n_reached"] and st["n_vertices"] == len(V) and st["n_triangles"] == len(F), (tag, st)
+        assert abs(st["max_abs"] - info["max_abs"]) <= (lim if precision == 64 else float(np.spacing(np.float32(info["max_abs"])))), (tag, st)
+        assert st["isovalue"] == iso and st["band"] == band and st["max_abs"] < band
+        assert st["n_candidate_pairs"] == ref.candidate_pairs(phi, n, h, iso, band), tag
+        if name in ("above", "below"):
+            assert st["n_triangles"] == 0 and st["n_reached"] == 0 and st["n_candidate_pairs"] == 0
+            assert (psi == float(dt(precision)(band)) * (-1.0 if name == "above" else 1.0)).all()
+        else:
+            assert st["n_triangles"] > 0 and st["n_reached"] > 0 and np.isfinite(psi).all()
+        if name == "node":
+            # the node lies on the surface: its vertex is the isosurface kernels' idx*cell + bbox_min, which the compiler may have fused into one
+            # rounding, against the unfused node position of the contract -- 0 up to one rounding of a coordinate, never negative
+            g = node_beside(phi, n)
+            assert 0.0 <= psi[g] <= 8 * 2.0 ** -53 * iso_t.bound(d) and not np.signbit(psi[g]), (tag, psi[g])
+            X = V[F]
+            assert ((np.cross(X[:, 1] - X[:, 0], X[:, 2] - X[:, 0]) ** 2).sum(axis=1) == 0).any()      # zero-area triangles really occur
+        if name == "box":
+            assert cref.boundary_edges(F) > 0                                                          # the surface really touches the box
+        if b == 16.0 and n == 16 and name not in ("above", "below"):
+            assert st["n_reached"] == n ** 3
+
+
+@pytest.mark.gpu
+def test_determinism_and_slabs(shm):
+    """Two calls give bit-identical psi and stats.  Handles with 1, 2 and 3 slabs each solve for themselves and their phi differ in the last bits (DESIGN.md
+    section 4h; tests/test_redistance.py::test_slabs), so each handle is held to the restatement of its OWN phi; n_candidate_pairs is a function of the mesh's
+    cells and the band, identical across calls, and across handles wherever their meshes cut the same cells."""
+    n = 20
+    pairs = {}
+    for slabs in (1, 2, 3):
+        d, s, phi = solved(shm, "bunny_small", n, 64, slabs, solver="primal", precond="none", tol=1e-10)
+        h = float(d["cell"])
+        base = pairs.get("phi", phi)
+        pairs.setdefault("phi", phi)
+        for name in ("zero", "quarter_max", "box"):
+            iso = isovalues(base, n)[name]     # one set of levels for the three handles
+            st = run_exact(s, iso, 2.5 * h)
+            psi = s.get_redistanced()
+            (want, info), _ = device_reference(s, st, d, phi, n, iso, 2.5 * h, 64)
+            compare(psi, want, info, 64, n, "slabs %d %s" % (slabs, name))
+            assert st["n_candidate_pairs"] == ref.candidate_pairs(phi, n, h, iso, 2.5 * h)
+            run_exact(s, 0.5 * iso + 0.1, 4 * h)   # another level and band in between: nothing of it may stay behind
+            st2 = run_exact(s, iso, 2.5 * h)
+            assert np.array_equal(s.get_redistanced(), psi)
+            st.pop("ms"), st2.pop("ms")
+            assert st2 == st
+            pairs.setdefault(name, {})[slabs] = (st["n_candidate_pairs"], st["n_triangles"])
+    for name in ("zero", "quarter_max", "box"):
+        print("candidate pairs %s: %s" % (name, pairs[name]))
+        assert pairs[name][1] == pairs[name][2] == pairs[name][3]
+
+
+@pytest.mark.gpu
+def test_state_and_errors(shm):
+    import test_iso_indexed as iso_t
+    need_symbols(shm)
+    d = iso_t.problem("bunny_small", 16)
+    n, h, N = 16, float(d["cell"]), 16 ** 3
+    s = shm.GridSolver()
+    st = shm.grid_abi.ShmRedistanceExactStats()
+    buf = np.full(N, -7.0)
+    run = lambda iso=0.0, band=2.5 * h, p=None: s._lib.shm_grid_redistance_exact(s._h, float(iso), float(band), p)   # noqa: E731
+    psi_iso = lambda dist: s._lib.shm_grid_isosurface_indexed_psi(s._h, float(dist), None, None)                       # noqa: E731
+    get = lambda: s._lib.shm_grid_get_redistanced(s._h, buf.ctypes.data)                                              # noqa: E731
+    assert run() == SHM_ERR_STATE and psi_iso(0.0) == SHM_ERR_STATE           # no problem
+    s.set_problem(d["pos"], d["wnormal"], d["area"], float(d["lam"]), int(d["n"]), d["bbox_min"], h)
+    assert run() == SHM_ERR_STATE and psi_iso(0.0) == SHM_ERR_STATE           # before a solve
+    s.solve(tol=1e-10)
+    assert psi_iso(0.0) == SHM_ERR_STATE and get() == SHM_ERR_STATE           # no psi yet
+    for iso, band in ((0.0, 0.0), (0.0, -1.0), (0.0, float("nan")), (0.0, INF), (0.0, 16.01 * h), (float("nan"), 2.5 * h), (INF, 2.5 * h)):
+        assert run(iso, band) == SHM_ERR_INVALID and s._lib.shm_grid_last_error(s._h), (iso, band)
+    assert get() == SHM_ERR_STATE and (buf == -7).all()
+    assert run(0.0, 16.0 * h) == 0                                             # the cap itself is valid
+    # phi, one sample and a ray cast are left as they were; the resident indexed mesh afterwards is isosurface_indexed(isovalue)
+    phi = s.get_phi()[0]
+    pts = np.asarray(d["bbox_min"]) + (np.random.default_rng(5).random((257, 3)) * 15.0) * h
+    smp = s.sample(pts, grad=True)
+    t_ray = s.raycast(pts, np.ones_like(pts))[0]
+    Vo, Fo = s.isosurface(0.0)
+    iso = 0.25 * float(phi.max())
+    V, F = s.isosurface_indexed(iso)
+    s.isosurface_indexed(0.0)
+    assert run(iso, 2.5 * h, C.byref(st)) == 0 and st.n_reached > 0 and st.n_triangles == len(F) and st.n_vertices == len(V) and st.ms > 0 and st.n_candidate_pairs > 0
+    assert run(iso) == 0                                                       # out may be NULL
+    Vg, Fg = s.get_isosurface_indexed(len(V), len(F))
+    assert np.array_equal(Vg, V) and np.array_equal(Fg, F)
+    assert np.array_equal(s.get_phi()[0], phi)
+    smp2 = s.sample(pts, grad=True)
+    assert np.array_equal(smp2[0], smp[0]) and np.array_equal(smp2[1], smp[1]) and smp2[2] == smp[2]
+    assert np.array_equal(s.raycast(pts, np.ones_like(pts))[0], t_ray, equal_nan=True)
+    Vg, Fg = np.empty_like(Vo), np.empty_like(Fo)
+    assert s._lib.shm_grid_get_isosurface(s._h, Vg.ctypes.data, Fg.ctypes.data) == 0 and np.array_equal(Vg, Vo) and np.array_equal(Fg, Fo)
+    # the getters serve whichever call ran last
+    assert get() == 0
+    exact = buf.copy()
+    want, _ = ref.exact_distance(V[F], phi, n, d["bbox_min"], h, iso, 2.5 * h)
+    assert float(np.abs(exact - want).max()) <= ref1.tol(n, np.float64, want)
+    s.redistance(iso)
+    first = s.get_redistanced()
+    want1, _ = ref1.redistance(phi, n, h, iso)
+    assert float(np.abs(first - want1).max()) <= ref1.tol(n, np.float64, want1) and not np.array_equal(first, exact)
+    assert run(iso) == 0 and get() == 0 and np.array_equal(buf, exact)
+    dev = s.get_redistanced(device=True)
+    assert np.array_equal(dev.cpu().numpy(), exact)
+    # a call refused for its arguments leaves psi and the mesh alone; anything that replaces phi invalidates psi
+    assert run(iso, -1.0) == SHM_ERR_INVALID and get() == 0 and np.array_equal(buf, exact)
+    assert psi_iso(float("nan")) == SHM_ERR_INVALID and psi_iso(INF) == SHM_ERR_INVALID
+    assert psi_iso(1.6 * h) == SHM_ERR_INVALID and psi_iso(-1.6 * h) == SHM_ERR_INVALID and psi_iso(1.4 * h) == 0      # |d| + cell <= band = 2.5 cell
+    s.solve(tol=1e-10)
+    assert get() == SHM_ERR_STATE and psi_iso(0.0) == SHM_ERR_STATE
+    assert run(iso) == 0 and get() == 0 and np.array_equal(buf, exact)          # the same phi again: the same psi
+    s.apply_laplacian(np.zeros(N))                                              # a stage entry point that overwrites phi
+    assert run(iso) == SHM_ERR_STATE and psi_iso(0.0) == SHM_ERR_STATE and get() == SHM_ERR_STATE
+    header = open(os.path.join(ROOT, "include", "shm_grid.h")).read()
+    for name in ("shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi"):
+        assert ("shm_status %s(" % name) in header and name in shm.grid_abi.ABI_SYMBOLS
+    assert s._lib.shm_grid_abi_version() == 5 and "#define SHM_GRID_ABI_VERSION 5" in header and C.sizeof(st) == 64
+    s.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("precision", [64, 32])
+@pytest.mark.parametrize("kind", ["exact", "first_order"])
+def test_offset_mesh(shm, kind, precision):
+    """The indexed contour of the resident psi at d in {-1.5, 0, 0.5, 1.5} cell: vertices and triangles are iso_ref.marching_cubes(psi_dev, d) in the canonical
+    order, under the comparisons tests/test_iso_indexed.py uses for phi; components, records and keep_largest match tests/components_ref.py; the phi mesh
+    rebuilt afterwards is bit-identical to the one built before."""
+    import test_iso_indexed as iso_t
+    n = 20
+    d, s, phi = solved(shm, "bunny_small", n, precision)
+    h = float(d["cell"])
+    iso = isovalues(phi, n)["quarter_max"]
+    V0, F0 = s.isosurface_indexed(iso)
+    if kind == "exact":
+        run_exact(s, iso, 4 * h)
+    else:
+        s.redistance(iso, band=4 * h)
+    psi = s.get_redistanced()
+    tol = 8 * 2.0 ** -53 * iso_t.bound(d)
+    for k in (-1.5, 0.0, 0.5, 1.5):
+        V, F = s.isosurface_indexed_psi(k * h)
+        iso_t.check_against_restatement(V, F, psi, n, 0, d["bbox_min"], h, k * h, tol, tri_tag=("psi", kind, precision, k))
+        assert len(F) > 0
+        Vd, Fd = s.isosurface_indexed_psi(k * h, device=True)
+        assert np.array_equal(Fd.cpu().numpy(), F) and np.array_equal(Vd.cpu().numpy(), V.astype(dt(precision)))
+        # components of the offset mesh
+        rec, tc, vc = s.isosurface_components(labels=True)
+        want, wtc, wvc, _, _ = cref.records(V, F, n, d["bbox_min"], h)
+        assert len(rec) == len(want) and np.array_equal(tc, wtc) and np.array_equal(vc, wvc)
+        for key in ("first_vertex", "n_vertices", "n_triangles", "touches_box"):
+            assert np.array_equal(rec[key], want[key]), key
+        assert rec["lo"].tobytes() == want["lo"].tobytes() and rec["hi"].tobytes() == want["hi"].tobytes()
+        Vk, Fk = s.isosurface_indexed_psi(k * h, keep_largest=1)
+        Vw, Fw = cref.keep_mesh(V, F, vc, tc, cref.largest_mask(want, keep_largest=1))
+        assert np.array_equal(Vk, Vw) and np.array_equal(Fk, Fw)
+        print("offset %s fp%d d = %+.1f cell: %d vertices %d triangles %d components" % (kind, precision, k, len(V), len(F), len(rec)))
+    for bad in (3.01 * h, -3.01 * h):
+        assert s._lib.shm_grid_isosurface_indexed_psi(s._h, bad, None, None) == SHM_ERR_INVALID      # |d| + cell > band
+    assert np.array_equal(s.get_redistanced(), psi) and np.array_equal(s.get_phi()[0].astype(dt(precision)).astype(np.float64), phi)
+    V1, F1 = s.isosurface_indexed(iso)
+    assert np.array_equal(V1, V0) and np.array_equal(F1, F0)
+    if kind == "first_order":
+        s.redistance(iso)                                      # band = +inf: any finite distance is valid
+        assert s._lib.shm_grid_isosurface_indexed_psi(s._h, 6.0 * h, None, None) == 0
+
+
+@pytest.mark.gpu
+def test_host_mirror_cli_and_python_equal_the_abi(shm, tmp_path):
+    from signed_heat_3d_amd.host_abi import HostSolver
+    need_symbols(shm)
+    obj = os.path.join(ROOT, "data", "bunny_small.obj")
+    host = HostSolver(obj, tol=1e-10)
+    phi, _ = host.compute_distance(hCoef=0.0)
+    pre = host.preprocess(hCoef=0.0)
+    assert pre["n"] == 16
+    s = shm.GridSolver()
+    s.set_problem(pre["pos"], pre["wnormal"], pre["area"], pre["lam"], pre["n"], pre["bbox_min"], pre["cell"])
+    s.solve(tol=1e-10)
+    assert np.array_equal(s.get_phi()[0], phi)
+    iso, B, D = 0.25 * float(phi.max()), 4.0 * float(pre["cell"]), 1.5 * float(pre["cell"])
+    st = s.redistance_exact(iso, B)
+    psi = s.get_redistanced()
+    assert s.redistance_exact(iso)["band"] == B                       # the Python default band: 4 cells
+    V, F = s.isosurface_indexed_psi(D)
+    Vk, Fk = s.isosurface_indexed_psi(D, keep_largest=1, min_triangles=4)
+    psi_h, st_h = host.redistance_exact(iso, B)
+    assert np.array_equal(psi_h, psi)
+    st.pop("ms"), st_h.pop("ms")
+    assert st_h == st and st["n_reached"] > 0
+    Vh, Fh = host.isosurface_indexed_offset(D)
+    assert np.array_equal(Vh, V) and np.array_equal(Fh, F) and len(F) > 0
+    Vh, Fh = host.isosurface_indexed_offset(D, keep_largest=1, min_triangles=4)
+    assert np.array_equal(Vh, Vk) and np.array_equal(Fh, Fk)
+    exe = os.path.join(ROOT, "signed-heat-3d_amd", "bin", "shm_grid_cli")
+    f_psi, f_obj = str(tmp_path / "psi.bin"), str(tmp_path / "offset.obj")
+    p = subprocess.run([exe, obj, "--g", "--h", "0", "--tol", "1e-10", "--iso", repr(iso), "--redistance-exact", "--band", repr(B), "--out-psi", f_psi, "--iso-indexed",
+                        "--offset", repr(D), "--keep-largest", "1", "--min-triangles", "4", "--export", f_obj], capture_output=True, text=True)
+    assert p.returncode == 0 and "psi written to" in p.stderr and "Offset surface written to" in p.stderr, p.stderr
+    assert np.array_equal(np.fromfile(f_psi), psi)
+    rows = [ln.split() for ln in open(f_obj) if ln[:2] in ("v ", "f ")]
+    Vc = np.array([[float(x) for x in r[1:4]] for r in rows if r[0] == "v"])
+    Fc = np.array([[int(x.split("/")[0]) - 1 for x in r[1:4]] for r in rows if r[0] == "f"], dtype=np.int64)
+    assert np.array_equal(Fc, Fk) and Vc.shape == Vk.shape and float(np.abs(Vc - Vk).max()) <= 1e-5 * (1.0 + float(np.abs(Vk).max()))   # OBJ text: a few digits
+    for bad in (["--redistance-exact", "--out-psi", f_psi], ["--redistance-exact", "--redistance", "--band", "1", "--out-psi", f_psi], ["--offset", "0.1", "--iso-indexed"]):
+        p = subprocess.run([exe, obj, "--g", *bad], capture_output=True, text=True)
+        assert p.returncode != 0 and p.stderr, bad
+    p = subprocess.run([exe, "--help"], capture_output=True, text=True)
+    assert "--redistance-exact" in p.stdout and "--offset" in p.stdout
+    host.close()
+    s.close()
+
+
+@pytest.mark.gpu
+def test_two_ranks_are_refused(shm, tmp_path):
+    """world = 2 through the librccl double: SHM_ERR_STATE on both ranks for both entry points, with a message, and the ranks go on to finish."""
+    need_symbols(shm)
+    so = str(tmp_path / "librccl_mock.so")
+    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", os.path.join(ROOT, "tests", "native", "rccl_mock.c"), "-o", so, "-I/opt/rocm/include",
+                           "-D__HIP_PLATFORM_AMD__", "-L/opt/rocm/lib", "-lamdhip64", "-lrt", "-lpthread"])
+    uid = ("/shmmock_%d_rx_2" % os.getpid()).encode().ljust(128, b"\x00")
+    log = open(tmp_path / "worker.log", "w+")
+    p = subprocess.Popen([sys.executable, os.path.abspath(__file__), "worker", "2", uid.hex(), "bunny_small_n16", str(tmp_path)],
+                         env=dict(os.environ, SHM_RCCL_LIB=so), stdout=log, stderr=subprocess.STDOUT)
+    try:
+        p.wait(timeout=300)
+    except subprocess.TimeoutExpired:
+        p.kill()
+        p.wait()
+    log.seek(0)
+    assert p.returncode == 0, log.read()
+    for r in range(2):
+        lines = open(tmp_path / ("rx_%d.txt" % r)).read().split("\n")
+        assert int(lines[0]) == SHM_ERR_STATE and "world > 1" in lines[1], (r, lines)
+        assert int(lines[2]) == SHM_ERR_STATE and "world > 1" in lines[3], (r, lines)
+
+
+# ---- the worker of test_two_ranks_are_refused ------------------------------------------------------------------------------------------------------------------
+def _worker(world, uid_hex, case, out_dir):
+    import threading
+    import traceback
+    import shm_import
+    shm = shm_import.load()
+
+    def run_rank(rank):
+        d = load_golden(case)
+        s = shm.GridSolver(device=0, rank=rank, world=world, rccl_unique_id=bytes.fromhex(uid_hex))
+        s.set_problem(d["pos"], d["wnormal"], d["area"], float(d["lam"]), int(d["n"]), d["bbox_min"], float(d["cell"]))
+        s.solve(tol=1e-10)
+        rc = s._lib.shm_grid_redistance_exact(s._h, 0.0, 2.0 * float(d["cell"]), None)
+        msg = s._lib.shm_grid_last_error(s._h).decode()
+        rc2 = s._lib.shm_grid_isosurface_indexed_psi(s._h, 0.0, None, None)
+        msg2 = s._lib.shm_grid_last_error(s._h).decode()
+        with open(os.path.join(out_dir, "rx_%d.txt" % rank), "w") as f:
+            f.write("%d\n%s\n%d\n%s" % (rc, msg.replace("\n", " "), rc2, msg2.replace("\n", " ")))
+        s.sample(np.asarray(d["bbox_min"], dtype=np.float64).reshape(1, 3))   # the ranks are still in step: a collective call after the refusal completes
+        s.close()
+
+    def body(rank):
+        try:
+            run_rank(rank)
+        except BaseException:
+            traceback.print_exc()
+            sys.stdout.flush()
+            sys.stderr.flush()
+            os._exit(1)
+
+    threads = [threading.Thread(target=body, args=(r,)) for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+
+
+if __name__ == "__main__" and len(sys.argv) == 6 and sys.argv[1] == "worker":
+    _worker(int(sys.argv[2]), sys.argv[3], sys.argv[4], sys.argv[5])
