@@ -234,6 +234,14 @@ shm_status shm_grid_get_field_planes(shm_solver* s, shm_field f, int32_t k_begin
 /* out = L*u with the reference's Laplacian (signed_heat_grid_solver.cpp:278-334); u,out: n^3 doubles
  * on the host (world==1). */
 shm_status shm_grid_apply_laplacian(shm_solver* s, const double* u, double* out);
+/* Make the caller's field the resident phi: phi holds n^3 doubles on the host in shm_grid_get_phi's node order (world==1), each rounded once to the handle's
+ * precision on the way in, so shm_grid_get_phi returns exactly those rounded values.  Test and tooling entry point, added within ABI 5 (no struct changed,
+ * SHM_GRID_ABI_VERSION stays 5; detect it by its symbol): the tests feed every reader of phi fields no solve produces (tests/test_injected_phi.py), and a caller
+ * may contour, sample, ray-cast or redistance a field of their own.  Non-finite values are legal; each reader states its rule for them below.
+ * Afterwards the handle is as after a solve that returned this phi: every reader of phi is valid; the indexed mesh, its labelling, the brick extrema and psi of
+ * the old phi are dropped (their getters return SHM_ERR_STATE until rebuilt).  Y, the divergence, the constraints and their flags are left alone, and a later
+ * solve is not affected.  SHM_ERR_STATE before shm_grid_set_problem; SHM_ERR_INVALID for NULL or world != 1. */
+shm_status shm_grid_set_phi(shm_solver* s, const double* phi /* [n^3] */);
 /* Constraint rows (signed_heat_grid_solver.cpp:80-98): nodes/coeffs hold 8*S entries; *m rows written. */
 shm_status shm_grid_get_constraints(shm_solver* s, int64_t* nodes, double* coeffs, int32_t* m);
 /* The explicit Schur complement S = A K^+ A^T of the dual solver, as a solve with default options would assemble it: m x m doubles, row-major; *m rows.
@@ -254,7 +262,10 @@ shm_status shm_grid_apply_preconditioner(shm_solver* s, const double* v, double*
  *   SHM_ISO_MARCHING_CUBES (what shm_grid_isosurface runs, round 5): 256-case table, ambiguous faces resolved per face so that neighbouring cells agree
  *                          (watertight; csrc/shm_mc_table.h, generated by tools/gen_mc_table.py)
  *   SHM_ISO_MARCHING_TETS  (rounds 1-4): Kuhn split of every cell into six tetrahedra; also watertight, about 2.3x the triangles, extra vertices on the
- *                          face and body diagonals */
+ *                          face and body diagonals
+ * Non-finite nodes (both methods, and shm_grid_isosurface_indexed / shm_grid_isosurface_indexed_psi below): a cell with a non-finite corner (NaN, +inf or
+ *   -inf) contributes no triangle, and an edge carries a vertex only if both its ends are finite and it is cut; no returned position is non-finite.  For a
+ *   finite field nothing is discarded.  The surface ends in a free boundary around such cells. */
 enum { SHM_ISO_MARCHING_CUBES = 0, SHM_ISO_MARCHING_TETS = 1 };
 shm_status shm_grid_isosurface(shm_solver* s, double isovalue, int64_t* n_vertices, int64_t* n_triangles);
 shm_status shm_grid_isosurface_ex(shm_solver* s, double isovalue, int32_t method, int64_t* n_vertices, int64_t* n_triangles);
@@ -272,6 +283,9 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices /* [3*nv] */,
  * Box: a point with every coordinate in [bbox_min, bbox_min + (n-1)*cell] (the upper bound computed as (n-1)*cell + bbox_min, no tolerance band) is
  *   in the box.  On an upper face of an axis it uses cell n-2 of that axis with t = 1.  Any other point, and any point with a NaN coordinate, gets NaN
  *   for phi and for its gradient.  (The reference reads out of bounds there; wherever it is defined the arithmetic is the same.)
+ * Non-finite nodes: no special case.  The formula is evaluated in IEEE arithmetic on the eight corners of the chosen cell, so value and gradient are
+ *   non-finite (NaN, or +-inf beside an infinite corner) exactly where a corner of that cell is non-finite -- a corner of weight zero included, 0 * NaN and
+ *   0 * inf being NaN -- and finite everywhere else.
  * Ownership: like shm_grid_isosurface, a process answers the points whose cell has its lower z-plane among the planes its slabs own; the cell of a
  *   slab's top plane reads the plane above from the ghost layer (exchanged inside the call).  Every output entry is written; points this process
  *   does not answer get NaN, and *n_answered counts the points it did answer.  Each in-box point is answered by exactly one rank: combine the ranks'
@@ -298,6 +312,10 @@ shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, v
  *   vertices ascend in 3*g + axis, g = i + j*n + k*n^2 the edge's lower node, axis 0/1/2 = x/y/z;
  *   triangles ascend in (g of the cell's node 000, position in the case's table entry), corners in the table's order -- the order shm_grid_isosurface's
  *   sort produces, so the two meshes differ only by a renumbering of the vertices.  Two calls give bit-identical buffers.
+ * Non-finite nodes: shm_grid_isosurface's rule.  The vertex array holds every cut edge with two finite ends, also one whose (up to four) cells are all
+ *   discarded: that vertex is referenced by no triangle (finding out would take the corners of all its cells; the test is on the eight values a lane holds
+ *   anyway).  shm_grid_isosurface, which welds from the triangles, has no such vertex: the two meshes then differ by the renumbering and by these vertices.
+ *   shm_grid_isosurface_components reports each as a component of its own with n_vertices = 1, n_triangles = 0, area = volume = 0 and lo = hi = its position.
  * Coverage: as shm_grid_isosurface -- the cells whose lower z-plane this process owns, the plane above the last owned one read from the ghost layer
  *   (exchanged inside the call: COLLECTIVE with world > 1).  Indices are local to the process's vertex array; seam vertices are duplicated between ranks.
  * shm_grid_isosurface_indexed: builds the mesh and returns the counts.  Valid whenever shm_grid_isosurface is; SHM_ERR_STATE without a resident phi.
@@ -328,7 +346,7 @@ shm_status shm_grid_get_isosurface_indexed_device(shm_solver* s, void* d_vertice
  * shm_grid_isosurface_components: labels the mesh of the last shm_grid_isosurface_indexed, ranks the roots ascending (a flag and a scan) and fills one record
  *   per component on the device.  Every number is a function of the mesh alone: counts are integer sums; lo / hi are minima / maxima taken on an
  *   order-preserving integer image of the doubles; touches_box is an OR of exact comparisons (a vertex's off-axis coordinates are idx*cell + bbox_min with no
- *   further term); area and volume are fixed-point sums in int64, so they do not depend on the order of the adds:
+ *   further term; the upper face is (n-1)*cell + bbox_min rounded once or twice, whichever way the isosurface kernel's expression was contracted); area and volume are fixed-point sums in int64, so they do not depend on the order of the adds:
  *     area   = qA * sum_t llrint(A_t / qA),  qA = cell^2 2^-32,  A_t = |(b-a) x (c-a)| / 2                      (fp64, unfused)
  *     volume = qV * sum_t llrint(V_t / qV),  qV = cell^3 2^-20,  V_t = (a-o) . ((b-o) x (c-o)) / 6,  o = bbox_min
  *   cross(u, w) = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0); squares and dot products are summed (x + y) + z.  The volume is positive for a blob of inside
@@ -348,7 +366,7 @@ typedef struct {
     int64_t n_vertices, n_triangles;
     double  area, volume;          /* fixed-point sums, above */
     double  lo[3], hi[3];          /* min / max of its vertices' positions, bitwise those of the resident fp64 vertices */
-    int32_t touches_box;           /* 1: some vertex has a coordinate == bbox_min[a] or == (n-1)*cell + bbox_min[a] */
+    int32_t touches_box;           /* 1: some vertex has a coordinate == bbox_min[a] or == (n-1)*cell + bbox_min[a] (fused or not) */
     int32_t reserved;
 } shm_iso_component;               /* 96 bytes */
 shm_status shm_grid_label_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_triangles /* [3*nt] int64 */, void* d_root /* [nv] int64 */, int64_t* n_components);
@@ -418,7 +436,9 @@ int64_t shm_audit_sample_nodes(int32_t n, int32_t k_begin, int32_t k_end, int64_
  *   consecutive rays runs as long as its longest ray.
  * NaN, not an error: a non-finite origin or direction; d = 0; t_min > t_max; a ray that misses the box (with d[a] = 0, an o[a] outside
  *   [bbox_min[a], (n-1)*cell + bbox_min[a]] is a miss).  t_max = +inf is valid.
- * Non-finite nodes: a cell with a non-finite corner is never hit, and a brick that holds one is never skipped.
+ * Non-finite nodes: a cell with a non-finite corner is never hit, and a brick that holds one is never skipped; hits behind such cells are found.  Beside a
+ *   non-finite node F is not continuous across faces, so for a ray that runs inside a grid plane or along a grid line there, the answer depends on which of
+ *   the adjacent cells is walked: that choice is the implementation's and such a ray's answer is not part of the contract.
  * State: valid whenever shm_grid_sample is; SHM_ERR_STATE before a solve or after a test entry point that overwrote phi.  phi, Y, both isosurface meshes
  *   and every flag are left as they were.  The brick extrema (1/256 of phi) are built at the first cast of a phi -- about 1.4 reads of phi -- and kept
  *   until phi is replaced.
@@ -504,8 +524,8 @@ shm_status shm_grid_get_redistanced_device(shm_solver* s, void* d_psi /* [n^3], 
  * Result: u = T(sqrt(min over all triangles of d^2)), rounded once to the handle's precision T.  A node is reached iff u < band.  psi = s u at reached nodes and
  *   s band elsewhere, s = -1 where phi < isovalue and +1 otherwise.  T o sqrt is monotone, so the minimum is taken over the per-pair T(sqrt(d^2)) (on the bit
  *   pattern of the non-negative value), and the minimum commutes: psi is a function of phi, the isovalue and the band alone, two calls give bit-identical psi,
- *   and any local_slabs works.  A node whose phi is not finite holds NaN and a cell with a non-finite corner contributes no triangle (neither can be injected
- *   through this ABI; the rule is held by the numpy restatement, tests/redistance_exact_ref.py).
+ *   and any local_slabs works.  A node whose phi is not finite holds NaN and a cell with a non-finite corner contributes no triangle (M is built
+ *   by shm_grid_isosurface_indexed's rule; tested on the device through shm_grid_set_phi, tests/test_injected_phi.py).
  * Band: finite, positive and <= 16 cell, else SHM_ERR_INVALID (the work grows with (band / cell)^3 per surface cell; the cap keeps a call bounded).  With no
  *   triangle the call returns SHM_OK, n_reached = 0 and psi = s band.
  * Culling: a triangle lies in its cell's closed box, so the nodes offered a cell's triangles are those of [c - r, c + 1 + r]^3, r = ceil(band / cell), clipped
@@ -515,7 +535,8 @@ shm_status shm_grid_get_redistanced_device(shm_solver* s, void* d_psi /* [n^3], 
  *   for a NaN or infinite isovalue.  phi, Y, the mesh of shm_grid_isosurface, the brick extrema and every flag are left as they were; a call refused for its
  *   arguments leaves psi and the indexed mesh alone.
  * shm_grid_isosurface_indexed_psi: the indexed marching-cubes mesh of the resident psi (from either redistance call) at `distance`: the passes, case table,
- *   inside rule (v < distance), vertex arithmetic and canonical order of shm_grid_isosurface_indexed.  The mesh goes into the resident indexed-mesh slot:
+ *   inside rule (v < distance), vertex arithmetic, canonical order and non-finite rule of shm_grid_isosurface_indexed (psi is NaN wherever phi is not finite,
+ *   and +-inf where the first-order front never arrived: cells with such a corner carry no triangle).  The mesh goes into the resident indexed-mesh slot:
  *   both indexed getters, shm_grid_isosurface_components, its getter and shm_grid_isosurface_keep_components work on it unchanged, and a later
  *   shm_grid_isosurface_indexed or shm_grid_redistance_exact replaces it again.
  *   |distance| + cell <= band must hold (always true for band = +inf), else SHM_ERR_INVALID: an edge cut at d has psi_a < d <= psi_b <= psi_a + cell < d + cell,

@@ -176,6 +176,12 @@ shm_status shm_grid_apply_laplacian(shm_solver* s, const double* u, double* out)
         s->impl->apply_laplacian(u, out);
     });
 }
+shm_status shm_grid_set_phi(shm_solver* s, const double* phi) {
+    return guard(s, [&] {
+        if (!phi) throw shm::Error(SHM_ERR_INVALID, "null argument");
+        s->impl->set_phi(phi);
+    });
+}
 shm_status shm_grid_get_constraints(shm_solver* s, int64_t* nodes, double* coeffs, int32_t* m) {
     return guard(s, [&] {
         if (!nodes || !coeffs || !m) throw shm::Error(SHM_ERR_INVALID, "null argument");

@@ -43,6 +43,7 @@ static_assert(sizeof(CmpAcc) == 96 && sizeof(shm_iso_component) == 96, "a compon
 
 struct CmpGeom {
     double bbox_min[3], bbox_max[3];   // the box's face planes: bbox_min[a] and (n-1)*cell + bbox_min[a]
+    double bbox_max_fused[3];          // ... the latter in one rounding: the isosurface kernels' idx*cell + bbox_min may be contracted, so either is a face
     double qA, qV;                     // cell^2 2^-32, cell^3 2^-20
 };
 
@@ -262,7 +263,7 @@ __global__ __launch_bounds__(B) void cmp_vertex_records_kernel(CmpGeom G, size_t
             for (int a = 0; a < 3; a++) {
                 const double x = V[3 * v + a];
                 k[a] = cmp_key(x);
-                touch |= (x == G.bbox_min[a] || x == G.bbox_max[a]) ? 1 : 0;
+                touch |= (x == G.bbox_min[a] || x == G.bbox_max[a] || x == G.bbox_max_fused[a]) ? 1 : 0;
             }
         }
         const cmp_u64 all = __ballot(active);

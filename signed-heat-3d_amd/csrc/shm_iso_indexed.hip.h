@@ -37,6 +37,9 @@ struct IsoIdxParams {
 
 // What one lane knows about its node.  v[q] is phi at corner q of the cell the node is corner 000 of; a corner past the grid (or past ktop) repeats the
 // nearest one inside, so every load is in bounds and an edge that does not exist is never seen as cut.
+// Non-finite phi (include/shm_grid.h): a cell with a non-finite corner carries no triangle, and an edge carries a vertex only if both its ends are finite and
+// it is cut.  Both tests are on the eight values the lane holds anyway; for a finite field nothing changes.  A cut edge between finite ends whose cells are all
+// discarded keeps its vertex, referenced by no triangle: knowing that would take the other three cells' corners.
 struct IsoNode {
     int i, j, k;
     int cut;      // bit a: the edge from this node along axis a is cut
@@ -52,17 +55,19 @@ __device__ __forceinline__ void iso_node_load(const IsoIdxParams& P, const T* __
     const int k = P.k0 + kk;
     const int di = i < n - 1 ? 1 : 0, dj = j < n - 1 ? 1 : 0, dk = k < P.ktop ? 1 : 0;
     const size_t base = (size_t)(kk + GHOST) * plane + (size_t)j * n + i;
-    int inside = 0;
+    int inside = 0, fin = 0;
 #pragma unroll
     for (int q = 0; q < 8; q++) {
         nd.v[q] = (double)phi[base + (size_t)((q & 1) * di) + (size_t)(((q >> 1) & 1) * dj) * (size_t)n + (size_t)(((q >> 2) & 1) * dk) * plane];
         inside |= (nd.v[q] < P.iso ? 1 : 0) << q;
+        fin |= (nd.v[q] - nd.v[q] == 0. ? 1 : 0) << q;
     }
     nd.i = i; nd.j = j; nd.k = k;
     nd.inside = inside;
     const int in0 = inside & 1;
     nd.cut = (di & (((inside >> 1) & 1) ^ in0)) | ((dj & (((inside >> 2) & 1) ^ in0)) << 1) | ((dk & (((inside >> 4) & 1) ^ in0)) << 2);
-    nd.ntri = (di & dj & dk) ? (int)kMcCount[inside] : 0;
+    nd.cut &= (fin & 1) ? (((fin >> 1) & 1) | (((fin >> 2) & 1) << 1) | (((fin >> 4) & 1) << 2)) : 0;
+    nd.ntri = (di & dj & dk) && fin == 255 ? (int)kMcCount[inside] : 0;
 }
 
 // The node a lane holds while its workgroup walks a tile: (kk, j, i) of node l of the launch, found by division once and then advanced by kBlock nodes per

@@ -2073,12 +2073,14 @@ __global__ __launch_bounds__(kBlock) void iso_kernel(IsoParams P, const T* __res
         const size_t base = (size_t)(kk + 1) * plane + (size_t)j * n + i;
         double v[8];
         int inside = 0;
+        bool fin = true;
 #pragma unroll
         for (int q = 0; q < 8; q++) {
             v[q] = (double)phi[base + (q & 1) + ((q >> 1) & 1) * (size_t)n + ((q >> 2) & 1) * plane];
             inside |= (v[q] < P.iso ? 1 : 0) << q;
+            fin &= v[q] - v[q] == 0.;
         }
-        if (inside == 0 || inside == 255) continue;
+        if (inside == 0 || inside == 255 || !fin) continue;   // (a cell with a non-finite corner carries no triangle, include/shm_grid.h)
         const int k = P.k0 + kk;
         const unsigned long long gnode = (unsigned long long)i + (unsigned long long)j * n + (unsigned long long)k * plane;
         for (int t = 0; t < 6; t++) {
@@ -2178,12 +2180,14 @@ __global__ __launch_bounds__(kBlock) void iso_mc_kernel(IsoParams P, const T* __
         const size_t base = (size_t)(kk + 1) * plane + (size_t)j * n + i;
         double v[8];
         int inside = 0;
+        bool fin = true;
 #pragma unroll
         for (int q = 0; q < 8; q++) {
             v[q] = (double)phi[base + (q & 1) + ((q >> 1) & 1) * (size_t)n + ((q >> 2) & 1) * plane];
             inside |= (v[q] < P.iso ? 1 : 0) << q;
+            fin &= v[q] - v[q] == 0.;
         }
-        const int nt = kMcCount[inside];
+        const int nt = fin ? kMcCount[inside] : 0;   // (a cell with a non-finite corner carries no triangle, include/shm_grid.h)
         if (nt == 0) continue;
         if (!EMIT) {
             mycount += nt;

@@ -2903,14 +2903,14 @@ struct Solver final : SolverBase {
     }
 
     void upload_owned(const double* in, int which) {
-        // host N-vector -> slab array `which` (0: p with ghosts filled from the host copy, 1: r)
+        // host N-vector -> slab array `which` (0: p with ghosts filled from the host copy, 1: r, 2: q), each value rounded once to T
         std::vector<T> tmp;
         for (Slab<T>& sl : slabs) {
             tmp.assign(sl.ntot, (T)0);
             const int klo = std::max(0, sl.k0 - 1), khi = std::min(n, sl.k1 + 1);
             for (int k = klo; k < khi; k++)
                 for (size_t a = 0; a < sl.plane; a++) tmp[(size_t)(k - sl.k0 + 1) * sl.plane + a] = (T)in[(size_t)k * sl.plane + a];
-            T* dst = which == 0 ? sl.p.p : sl.r.p;
+            T* dst = which == 0 ? sl.p.p : which == 1 ? sl.r.p : sl.q.p;
             HIPCHK(hipMemcpyAsync(dst, tmp.data(), sl.ntot * sizeof(T), hipMemcpyHostToDevice, stream));
             HIPCHK(hipStreamSynchronize(stream));
         }
@@ -2927,6 +2927,20 @@ struct Solver final : SolverBase {
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_phi = false;  // q now holds L u, not phi
         iso_idx_valid = false;
+        ray_bricks_valid = false;
+        redist_valid = false;
+    }
+
+    // Test and tooling entry point: the caller's field becomes the resident phi (q of every slab), as if a solve had produced it.  Y, the divergence, the
+    // constraints and their flags stay; everything derived from the old phi falls, as at the start of a solve.
+    void set_phi(const double* phi) override {
+        need_problem();
+        if (cfg.world != 1) throw Error(SHM_ERR_INVALID, "set_phi is a single-process test entry point");
+        HIPCHK(hipSetDevice(cfg.device));
+        upload_owned(phi, 2);
+        have_phi = true;
+        iso_idx_valid = false;
+        cmp_valid = false;
         ray_bricks_valid = false;
         redist_valid = false;
     }
@@ -3367,6 +3381,7 @@ struct Solver final : SolverBase {
         for (int a = 0; a < 3; a++) {
             G.bbox_min[a] = bbox_min[a];
             G.bbox_max[a] = (n - 1) * cell + bbox_min[a];
+            G.bbox_max_fused[a] = std::fma((double)(n - 1), cell, bbox_min[a]);
         }
         G.qA = cell * cell * 0x1p-32;
         G.qV = cell * cell * cell * 0x1p-20;

@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 # every symbol include/shm_grid.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
-               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
+               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
@@ -152,6 +152,7 @@ def load_library():
     lib.shm_grid_get_field.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.shm_grid_get_field_planes.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
     lib.shm_grid_apply_laplacian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.shm_grid_set_phi.argtypes = [C.c_void_p, C.c_void_p]
     lib.shm_grid_get_constraints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.shm_grid_get_schur.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.shm_grid_apply_projector.argtypes = [C.c_void_p, C.c_void_p]
@@ -347,6 +348,18 @@ class GridSolver:
         out = np.empty_like(u)
         self._chk(self._lib.shm_grid_apply_laplacian(self._h, u.ctypes.data, out.ctypes.data))
         return out
+
+    def set_phi(self, phi):
+        """Make phi [n^3] (float64, get_phi's node order; None passes NULL) the resident phi (shm_grid_set_phi): each value is rounded once to the handle's
+        precision, every reader then works on it as on a solve's phi, and what was derived from the old phi (indexed mesh, labelling, brick extrema, psi) is
+        dropped.  Non-finite values are legal.  Single process; test and tooling entry point."""
+        if phi is None:
+            self._chk(self._lib.shm_grid_set_phi(self._h, None))
+            return
+        phi = _f64(phi).reshape(-1)
+        if self.n and phi.size != self.n ** 3:
+            raise ValueError("set_phi: phi must hold n^3 = %d values, got %d" % (self.n ** 3, phi.size))
+        self._chk(self._lib.shm_grid_set_phi(self._h, phi.ctypes.data))
 
     def get_constraints(self):
         nodes = np.empty(8 * self.S, dtype=np.int64)

@@ -6,6 +6,8 @@ roots():     labels by min-propagation to the fixed point -- every vertex, and t
              smallest vertex id of v's component, as a function of the triangle list alone.
 records():   one record per component from a fetched mesh, with the header's fixed-point formulas: float64, one rounding per operation (numpy fuses nothing).
 keep_mesh(): the numpy filter the device's compaction is held to."""
+from fractions import Fraction
+
 import numpy as np
 
 DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_triangles", "<i8"), ("area", "<f8"), ("volume", "<f8"),
@@ -100,7 +102,8 @@ def records(V, F, n, bbox_min, cell):
     rec["area"] = qA * sa.astype(np.float64)
     rec["volume"] = qV * sv.astype(np.float64)
     hi_plane = np.array([(n - 1) * cell + bbox_min[a] for a in range(3)])
-    touch = ((V == bbox_min[None, :]) | (V == hi_plane[None, :])).any(axis=1)
+    hi_fused = np.array([float(Fraction(n - 1) * Fraction(float(cell)) + Fraction(float(bbox_min[a]))) for a in range(3)])   # the same in one rounding
+    touch = ((V == bbox_min[None, :]) | (V == hi_plane[None, :]) | (V == hi_fused[None, :])).any(axis=1)
     for c in range(nc):
         sel = vcomp == c
         rec["lo"][c] = V[sel].min(axis=0)

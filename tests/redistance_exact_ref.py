@@ -64,30 +64,12 @@ def node_positions(n, bbox_min, cell):
 
 
 def mesh(phi, n, bbox_min, cell, iso):
-    """X [nt, 3, 3] of iso_ref.marching_cubes in its own order, without the triangles of cells that have a non-finite corner."""
-    P = np.asarray(phi, dtype=np.float64).reshape(n, n, n)
-    with np.errstate(invalid="ignore"):
-        pts, tris = iso_ref.marching_cubes(P.reshape(-1), n, bbox_min, cell, iso)
+    """X [nt, 3, 3] of iso_ref.marching_cubes in its own order, under its rule for non-finite nodes: no triangle from a cell with a non-finite corner."""
+    P = np.asarray(phi, dtype=np.float64).reshape(-1)
+    pts, tris = iso_ref.marching_cubes(P, n, bbox_min, cell, iso, drop_nonfinite=True)
     if not tris:
         return np.zeros((0, 3, 3))
-    X = np.array([[pts[e] for e in t] for t in tris], dtype=np.float64).reshape(-1, 3, 3)
-    fin = np.isfinite(P)
-    if fin.all():
-        return X
-    # iso_ref walks the cut cells in (k, j, i) order and appends len(table[case]) triangles for each: the cell of every triangle
-    table, _ = iso_ref._mc_table()
-    inside = P < iso
-    case = np.zeros((n - 1,) * 3, dtype=np.int32)
-    good = np.ones((n - 1,) * 3, dtype=bool)
-    for q in range(8):
-        sl = (slice((q >> 2) & 1, n - 1 + ((q >> 2) & 1)), slice((q >> 1) & 1, n - 1 + ((q >> 1) & 1)), slice(q & 1, n - 1 + (q & 1)))
-        case |= inside[sl].astype(np.int32) << q
-        good &= fin[sl]
-    keep = []
-    for k, j, i in zip(*np.nonzero((case > 0) & (case < 255))):
-        keep += [bool(good[k, j, i])] * len(table[case[k, j, i]])
-    assert len(keep) == len(X)
-    return X[np.array(keep, dtype=bool)]
+    return np.array([[pts[e] for e in t] for t in tris], dtype=np.float64).reshape(-1, 3, 3)
 
 
 def _finish(d2, phi, n, iso, band, dtype):
@@ -173,15 +155,11 @@ def exact_distance(X, phi, n, bbox_min, cell, iso, band, dtype=np.float64):
 
 
 def candidate_pairs(phi, n, cell, iso, band):
-    """n_candidate_pairs of the header: over the cells that carry a triangle, the nodes whose distance to the cell's box, in index space, has
-    (gx^2 + gy^2 + gz^2) cell^2 < band^2 (1 + 2^-18)."""
+    """n_candidate_pairs of the header: over the cells that carry a triangle (none with a non-finite corner does), the nodes whose distance to the cell's box,
+    in index space, has (gx^2 + gy^2 + gz^2) cell^2 < band^2 (1 + 2^-18)."""
     table, _ = iso_ref._mc_table()
     P = np.asarray(phi, dtype=np.float64).reshape(n, n, n)
-    inside = P < iso
-    case = np.zeros((n - 1,) * 3, dtype=np.int32)
-    for q in range(8):
-        case |= inside[(q >> 2) & 1:n - 1 + ((q >> 2) & 1), (q >> 1) & 1:n - 1 + ((q >> 1) & 1), (q & 1):n - 1 + (q & 1)].astype(np.int32) << q
-    ntri = np.array([len(t) for t in table])[case]
+    ntri = np.array([len(t) for t in table])[iso_ref.cell_cases(P, iso)] * iso_ref.finite_cells(P)
     ck, cj, ci = np.nonzero(ntri > 0)
     if not len(ck):
         return 0

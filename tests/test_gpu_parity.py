@@ -1484,8 +1484,8 @@ def test_isosurface_matches_python_restatement(shm, slabs, method):
 
 
 def test_isosurface_of_a_sphere_known_answer(shm):
-    """phi = |x| - 0.9 sampled on the grid through the solver's phi buffer is not injectable from outside, so use the SHM
-    result for sphere point samples: the 0-level set is a closed surface of area ~ 4 pi r^2 and radius ~ r."""
+    """The SHM result for sphere point samples: the 0-level set is a closed surface of area ~ 4 pi r^2 and radius ~ r.  (Fields put into the phi buffer from
+    outside, through shm_grid_set_phi, are contoured in tests/test_injected_phi.py.)"""
     import math
     P = 3000
     i = np.arange(P) + 0.5

@@ -4,8 +4,8 @@ the kernels, the C ABI, the Python bindings, the C++ host mirror and the CLI.
 Reference: tests/redistance_ref.py, a numpy Jacobi iteration of the scheme run until nothing changes, fed the device's own phi cast to the handle's precision.
 The discrete solution is unique, so the device (blocks, two colours, in-LDS iterations) and the restatement must agree to rounding:
     TOL = n eps_T max|psi|      eps_T the epsilon of the handle's precision: an update costs a few ulp and a causal chain is at most 3 n nodes long.
-The +-inf patterns (unreached nodes, empty level sets) are compared exactly.  Non-finite phi cannot be injected through the ABI: that rule (a wall for the
-neighbours, NaN in psi, counted) is held by the restatement and by a CPU test of it.
+The +-inf patterns (unreached nodes, empty level sets) are compared exactly.  The rule for non-finite phi (a wall for the neighbours, NaN in psi, counted) is
+held by the restatement and a CPU test of it here, and on the device in tests/test_injected_phi.py, which injects such a phi through shm_grid_set_phi.
 
 Run as a script (`test_redistance.py worker <world> <uid hex> <case> <dir>`) this file is the worker of test_two_ranks_are_refused: the ranks of a solve as
 threads of one process over the shared-memory RCCL double, as tests/ray_worker.py."""

@@ -6,8 +6,8 @@ fetched mesh -- never the code under test.  psi is held to
     TOL = n eps_T max|psi|      (redistance_ref.tol, the project's own)
 in fp64.  In fp32 the last operation of both sides is one rounding of sqrt(d^2) to fp32, so the two agree bit for bit except where the fp64 values before the
 rounding differ in their last bits across a rounding boundary: at most a 1e-3 share of the reached nodes may differ, and then by one fp32 ulp.
-The +-band pattern (unreached nodes, empty meshes) is compared exactly.  Non-finite phi cannot be injected through the ABI: that rule is held by the restatement
-and by a CPU test of it.
+The +-band pattern (unreached nodes, empty meshes) is compared exactly.  The rule for non-finite phi is held by the restatement and a CPU test of it here, and
+on the device in tests/test_injected_phi.py, which injects such a phi through shm_grid_set_phi.
 
 Run as a script (`test_redistance_exact.py worker <world> <uid hex> <case> <dir>`) this file is the worker of test_two_ranks_are_refused, as tests/test_redistance.py."""
 import ctypes as C
