@@ -554,6 +554,55 @@ typedef struct {
 shm_status shm_grid_redistance_exact(shm_solver* s, double isovalue, double band, shm_redistance_exact_stats* out /* or NULL */);
 shm_status shm_grid_isosurface_indexed_psi(shm_solver* s, double distance, int64_t* n_vertices, int64_t* n_triangles);
 
+/* --- closest-point queries against the resident indexed mesh -------------------------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * For an arbitrary point: how far is the contoured surface, where is the nearest point on it, and which triangle is that?  phi is not a distance (see
+ *   shm_grid_redistance) and shm_grid_redistance_exact answers at grid nodes only; this call answers anywhere.  Kernels in csrc/shm_closest.hip.h.
+ * M is the resident indexed mesh, whatever is in the slot: the mesh of shm_grid_isosurface_indexed, the one shm_grid_redistance_exact left behind, an offset
+ *   mesh of shm_grid_isosurface_indexed_psi, any of these after shm_grid_isosurface_keep_components (which is how the specks that would capture every nearby
+ *   query at isovalue 0 are removed first).  The call builds nothing and replaces nothing in that slot.  Vertices are the resident fp64 doubles, bitwise
+ *   those shm_grid_get_isosurface_indexed returns, on SHM_F32 handles as well.
+ * Pair distance: for query q and triangle t, A, B, C the corners minus q, d^2 = tri_dist2(A, B, C) of csrc/shm_tri_dist.h -- the formula stated under
+ *   shm_grid_redistance_exact, unchanged -- and c = the candidate that attained it (tri_closest of the same header: the same d^2 bit for bit; c = P + t e for a
+ *   segment candidate, the foot (s / nn) N for the face; candidates in the order AB, BC, CA, face with a strict <, so the first of equal candidates stays).
+ * Answer: d^2(q) = min over all triangles of M; tri(q) = the SMALLEST triangle id attaining that minimum; dist = sqrt(d^2) in fp64; the foot point is q + c,
+ *   one rounding per coordinate.  A query is answered iff dist < max_dist.  The minimum and the tie rule commute, so the answer is a function of M, q and
+ *   max_dist alone: two calls give bit-identical buffers, and neither local_slabs nor the order in which the device meets the triangles can show.
+ * The distance is UNSIGNED.  At a grid node the sign is phi < isovalue; at an arbitrary point the trilinear zero set and the marching-cubes mesh disagree
+ *   within a cell, and a sign consistent with the mesh needs pseudonormals: not provided.
+ * Outputs, every entry written, in input order: dist_out[q]; cp_out (optional) the foot point; tri_out (optional) the triangle id, an index into the
+ *   triangles of shm_grid_get_isosurface_indexed.  Unanswered entries hold NaN, NaN x 3 and -1.  *n_answered counts the finite answers.
+ * A query may lie anywhere, outside the box included: it is answered iff M is within max_dist of it.  A query with a non-finite coordinate is unanswered,
+ *   not an error.  Queries that are neighbours in space should be neighbours in the arrays: a wavefront of 64 consecutive queries runs as long as its
+ *   longest walk, and neighbours share the index words and triangles they load.
+ * max_dist: finite, positive and <= 16 cell, else SHM_ERR_INVALID -- shm_grid_redistance_exact's cap, for its reason: a query with nothing near walks
+ *   (2 max_dist / cell + 3)^3 cells.
+ * Errors: SHM_ERR_INVALID for Q < 0, Q > 2^48, or NULL pts / dist_out with Q > 0.  Q = 0 is valid.  SHM_ERR_STATE without a valid indexed mesh -- the
+ *   conditions under which shm_grid_get_isosurface_indexed refuses: before a build, or after anything that replaced phi -- and with world > 1.  An empty mesh
+ *   is SHM_OK with nothing answered.  phi, psi, Y, both meshes, the labelling, the brick extrema and every flag are left as they were.
+ * Index: the grid is the index.  Every triangle of a resident mesh lies in the closed box of one grid cell; a triangle is filed under the cell of the middle
+ *   of its extent (per axis floor((0.5 (min + max) - bbox_min) / cell) clamped to [0, n - 2]; one lying in a grid plane lands in either neighbour).  The
+ *   index is a bitmask of the occupied cells, the prefix of its words' popcounts, and the triangle ids grouped by cell: at most n^3 / 4 bytes plus 16 bytes
+ *   per triangle (32-bit keys and ids: n^3 and the triangle count must stay below 2^32, else SHM_ERR_INVALID).  It is built at the first query of a mesh,
+ *   kept until the slot holds another mesh (a rebuild, a filter, an offset mesh; anything that replaces phi), and freed with the handle.  A query walks the
+ *   Chebyshev shells of cells around its own (clamped) cell, passes over a cell whose box, grown by 2^-16 cell, is further than
+ *   min(running distance, max_dist) (1 + 2^-18)^(1/2), and stops after shell s once that limit is below s cell; csrc/shm_closest_index.h holds the rule and
+ *   the argument that it keeps a superset under rounding.
+ * Slivers: the answer is the minimum of the pair formula, whatever the formula returns.  For a triangle thinner than 2^-22 cell (0 < N.N < (2^-22 cell)^2 times
+ *   its longest edge squared) the formula's inside test is rounding noise and the face candidate can be the distance to the triangle's plane from cells away;
+ *   vertices that coincide up to an ulp, where a node sits on the isovalue, make such triangles.  No cull by position holds for them, so they are filed under
+ *   no cell and every query tests them: the result equals brute force over all triangles on such meshes as well.  (shm_grid_redistance_exact culls them by
+ *   their cell like any other triangle.)  Ordinary fields have none.
+ * shm_grid_closest_point: host buffers, fp64; pts [3Q] xyz-interleaved.  The queries stream through the device in chunks of 2^20 through the pinned staging
+ *   buffers the handle keeps for shm_grid_raycast.
+ * shm_grid_closest_point_device: device buffers of the handle's precision on the handle's device, same layouts, d_tri int64; float points are promoted
+ *   first and the fp64 outputs rounded once on the store; synchronous.  Every pointer is checked as shm_grid_sample_device checks its own before anything is
+ *   enqueued: host memory, another device's memory or an allocation smaller than Q queries is SHM_ERR_INVALID. */
+shm_status shm_grid_closest_point(shm_solver* s, int64_t Q, const double* pts /* [3Q] */, double max_dist, double* dist_out /* [Q] */,
+                                  double* cp_out /* [3Q] or NULL */, int64_t* tri_out /* [Q] or NULL */, int64_t* n_answered);
+shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d_pts, double max_dist, void* d_dist, void* d_cp /* or NULL */,
+                                         void* d_tri /* int64, or NULL */, int64_t* n_answered);
+
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */
 shm_status shm_comm_unique_id(void* out128);

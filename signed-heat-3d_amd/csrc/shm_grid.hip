@@ -273,6 +273,13 @@ shm_status shm_grid_get_redistanced_device(shm_solver* s, void* d_psi) {
     return guard(s, [&] { s->impl->get_redistanced_device(d_psi); });
 }
 
+shm_status shm_grid_closest_point(shm_solver* s, int64_t Q, const double* pts, double max_dist, double* dist_out, double* cp_out, int64_t* tri_out, int64_t* n_answered) {
+    return guard(s, [&] { s->impl->closest_point(Q, pts, max_dist, dist_out, cp_out, tri_out, n_answered); });
+}
+shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d_pts, double max_dist, void* d_dist, void* d_cp, void* d_tri, int64_t* n_answered) {
+    return guard(s, [&] { s->impl->closest_point_device(Q, d_pts, max_dist, d_dist, d_cp, d_tri, n_answered); });
+}
+
 shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) {
     return guard(s, [&] { s->impl->audit_step1(count, nodes, dy_out, ratio_out, out); });
 }

@@ -576,6 +576,8 @@ struct SolverBase {
     virtual void get_redistanced_device(void*) = 0;
     virtual void redistance_exact(double, double, shm_redistance_exact_stats*) = 0;
     virtual void isosurface_indexed_psi(double, int64_t*, int64_t*) = 0;
+    virtual void closest_point(int64_t, const double*, double, double*, double*, int64_t*, int64_t*) = 0;
+    virtual void closest_point_device(int64_t, const void*, double, void*, void*, void*, int64_t*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

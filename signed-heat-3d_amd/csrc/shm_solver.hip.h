@@ -28,6 +28,7 @@
 #include "shm_raycast.hip.h"
 #include "shm_redistance.hip.h"
 #include "shm_redistance_exact.hip.h"
+#include "shm_closest.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -3178,6 +3179,7 @@ struct Solver final : SolverBase {
     int64_t iso_idx_nv = 0, iso_idx_nt = 0;
     int iso_idx_n = -1;
     bool iso_idx_valid = false;
+    uint64_t iso_idx_gen = 0;   // counts the meshes the slot has held (a build, a compaction)
 
     void isosurface_indexed(double iso, int64_t* nv_out, int64_t* nt_out) override {
         need_problem();
@@ -3194,6 +3196,7 @@ struct Solver final : SolverBase {
     std::vector<size_t> iso_tile_base;
     void iso_idx_build(double iso, bool from_psi) {
         iso_idx_valid = false;
+        iso_idx_gen++;       // the closest-point index belongs to the mesh it was made of
         cmp_valid = false;   // a labelling belongs to the mesh it was made of
         iso_idx_nv = iso_idx_nt = 0;
         const int kb = from_psi ? 0 : slabs.front().k0, ke = from_psi ? n : slabs.back().k1;
@@ -3461,6 +3464,7 @@ struct Solver final : SolverBase {
             std::swap(d_iso_F.count, F2.count);
             iso_idx_nv = nv2;
             iso_idx_nt = nt2;
+            iso_idx_gen++;
         }
         cmp_valid = false;   // the records described the unfiltered mesh
         cmp_nc = 0;
@@ -3540,24 +3544,30 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
     }
 
+    // the two staging slots, pinned and on the device, of C * 10 doubles each (closest_point streams through them as well: 8 doubles per query)
+    void ray_staging_reserve(int64_t C) {
+        for (auto& e : ray_done)
+            if (!e) e.reset(new Event());
+        if (C <= ray_cap) return;
+        for (int b = 0; b < 2; b++) {
+            if (ray_pinned[b]) HIPCHK(hipHostFree(ray_pinned[b]));
+            ray_pinned[b] = nullptr;
+            ray_dev[b].release();
+        }
+        ray_cap = 0;
+        for (int b = 0; b < 2; b++) {
+            HIPCHK(hipHostMalloc(&ray_pinned[b], (size_t)C * 10 * sizeof(double)));
+            ray_dev[b].alloc((size_t)C * 10);
+        }
+        ray_cap = C;
+    }
+
     // host buffers: the rays stream through two pinned staging slots of their own (a ray is 6 + 4 doubles against sample's 3 + 4), as in sample()
     void raycast(int64_t Q, const double* org, const double* dir, double iso, double t_min, double t_max, double* t_out, double* grad, int64_t* n_hits) override {
         raycast_check("raycast", Q, org, dir, t_out, iso);
         const RayParams P = raycast_begin(iso, t_min, t_max);
         const int64_t C = std::min(Q, kRayChunk);
-        if (C > ray_cap) {
-            for (int b = 0; b < 2; b++) {
-                if (ray_pinned[b]) HIPCHK(hipHostFree(ray_pinned[b]));
-                ray_pinned[b] = nullptr;
-                ray_dev[b].release();
-            }
-            ray_cap = 0;
-            for (int b = 0; b < 2; b++) {
-                HIPCHK(hipHostMalloc(&ray_pinned[b], (size_t)C * 10 * sizeof(double)));
-                ray_dev[b].alloc((size_t)C * 10);
-            }
-            ray_cap = C;
-        }
+        ray_staging_reserve(C);
         const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
         auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
             const int b = (int)(c & 1);
@@ -3799,6 +3809,156 @@ struct Solver final : SolverBase {
             out->band = band;
             out->ms = elapsed(*rdx_ev[0], *rdx_ev[3]);
         }
+    }
+
+    // ---- closest-point queries against the resident indexed mesh (shm_closest.hip.h) ----------------------------------------------------------------------------
+    // Working memory: the index -- n^3 / 8 bytes of mask, n^3 / 16 of its popcount prefix, 16 bytes per triangle -- built at the first query of a mesh and
+    // kept until the slot holds another mesh (cp_gen against iso_idx_gen; anything that replaces phi makes the mesh itself invalid); freed with the handle.
+    // The host entry streams through the ray casts' staging slots.  The mesh, phi, psi and every flag are left as they were.
+    DevArray<unsigned long long> d_cp_mask, d_cp_cnt;
+    DevArray<uint32_t> d_cp_rank, d_cp_key, d_cp_list, d_cp_count, d_cp_first, d_cp_tile, d_cp_ns;
+    int64_t cp_n_slivers = 0;   // triangles filed under no cell: every query tests them (shm_closest_index.h)
+    uint64_t cp_gen = 0;
+    bool cp_have = false;   // an index of mesh cp_gen exists
+    std::unique_ptr<Event> cp_ev[3];
+    float cp_build_ms = 0.f;
+
+    void closest_check(const char* who, int64_t Q, const void* pts, const void* dist, double max_dist) {
+        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
+        if (Q > ((int64_t)1 << 48)) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 queries", who));   // (the byte counts below must not wrap)
+        if (Q > 0 && (!pts || !dist)) throw Error(SHM_ERR_INVALID, fmt("%s: null points or distance output", who));
+        need_problem();
+        if (!(max_dist > 0.) || !(max_dist <= kCpMaxDistCells * cell))
+            throw Error(SHM_ERR_INVALID, fmt("%s: max_dist must be finite, positive and at most %d cells (a walk visits (2 max_dist / cell + 3)^3 cells at worst)", who, kCpMaxDistCells));
+        need_iso_indexed(who);
+        if (cfg.world != 1)
+            throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: the nearest triangle may lie in the planes of another rank", who));
+    }
+    // exclusive scan of `count` values (popcounts of mask words, or 32-bit counts) into out[0 .. count], out[count] the total
+    template <bool POP> void cp_scan(size_t count, const void* in, uint32_t* out) {
+        const size_t ntiles = (count + 1 + kCpScanBlock - 1) / kCpScanBlock;
+        d_cp_tile.alloc(2 * ntiles + 1);
+        uint32_t* sums = d_cp_tile.p;
+        uint32_t* offs = d_cp_tile.p + ntiles;
+        hipLaunchKernelGGL((cp_tile_sums_kernel<POP>), dim3((unsigned)ntiles), dim3(kCpScanBlock), 0, stream, count, in, sums);
+        hipLaunchKernelGGL((cp_tile_scan_kernel<kCpScanBlock>), dim3(1), dim3(kCpScanBlock), 0, stream, ntiles, sums, offs);
+        hipLaunchKernelGGL((cp_tile_prefix_kernel<POP>), dim3((unsigned)ntiles), dim3(kCpScanBlock), 0, stream, count, in, offs, out, 1);
+    }
+    void cp_index_build() {
+        if (cp_have && cp_gen == iso_idx_gen) return;
+        cp_have = false;
+        cp_build_ms = 0.f;
+        cp_n_slivers = 0;
+        const int64_t nt = iso_idx_nt;
+        if (nt > 0) {
+            if (nt >= ((int64_t)1 << 32) || (double)n * n * n >= 4294967296.)
+                throw Error(SHM_ERR_INVALID, "closest_point: the index holds 32-bit cell keys and triangle ids: 2^32 triangles or cells are not supported");
+            for (auto& e : cp_ev)
+                if (!e) e.reset(new Event());
+            cp_ev[0]->record(stream);
+            const CpGrid G = cp_grid(n, bbox_min, cell);
+            const size_t ncells = (size_t)n * n * n, nwords = (ncells + 63) / 64;
+            d_cp_mask.alloc(nwords);
+            d_cp_rank.alloc(nwords + 1);
+            d_cp_key.alloc((size_t)nt);
+            d_cp_list.alloc((size_t)nt);
+            d_cp_count.alloc((size_t)nt);       // one per occupied cell: at most nt
+            d_cp_first.alloc((size_t)nt + 1);
+            HIPCHK(hipMemsetAsync(d_cp_mask.p, 0, nwords * sizeof(unsigned long long), stream));
+            HIPCHK(hipMemsetAsync(d_cp_count.p, 0, (size_t)nt * sizeof(uint32_t), stream));
+            d_cp_ns.alloc(1);
+            HIPCHK(hipMemsetAsync(d_cp_ns.p, 0, sizeof(uint32_t), stream));
+            const dim3 tgrid(grid_for((size_t)nt, 16384));
+            hipLaunchKernelGGL((cp_keys_kernel<kBlock>), tgrid, dim3(kBlock), 0, stream, G, nt, d_iso_V.p, d_iso_F.p, d_cp_key.p, d_cp_mask.p, d_cp_list.p, d_cp_ns.p);
+            cp_scan<true>(nwords, d_cp_mask.p, d_cp_rank.p);
+            hipLaunchKernelGGL((cp_count_kernel<kBlock>), tgrid, dim3(kBlock), 0, stream, nt, d_cp_key.p, d_cp_mask.p, d_cp_rank.p, d_cp_count.p);
+            // (the scan runs over nt counts: the entries past the last occupied cell are zero, and cell_first stays flat there)
+            cp_scan<false>((size_t)nt, d_cp_count.p, d_cp_first.p);
+            HIPCHK(hipMemsetAsync(d_cp_count.p, 0, (size_t)nt * sizeof(uint32_t), stream));   // the counts become the fill cursors
+            hipLaunchKernelGGL((cp_fill_kernel<kBlock>), tgrid, dim3(kBlock), 0, stream, nt, d_cp_key.p, d_cp_mask.p, d_cp_rank.p, d_cp_first.p, d_cp_count.p, d_cp_list.p);
+            HIPCHK(hipGetLastError());
+            cp_ev[1]->record(stream);
+            uint32_t ns = 0;
+            HIPCHK(hipMemcpyAsync(&ns, d_cp_ns.p, sizeof ns, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            cp_n_slivers = (int64_t)ns;
+            cp_build_ms = elapsed(*cp_ev[0], *cp_ev[1]);
+        }
+        cp_gen = iso_idx_gen;
+        cp_have = true;
+    }
+    void closest_begin() {
+        HIPCHK(hipSetDevice(cfg.device));
+        cp_index_build();
+        d_cp_cnt.alloc(kCpCounters);
+        HIPCHK(hipMemsetAsync(d_cp_cnt.p, 0, kCpCounters * sizeof(unsigned long long), stream));
+    }
+    int64_t closest_end(int64_t Q) {
+        unsigned long long c[kCpCounters] = {};
+        HIPCHK(hipMemcpyAsync(c, d_cp_cnt.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        log("[shm] closest_point: %lld queries, %llu answered, %llu triangle tests, %lld slivers, index build %.3f ms", (long long)Q, c[kCpAnswered], c[kCpTriTests],
+            (long long)cp_n_slivers, cp_build_ms);
+        cp_build_ms = 0.f;   // (reported by the call that paid for it)
+        return (int64_t)c[kCpAnswered];
+    }
+    template <typename TIO> void launch_closest(int64_t Q, double max_dist, const TIO* pts, TIO* dist, TIO* cpo, int64_t* tri) {
+        if (Q <= 0) return;
+        const CpGrid G = cp_grid(n, bbox_min, cell);
+        const CpIndex X{d_cp_mask.p, d_cp_rank.p, d_cp_first.p, d_cp_list.p, d_iso_V.p, d_iso_F.p, iso_idx_nt, cp_n_slivers};
+        const int grid = grid_for((size_t)Q, 16384);
+        if (iso_idx_nt > 0) hipLaunchKernelGGL((closest_point_kernel<TIO, true>), dim3(grid), dim3(kBlock), 0, stream, G, X, Q, max_dist, pts, dist, cpo, tri, d_cp_cnt.p);
+        else hipLaunchKernelGGL((closest_point_kernel<TIO, false>), dim3(grid), dim3(kBlock), 0, stream, G, X, Q, max_dist, pts, dist, cpo, tri, d_cp_cnt.p);
+        HIPCHK(hipGetLastError());
+    }
+    // host buffers: chunks of 2^20 queries through the ray casts' two staging slots; per slot points [3C], dist [C], foot points [3C], triangles [C] (int64)
+    void closest_point(int64_t Q, const double* pts, double max_dist, double* dist, double* cpo, int64_t* tri, int64_t* n_answered) override {
+        closest_check("closest_point", Q, pts, dist, max_dist);
+        closest_begin();
+        const int64_t C = std::min(Q, kRayChunk);
+        ray_staging_reserve(C);
+        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
+        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
+            const int b = (int)(c & 1);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            HIPCHK(hipEventSynchronize(ray_done[b]->e));
+            const double* hb = (const double*)ray_pinned[b];
+            memcpy(dist + q0, hb + 3 * C, (size_t)m * sizeof(double));
+            if (cpo) memcpy(cpo + 3 * q0, hb + 4 * C, (size_t)m * 3 * sizeof(double));
+            if (tri) memcpy(tri + q0, hb + 7 * C, (size_t)m * sizeof(int64_t));
+        };
+        for (int64_t c = 0; c < nchunks; c++) {
+            const int b = (int)(c & 1);
+            if (c >= 2) finish(c - 2);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            double* hb = (double*)ray_pinned[b];
+            double* db = ray_dev[b].p;
+            memcpy(hb, pts + 3 * q0, (size_t)m * 3 * sizeof(double));
+            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+            launch_closest<double>(m, max_dist, db, db + 3 * C, cpo ? db + 4 * C : nullptr, tri ? (int64_t*)(db + 7 * C) : nullptr);
+            HIPCHK(hipMemcpyAsync(hb + 3 * C, db + 3 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (cpo) HIPCHK(hipMemcpyAsync(hb + 4 * C, db + 4 * C, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (tri) HIPCHK(hipMemcpyAsync(hb + 7 * C, db + 7 * C, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipEventRecord(ray_done[b]->e, stream));
+        }
+        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        const int64_t a = closest_end(Q);
+        if (n_answered) *n_answered = a;
+    }
+    void closest_point_device(int64_t Q, const void* pts, double max_dist, void* dist, void* cpo, void* tri, int64_t* n_answered) override {
+        const char* who = "closest_point_device";
+        closest_check(who, Q, pts, dist, max_dist);
+        HIPCHK(hipSetDevice(cfg.device));
+        if (Q > 0) {
+            check_device_buffer(pts, (size_t)Q * 3 * sizeof(T), "the point buffer", who, "the Q queries asked for");
+            check_device_buffer(dist, (size_t)Q * sizeof(T), "the distance buffer", who, "the Q queries asked for");
+            if (cpo) check_device_buffer(cpo, (size_t)Q * 3 * sizeof(T), "the foot-point buffer", who, "the Q queries asked for");
+            if (tri) check_device_buffer(tri, (size_t)Q * sizeof(int64_t), "the triangle buffer", who, "the Q queries asked for");
+        }
+        closest_begin();
+        launch_closest<T>(Q, max_dist, (const T*)pts, (T*)dist, (T*)cpo, (int64_t*)tri);
+        const int64_t a = closest_end(Q);
+        if (n_answered) *n_answered = a;
     }
 
     // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------

@@ -24,6 +24,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
+               "shm_grid_closest_point", "shm_grid_closest_point_device",
                "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
@@ -185,6 +186,9 @@ def load_library():
     if hasattr(lib, "shm_grid_redistance_exact"):   # added within ABI 5: found by symbol
         lib.shm_grid_redistance_exact.argtypes = [C.c_void_p, C.c_double, C.c_double, C.POINTER(ShmRedistanceExactStats)]
         lib.shm_grid_isosurface_indexed_psi.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(lib, "shm_grid_closest_point"):   # added within ABI 5: found by symbol
+        lib.shm_grid_closest_point.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.shm_grid_closest_point_device.argtypes = lib.shm_grid_closest_point.argtypes
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -578,6 +582,75 @@ class GridSolver:
         if keep_largest is not None or min_triangles is not None:
             nv.value, nt.value = self.isosurface_keep(largest_components_mask(self.isosurface_components(), keep_largest, min_triangles))
         return self.get_isosurface_indexed(nv.value, nt.value, device)
+
+    def _closest_result(self, dist, c, t, na, label):
+        out = (dist,) + ((c,) if c is not None else ()) + ((t,) if t is not None else ())
+        if label:
+            out += (self._closest_labels(t),)
+        return out + (na,)
+
+    def _closest_labels(self, tri):
+        """tri_component[tri] for the answered queries and -1 for the others, or None when the resident mesh carries no valid labelling."""
+        # the getter refuses with SHM_ERR_STATE without a labelling; with one it accepts no buffers (no component) or misses the record buffer (SHM_ERR_INVALID)
+        if self._lib.shm_grid_get_isosurface_components(self._h, None, None, None) == 7:   # SHM_ERR_STATE
+            return None
+        _, tc, _ = self.isosurface_components(labels=True)   # the same mesh labels the same way: the resident labelling is recomputed, not changed
+        if hasattr(tri, "cpu"):
+            tri = tri.cpu().numpy()
+        out = np.full(tri.shape, -1, dtype=np.int64)
+        ok = tri >= 0
+        out[ok] = tc[tri[ok]]
+        return out
+
+    def closest_point(self, points, max_dist=None, cp=True, tri=True, label=False):
+        """For every point of points [Q, 3] the distance to the resident indexed mesh (whatever isosurface_indexed, redistance_exact,
+        isosurface_indexed_psi or isosurface_keep left in the slot), the nearest point on it and its triangle (shm_grid_closest_point): returns
+        (dist [Q], [cp [Q, 3],] [tri [Q] int64,] [component [Q] int64 or None,] n_answered), float64.  A point further than max_dist (length units, at
+        most 16 cells, the default 4 cells) or with a non-finite coordinate is unanswered: NaN, NaN x 3, -1.  The distance is unsigned.  tri is the
+        smallest id among the nearest triangles.  label=True (needs tri) adds the component rank of that triangle, -1 where unanswered, when the mesh's
+        labelling is valid (isosurface_components has run on it), else None.  Keep neighbouring points neighbours in the array."""
+        if not hasattr(self._lib, "shm_grid_closest_point"):
+            raise RuntimeError("closest_point: this build of libshm_grid.so does not export shm_grid_closest_point")
+        if label and not tri:
+            raise ValueError("closest_point: label=True needs tri=True")
+        pts = _f64(points).reshape(-1, 3)
+        Q = pts.shape[0]
+        if max_dist is None:
+            max_dist = 4.0 * self.cell
+        dist = np.empty(Q, dtype=np.float64)
+        c = np.empty((Q, 3), dtype=np.float64) if cp else None
+        t = np.empty(Q, dtype=np.int64) if tri else None
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_closest_point(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, c.ctypes.data if cp else None,
+                                                   t.ctypes.data if tri else None, C.byref(na)))
+        return self._closest_result(dist, c, t, na.value, label)
+
+    def closest_point_device(self, points, max_dist=None, cp=True, tri=True, label=False):
+        """The same on device memory (shm_grid_closest_point_device), with sample_device's conventions: points is a contiguous [Q, 3] torch tensor on this
+        handle's device with its dtype; dist and cp come back as tensors of that dtype (the fp64 answer rounded once), tri as int64, on that device; the
+        component labels of label=True are a numpy array.  Import torch before this library is loaded."""
+        if not hasattr(self._lib, "shm_grid_closest_point_device"):
+            raise RuntimeError("closest_point_device: this build of libshm_grid.so does not export shm_grid_closest_point_device")
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("closest_point_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        if label and not tri:
+            raise ValueError("closest_point_device: label=True needs tri=True")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if points.dtype != dt or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise ValueError("closest_point_device: points must be a contiguous [Q, 3] %s tensor" % dt)
+        Q = points.shape[0]
+        if max_dist is None:
+            max_dist = 4.0 * self.cell
+        dist = torch.empty(Q, dtype=dt, device=points.device)
+        c = torch.empty((Q, 3), dtype=dt, device=points.device) if cp else None
+        t = torch.empty(Q, dtype=torch.int64, device=points.device) if tri else None
+        if points.is_cuda:
+            torch.cuda.current_stream(points.device).synchronize()   # the points may still be in flight on torch's stream
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_closest_point_device(self._h, Q, points.data_ptr() if Q else None, float(max_dist), dist.data_ptr() if Q else None,
+                                                          c.data_ptr() if cp and Q else None, t.data_ptr() if tri and Q else None, C.byref(na)))
+        return self._closest_result(dist, c, t, na.value, label)
 
     def get_redistanced(self, device=False):
         """psi of the last redistance(): [n^3] float64 in get_phi's node order, or with device=True a torch tensor of the handle's dtype on its device,

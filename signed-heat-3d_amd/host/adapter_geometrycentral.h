@@ -137,6 +137,26 @@ class SignedHeatGridSolver {
         return t;
     }
 
+    // The distance from every point of q to the indexed mesh resident on the device (the mesh of the last isosurfaceIndexed() / isosurfaceIndexedOffset() /
+    // redistanceExact()), unsigned, NaN beyond maxDist (a length, at most 16 cells); optionally the nearest point on the mesh and the index of its face, -1
+    // where unanswered (shm_grid_closest_point).
+    std::vector<double> closestPoints(const std::vector<Vector3>& q, double maxDist, std::vector<Vector3>* points = nullptr, std::vector<int64_t>* triangles = nullptr) {
+        if (!handle) throw std::runtime_error("closestPoints: computeDistance has not been called");
+        size_t Q = q.size();
+        std::vector<double> pts(3 * Q), dist(Q), cp(points ? 3 * Q : 0);
+        for (size_t a = 0; a < Q; a++)
+            for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+        if (triangles) triangles->resize(Q);
+        int64_t answered = 0;
+        if (shm_grid_closest_point(handle, (int64_t)Q, pts.data(), maxDist, dist.data(), points ? cp.data() : nullptr, triangles ? triangles->data() : nullptr, &answered) != SHM_OK)
+            throw std::runtime_error(shm_grid_last_error(handle));
+        if (points) {
+            points->resize(Q);
+            for (size_t a = 0; a < Q; a++) (*points)[a] = Vector3{cp[3 * a], cp[3 * a + 1], cp[3 * a + 2]};
+        }
+        return dist;
+    }
+
     // Redistance the phi of the last computeDistance() on the device (shm_grid_redistance): psi with |grad psi| = 1 in the first-order upwind sense, psi < 0
     // exactly where phi < isoval, clamped to +-band; at the grid nodes, in computeDistance's order.  phi is left as it was.
     Vector<double> redistance(double isoval = 0., double band = std::numeric_limits<double>::infinity()) {

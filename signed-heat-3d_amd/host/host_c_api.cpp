@@ -213,6 +213,27 @@ int shmh_raycast(void* hv, int64_t Q, const double* origins, const double* dirs,
     });
 }
 
+// closestPoints through the C++ class: points [3Q] against the device's resident indexed mesh -> dist_out [Q], cp_out [3Q] or NULL, tri_out [Q] or NULL,
+// *n_answered finite answers.
+int shmh_closest_points(void* hv, int64_t Q, const double* pts, double max_dist, double* dist_out, double* cp_out, int64_t* tri_out, int64_t* n_answered) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> q((size_t)Q), c;
+        for (int64_t a = 0; a < Q; a++) q[(size_t)a] = Vector3{pts[3 * a], pts[3 * a + 1], pts[3 * a + 2]};
+        std::vector<int64_t> t;
+        const std::vector<double> d = h->solver.closestPoints(q, max_dist, cp_out ? &c : nullptr, tri_out ? &t : nullptr);
+        int64_t answered = 0;
+        for (int64_t a = 0; a < Q; a++) {
+            dist_out[a] = d[(size_t)a];
+            answered += d[(size_t)a] == d[(size_t)a] ? 1 : 0;
+            if (cp_out)
+                for (int b = 0; b < 3; b++) cp_out[3 * a + b] = c[(size_t)a][b];
+            if (tri_out) tri_out[a] = t[(size_t)a];
+        }
+        if (n_answered) *n_answered = answered;
+    });
+}
+
 // redistance through the C++ class: psi of the last compute_distance's phi at the grid nodes -> psi_out [n^3]; stats may be NULL.
 int shmh_redistance(void* hv, double isoval, double band, double* psi_out, shm_redistance_stats* stats) {
     Host* h = (Host*)hv;

@@ -41,11 +41,15 @@ static void usage() {
                  "      --band <B>        Width of the band the redistancing fills, a length; nodes beyond it hold +-B (default: the whole grid)\n"
                  "      --redistance-exact Instead of --redistance: psi = the exact distance to the marching-cubes surface at --iso inside --band (required, at most 16 cells)\n"
                  "      --offset <D>      With --iso-indexed and a redistance flag: export the offset surface psi = D instead of phi = --iso (|D| + cell <= --band)\n"
-                 "      --out-psi <file>  Raw float64 psi at the grid nodes, in the order of --out\n";
+                 "      --out-psi <file>  Raw float64 psi at the grid nodes, in the order of --out\n"
+                 "      --closest <file>  With --iso-indexed: points to measure against the indexed mesh (filtered / offset as exported), in --query's format\n"
+                 "      --closest-out <file> Raw float64, five values per point: distance (unsigned; NaN beyond --closest-max), nearest point xyz, triangle index (-1: none)\n"
+                 "      --closest-max <D> How far the mesh may be from a point, in cells (default 4, at most 16)\n";
 }
 
 int main(int argc, char** argv) {
-    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut;
+    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut, closestPath, closestOut;
+    double closestMax = 4.;
     double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
     bool redistance = false, redistanceExact = false, haveOffset = false;
     double offset = 0.;
@@ -90,6 +94,9 @@ int main(int argc, char** argv) {
         else if (s == "--offset") { offset = atof(need("--offset")); haveOffset = true; }
         else if (s == "--band") band = atof(need("--band"));
         else if (s == "--out-psi") psiOut = need("--out-psi");
+        else if (s == "--closest") closestPath = need("--closest");
+        else if (s == "--closest-out") closestOut = need("--closest-out");
+        else if (s == "--closest-max") closestMax = atof(need("--closest-max"));
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
         else path = s;
     }
@@ -99,6 +106,10 @@ int main(int argc, char** argv) {
     }
     if (raysPath.empty() != raysOut.empty()) {
         std::cerr << "--rays and --rays-out go together." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (closestPath.empty() != closestOut.empty() || (!closestPath.empty() && !isoIndexed)) {
+        std::cerr << "--closest and --closest-out go together and measure against the mesh of --iso-indexed." << std::endl;
         return EXIT_FAILURE;
     }
     if (redistance && redistanceExact) {
@@ -181,7 +192,7 @@ int main(int argc, char** argv) {
                       << rs.n_reached << " reached, max |psi| " << rs.max_abs << ", " << rs.n_candidate_pairs << " candidate pairs, " << rs.ms << " ms; psi written to "
                       << psiOut << std::endl;
         }
-        if (!exportPath.empty()) {
+        if (!exportPath.empty() || !closestPath.empty()) {   // (--closest needs the indexed mesh on the device whether or not it is exported)
             std::vector<Vector3> iv;
             std::vector<std::array<size_t, 3>> jf;
             if (isoIndexed && (haveOffset || keepLargest >= 0 || minTriangles >= 0)) {
@@ -196,8 +207,35 @@ int main(int argc, char** argv) {
                 }
             } else if (isoIndexed) solver.isosurfaceIndexed(isoval, iv, jf);
             else solver.isosurface(isoval, iv, jf);
-            writeSurfaceMesh(iv, jf, exportPath);
-            std::cerr << (haveOffset ? "Offset surface written to " : "Isosurface written to ") << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
+            if (!exportPath.empty()) {
+                writeSurfaceMesh(iv, jf, exportPath);
+                std::cerr << (haveOffset ? "Offset surface written to " : "Isosurface written to ") << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
+            }
+        }
+        if (!closestPath.empty()) {
+            std::ifstream f(closestPath, std::ios::binary | std::ios::ate);
+            if (!f) throw std::runtime_error("cannot read " + closestPath);
+            const std::streamsize bytes = f.tellg();
+            if (bytes % (std::streamsize)(3 * sizeof(double)) != 0) throw std::runtime_error(closestPath + ": size is not a multiple of 24 bytes (float64 xyz triples)");
+            std::vector<double> raw((size_t)bytes / sizeof(double));
+            f.seekg(0);
+            f.read((char*)raw.data(), bytes);
+            std::vector<Vector3> q(raw.size() / 3), c;
+            for (size_t a = 0; a < q.size(); a++) q[a] = Vector3{raw[3 * a], raw[3 * a + 1], raw[3 * a + 2]};
+            std::vector<int64_t> t;
+            const std::vector<double> d = solver.closestPoints(q, closestMax * solver.gridCell(), &c, &t);
+            std::vector<double> res(5 * q.size());
+            size_t answered = 0;
+            for (size_t a = 0; a < q.size(); a++) {
+                res[5 * a] = d[a];
+                answered += d[a] == d[a] ? 1 : 0;
+                for (int b = 0; b < 3; b++) res[5 * a + 1 + b] = c[a][b];
+                res[5 * a + 4] = (double)t[a];
+            }
+            std::ofstream o(closestOut, std::ios::binary);
+            o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
+            std::cerr << q.size() << " points measured against the indexed mesh within " << closestMax << " cells: " << answered
+                      << " answered; distance, nearest point and triangle written to " << closestOut << std::endl;
         }
         if (!queryPath.empty()) {
             std::ifstream f(queryPath, std::ios::binary | std::ios::ate);

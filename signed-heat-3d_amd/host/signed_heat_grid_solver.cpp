@@ -215,6 +215,23 @@ std::vector<double> SignedHeatGridSolver::castRays(const std::vector<Vector3>& o
     return t;
 }
 
+std::vector<double> SignedHeatGridSolver::closestPoints(const std::vector<Vector3>& q, double maxDist, std::vector<Vector3>* points, std::vector<int64_t>* triangles) {
+    if (!handle) throw std::runtime_error("closestPoints: computeDistance has not been called");
+    const size_t Q = q.size();
+    std::vector<double> pts(3 * Q), dist(Q), cp(points ? 3 * Q : 0);
+    for (size_t a = 0; a < Q; a++)
+        for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+    if (triangles) triangles->resize(Q);
+    int64_t answered = 0;
+    if (shm_grid_closest_point(handle, (int64_t)Q, pts.data(), maxDist, dist.data(), points ? cp.data() : nullptr, triangles ? triangles->data() : nullptr, &answered) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_closest_point: ") + shm_grid_last_error(handle));
+    if (points) {
+        points->resize(Q);
+        for (size_t a = 0; a < Q; a++) (*points)[a] = Vector3{cp[3 * a], cp[3 * a + 1], cp[3 * a + 2]};
+    }
+    return dist;
+}
+
 VectorXd SignedHeatGridSolver::redistance(double isoval, double band, shm_redistance_stats* stats) {
     if (!handle) throw std::runtime_error("redistance: computeDistance has not been called");
     if (shm_grid_redistance(handle, isoval, band, stats) != SHM_OK) throw std::runtime_error(std::string("shm_grid_redistance: ") + shm_grid_last_error(handle));

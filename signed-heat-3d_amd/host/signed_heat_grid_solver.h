@@ -80,6 +80,13 @@ class SignedHeatGridSolver {
     void isosurfaceIndexedOffset(double distance, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces, int64_t keepLargest = -1,
                                  int64_t minTriangles = -1, std::vector<shm_iso_component>* components = nullptr);
 
+    // For every point of q: the distance to the indexed mesh resident on the device -- the mesh of the LAST isosurfaceIndexed() / isosurfaceIndexedOffset()
+    // call, filtered if that call filtered it, or the one redistanceExact() left behind -- computed on the device (shm_grid_closest_point; contract in
+    // include/shm_grid.h).  Unsigned; NaN for a point further than maxDist (a length, at most 16 cells) or with a non-finite coordinate.  points (optional)
+    // receives the nearest point on the mesh (NaN x 3 where unanswered), triangles (optional) the index of its face in that call's `faces` (-1 where
+    // unanswered; the smallest index among equally near faces).  Keep neighbouring points neighbours in q.
+    std::vector<double> closestPoints(const std::vector<Vector3>& q, double maxDist, std::vector<Vector3>* points = nullptr, std::vector<int64_t>* triangles = nullptr);
+
     // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
     // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).
     shm_step1_audit auditStep1(size_t count = 4096, uint64_t seed = 0);

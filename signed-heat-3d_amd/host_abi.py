@@ -43,6 +43,8 @@ def load_host_library():
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
+    if hasattr(lib, "shmh_closest_points"):
+        lib.shmh_closest_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     if hasattr(lib, "shmh_redistance_exact"):
         lib.shmh_redistance_exact.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceExactStats)]
         lib.shmh_isosurface_indexed_offset.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
@@ -146,6 +148,16 @@ class HostSolver:
         self._chk(self._lib.shmh_raycast(self._h, o.shape[0], o.ctypes.data, d.ctypes.data, float(isovalue), float(t_min), float(t_max), t.ctypes.data,
                                          g.ctypes.data if grad else None, C.byref(nh)))
         return (t, g, nh.value) if grad else (t, nh.value)
+
+    def closest_points(self, points, max_dist):
+        """closestPoints of the C++ mirror: points [Q, 3] against the indexed mesh resident on the device (shm_grid_closest_point).
+        Returns (dist [Q], cp [Q, 3], tri [Q] int64, n_answered); NaN, NaN x 3 and -1 for a point further than max_dist."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        Q = pts.shape[0]
+        dist, cp, tri = np.empty(Q, dtype=np.float64), np.empty((Q, 3), dtype=np.float64), np.empty(Q, dtype=np.int64)
+        na = C.c_int64()
+        self._chk(self._lib.shmh_closest_points(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, cp.ctypes.data, tri.ctypes.data, C.byref(na)))
+        return dist, cp, tri, na.value
 
     def redistance(self, isovalue=0.0, band=float("inf")):
         """redistance of the C++ mirror: the phi of the last compute_distance redistanced on the device to its level set (shm_grid_redistance).
