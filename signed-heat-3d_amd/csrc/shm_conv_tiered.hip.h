@@ -55,9 +55,20 @@
 // __host__ __device__ function (far_carry_step, shm_far_carry.h) that tests/native/test_far_carry.cpp walks on the host.  The near list runs an exact count and lost its
 // padding entries.  LDS per workgroup: far lists 68 entries per wave as before (64 + carry 3 + at most 1 of padding, where 64 + 4 of padding stood), near list 64 entries
 // (68): 51 904 bytes at NPT = 4 (52 672), 49 728 at NPT = 2.  174 registers.
+// Round 9 (profiles/NOTES_r09.md): the RING PASS.  A block with a failing node used to walk every source again in fp64, 1.0 of the all-fp64 cost on top of the pass it throws
+// away -- although its far tier's L1 sum is dominated by the far sources nearest the threshold (their terms fall off by e per e-fold of margin).  Now such a block is first
+// walked again as pass 0 was -- cleared sums, empty far list, the same drop rule and the same R -- with the far threshold G + ring (ConvParams::tier_ring, nats) in the
+// classification AND in the price of the test: only the ring of sources between the two thresholds moves into fp64, the deep far sources stay packed fp32.  Only when that
+// pass's test fails too does the block evaluate every source in fp64.  The plan of the (up to three) passes is one __host__ __device__ function (tier_pass,
+// shm_tier_passes.h) that tests/native/test_tier_passes.cpp walks on the host; the pass loop is still ONE loop around one copy of the two pair loops, the far list is
+// drained behind the last cluster of each tiered pass (far_carry_step), ring = 0 is rounds 4-8's two passes.  counters[2] counts the fp64 pairs of every pass after the first,
+// counters[1] the ring pass's far pairs too.  The ring pass is skipped where pass 0's test fails on the dropped bound alone (it drops the same sources: tier_pass_runs).
+// Shipped with ring = 2 (kTierRingDefault; rocker 256^3 Step 1 -6.8 %, the bunny's unchanged); SHM_CONV_TIER_RING is the A/B knob, 0 the two passes of rounds 4-8.
+// 176 registers, LDS unchanged, both hot loops unchanged (100 / 123 instructions).
 #pragma once
 #include "shm_far_carry.h"
 #include "shm_kernels.hip.h"
+#include "shm_tier_passes.h"
 
 namespace shm {
 
@@ -307,10 +318,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         exp_tab[a] = tv;
     }
     __syncthreads();   // the only workgroup barrier: the table
+    // Placement of the two hot loops (round 9, profiles/NOTES_r09.md): the near and the far loop are 672 and 756 bytes of straight-line code that two waves per SIMD run back to
+    // back, and where their heads fall in the 64-byte instruction cache lines shows in Step 1: measured on one box with the SAME instruction streams, the bunny's 256^3 Step 1
+    // took 21.78 ms with the heads at byte 8 / 4 of a line (where rounds 7-8 happened to have them), 21.93 at 28 / 24 and 21.99 at 12 / 16.  The compiler does not align loops on
+    // this target, so unrelated code in front of them moves the heads; these no-ops, executed once per workgroup, put them back at 8 / 4 in the <4, double, true> instantiation.
+    // tools/step1_isa_check.py prints where the heads are: adjust the count when code in front of the loops changes.
+    asm volatile("s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0\n s_nop 0");
     const int n = P.n;
     const size_t plane = (size_t)n * n;
     const float lam_l2 = (float)(P.lambda * 1.4426950408889634);     // lambda in powers of two per unit length
     const float g_l2 = P.tier_log * 1.4426950408889634f;
+    // the pass plan (shm_tier_passes.h): with a ring, a block whose test fails is walked again at the threshold G + ring before it falls back to the all-fp64 pass
+    const float ring_l2 = CHECK ? P.tier_ring * 1.4426950408889634f : 0.f;
     const bool drop_on = P.drop_eps_soft > 0.f;   // (wave-uniform: kernel argument)
     const float cellq = (float)(P.cell * (P.lambda * 1.4426950408889634));   // the cell size in the far tier's scaled units
     const float lws = uniform_f32((float)log2(P.wscale));                      // log2 of the weights' scale factor (a power of two)
@@ -498,12 +517,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         if constexpr (CHECK) {   // (four registers less through the loops; a wave's LDS accesses execute in order)
             if (drop_on && lane == 0) star_stash[wave] = float4{(cx - nx) * lam_l2, (cy - ny) * lam_l2, (cz - nz) * lam_l2, wnear};
         }
-        const float span_c = uniform_f32(2.f * rt_w * lam_l2 - coff - 960.f);   // pass 1: a dropped source is evaluated only where its exponent stays inside the block's span
-        // pass 0: near sources in fp64, far ones in packed fp32.  pass 1 (only when the a-posteriori test failed): every source in fp64, from cleared accumulators.
+        const float span_c = uniform_f32(2.f * rt_w * lam_l2 - coff - 960.f);   // the all-fp64 pass: a dropped source is evaluated only where its exponent stays inside the block's span
+        // pass 0: near sources in fp64, far ones in packed fp32.  Only when its a-posteriori test failed, from cleared accumulators: the ring pass (P.tier_ring > 0) -- the
+        // same walk at the threshold G + ring -- and, when that one's test fails too (or there is no ring), every source in fp64.  The plan is tier_pass (shm_tier_passes.h).
         int far_pending = 0;
         int carry = 0;   // far list entries left at the head of the lists by the clusters before (wave-uniform, <= kFarGroup - 1; see far_carry_step)
+        bool drop_fails = false;   // (wave-uniform) pass 0's test failed on the dropped bound alone, at the ring pass's own price: the ring pass would fail as well
 #pragma unroll 1
-        for (int pass = 0; pass < 2; pass++) {
+        for (int pass = kTierPassFirst; pass <= kTierPassAllF64; pass++) {
+        if (!tier_pass_runs(pass, ring_l2, drop_fails)) continue;   // (no ring, or no use for one: from the first pass straight to the all-fp64 one)
+        const TierPass tp = tier_pass(pass, CHECK, g_l2, ring_l2);   // (wave-uniform)
         // the lane's source of cluster c: fetched into the wave's raw LDS region one cluster ahead (issued once cluster c - 1 has been read out of it, in flight
         // while that cluster's two loops run; a skipped cluster's fetch is simply overwritten by the next: loads return in order)
 #if SHM_TIER_LDS_FETCH
@@ -527,8 +550,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         // Rounds 3-5 tested one cluster per trip of a scalar loop -- six scalar loads, a dozen vector instructions on wave-uniform values, a branch: a dependent chain per
         // cluster, 216 of them per block on rocker, 817 on SprayBottle.pc, most of them for clusters that are dropped.  Now a lane tests ONE cluster of a batch of 64 (its
         // record by three 8-byte loads), ballots turn the 64 answers into scalar masks, and the walk below steps from set bit to set bit.  The accumulated drop rule takes a
-        // batch's candidates together -- all of them while the running sum allows, else only the ones below the hard threshold --, in the fixed order of the batches; pass 1
-        // repeats the masks and walks what pass 0 dropped as well (`cdrop_mask` tells the classification that every source of such a cluster was dropped).
+        // batch's candidates together -- all of them while the running sum allows, else only the ones below the hard threshold --, in the fixed order of the batches; the all-fp64
+        // pass repeats the masks and walks what the tiered passes dropped as well (`cdrop_mask` tells the classification that every source of such a cluster was dropped).
         int cur_batch = -1;
         unsigned long long kept_mask = 0ull, cdrop_mask = 0ull;
         auto load_batch = [&](int b) {
@@ -565,7 +588,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                     }
                 }
             }
-            kept_mask = pass == 1 ? validm : validm & ~cdrop_mask;
+            kept_mask = tp.tiered ? validm & ~cdrop_mask : validm;
         };
         // the next cluster >= `from` this pass walks (P.n_clusters: none); cdrop: pass 0 dropped it as a whole
         auto next_kept = [&](int from, bool& cdrop) {
@@ -586,8 +609,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
         };
         // The fetch runs one KEPT cluster ahead (round 5 in the fp64 solve; the fp32 solve kept the plain order then because the scalar scan for the next kept cluster sat between
         // a cluster's fetch and its use -- with the scan a few scalar instructions on a mask, round 6, both solves look ahead).
-        // (each pass starts its sums from zero, but pass 1 does NOT repeat pass 0's decisions: its look-ahead walks every cluster, so load_batch runs at other points of the
-        // scan, R_soft accumulates in another order and a soft / hard decision can differ.  Harmless: pass 1 evaluates every valid source, the dropped ones where span_ok.)
+        // (each pass starts its sums from zero.  The ring pass repeats pass 0's walk and with it pass 0's drop decisions and its R exactly -- the far threshold does not enter
+        // them.  The all-fp64 pass does NOT: its look-ahead walks every cluster, so load_batch runs at other points of the scan, R_soft accumulates in another order and a
+        // soft / hard decision can differ.  Harmless: that pass evaluates every valid source, the dropped ones where span_ok.)
         R_soft = 0.f;
         R_hard = 0.f;
         bool cdrop_cur = false, cdrop_next = false;
@@ -659,9 +683,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                 }
                 // (fp64 solve: only sources at least r_hi from the block -- the bound leaves out the factor r_hi / d_s, and a packed-fp32 distance next to a node has no
                 // relative accuracy left, which the a-posteriori test cannot see)
-                const bool far = lhs_far > g_l2 + rel && in_range && (!CHECK || dist >= r_hi_w);
+                const bool far = lhs_far > tp.g_l2 + rel && in_range && (!CHECK || dist >= r_hi_w);
                 // the drop rule by accumulated bound (see the block's header above): candidates of this cluster together, or only the ones below the hard threshold
-                bool drop = valid && cdrop_cur;   // (pass 1 walks a cluster that pass 0 dropped as a whole)
+                bool drop = valid && cdrop_cur;   // (the all-fp64 pass walks a cluster that the tiered passes dropped as a whole)
                 if (drop_on && !cdrop_cur) {
                     const float lb = rel - lhs_drop + 2e-5f;   // log2 of b_s without its geometric factor, rounded up
                     const bool cand = valid && lb <= P.drop_ltau;
@@ -683,10 +707,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
                         }
                     }
                 }
-                // pass 1 evaluates what pass 0 dropped as well, where the term's exponent stays inside the span of the block's scale (beyond it the term is < 2^-900 of the scale)
+                // the all-fp64 pass evaluates what the tiered passes dropped as well, where the term's exponent stays inside the span of the block's scale (beyond it the term is < 2^-900 of the scale)
                 const bool span_ok = fmaf(dist, lam_l2, span_c) < 0.f;
-                const bool to64 = valid && (pass == 0 ? (!drop && !far) : (drop ? span_ok : true));   // (drop first: a source outside the fp32 exponent range is not "far", but it may well be dropped)
-                const bool to32 = valid && pass == 0 && far && !drop;
+                const bool to64 = valid && (tp.tiered ? (!drop && !far) : (drop ? span_ok : true));   // (drop first: a source outside the fp32 exponent range is not "far", but it may well be dropped)
+                const bool to32 = valid && tp.tiered && far && !drop;
                 nearmask = __ballot(to64);
                 farmask = __ballot(to32);
                 // stage the cluster for the broadcast reads below (wave-private region: no barrier), COMPACTED: the near sources in fp64 and the far ones in fp32
@@ -728,7 +752,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
             }
             cnt_near += (unsigned)nnear;
             cnt_far += (unsigned)nfar;
-            if (pass) cnt_redo += (unsigned)nnear;
+            if (tp.redo) cnt_redo += (unsigned)nnear;
             // one near source against the lane's z-column; breadth-first over the pairs in flight: every stage of e^{-lambda r}/r for all of them before the next stage, so
             // that the dependent chain of one pair (rsq -> Newton -> exponent -> table -> exponent insertion) is covered by the others' independent work
             auto near_source = [&](const double (&rec)[6]) {
@@ -843,9 +867,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
             cdrop_cur = cdrop_next;
         }
         if (!CHECK) break;
-        if (pass == 0) {
-            // a-posteriori test of the far tier's contribution (see the header): eps_far L1_far <= budget |X| at every node of the block, or the far sources
-            // -- near, far and dropped -- are evaluated again in fp64 (pass 1) and the sums of pass 0 discarded
+        if (tp.test) {
+            // a-posteriori test of the far tier's contribution (see the header): eps_far L1_far <= budget |X| at every node of the block, or the sums of this pass are
+            // discarded and the sources walked again -- with the threshold a ring higher (the ring pass), or all of them, near, far and dropped, in fp64
             bool fail = false;
             const double e0 = far_scale();
             // what the block dropped, against |X| as well (round 6): its accumulated bound R is relative to the reference source's term at the node, evaluated here once per node
@@ -860,21 +884,30 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_TIER
             const float rs = r_drop * chk * 1.01f * sqrtf(st.w) * __builtin_amdgcn_exp2f(-lws) * lam_l2;   // (lambda': the reciprocal below is of the SCALED distance)
             const float sdx = qx - st.x, sdy = qy - st.y, sdz0 = qz0 - st.z;   // scaled coordinates, like the far tier's
             // the price of a packed-fp32 term grows with its exponent (its scaled distance carries ~1e-7 u of rounding into 2^-u): beyond u = P.tier_u0 the block's far terms
-            // -- at least coff + g_l2 powers of two below 1 -- are priced at eps_far u / u0 (a wave-uniform fp32 factor on the threshold: a scalar register; u0 = 0: flat)
-            const float ratio_f = uniform_f32((float)P.far_redo_ratio * (P.tier_u0 > 0.f ? fminf(1.f, P.tier_u0 / (coff + g_l2)) : 1.f));
+            // -- at least coff + g_l2 powers of two below 1, g_l2 this pass's threshold -- are priced at eps_far u / u0 (a wave-uniform fp32 factor on the threshold: a scalar register; u0 = 0: flat)
+            const float ratio_f = uniform_f32((float)P.far_redo_ratio * (P.tier_u0 > 0.f ? fminf(1.f, P.tier_u0 / (coff + tp.g_l2)) : 1.f));
             const float sxy2 = sdx * sdx + sdy * sdy;
+            // The ring pass moves far sources into fp64; it drops what pass 0 dropped, so R and R's term are pass 0's.  Where that term ALONE exceeds what the ring pass's
+            // test will admit (its ratio, at the exponent coff + g_l2 + ring) the ring pass is lost work: the block goes straight to the all-fp64 pass (tier_pass_runs).
+            const float ratio_ring = uniform_f32((float)P.far_redo_ratio * (P.tier_u0 > 0.f ? fminf(1.f, P.tier_u0 / (coff + tp.g_l2 + ring_l2)) : 1.f));
+            bool hopeless = false;
 #pragma unroll
             for (int e = 0; e < NPT; e++) {
                 const double x0 = ax[e] + (double)fx[e / 2][e & 1] * e0, x1 = ay[e] + (double)fy[e / 2][e & 1] * e0, x2 = az[e] + (double)fz[e / 2][e & 1] * e0;
                 // |w_*| e^{-lambda r} / r in the block's scale 2^-k0:  2^(-lambda' r - k0) lambda' / (lambda' r)      (the node on s*: inf * 0 = NaN -- compares false, X is NaN there itself)
                 const float dz = e * cellq + sdz0, d2 = fmaf(dz, dz, sxy2), rinv = __builtin_amdgcn_rsqf(d2);
                 const float tstar = r_drop > 0.f ? rs * __builtin_amdgcn_exp2f(-d2 * rinv - k0_here) * rinv : 0.f;
-                fail = fail || (live_xy && kk0 + e < P.kk_end && fma((double)fl[e / 2][e & 1], e0, (double)tstar) > (double)ratio_f * sqrt(x0 * x0 + x1 * x1 + x2 * x2));
+                const double nrm = sqrt(x0 * x0 + x1 * x1 + x2 * x2);
+                fail = fail || (live_xy && kk0 + e < P.kk_end && fma((double)fl[e / 2][e & 1], e0, (double)tstar) > (double)ratio_f * nrm);
+                hopeless = hopeless || (live_xy && kk0 + e < P.kk_end && (double)tstar > (double)ratio_ring * nrm);
             }
             if (__ballot(fail) == 0ull) break;
+            drop_fails = __ballot(hopeless) != 0ull;
 #pragma unroll
-            for (int e = 0; e < NPT / 2; e++) fx[e] = fy[e] = fz[e] = float2v{0.f, 0.f};
-            // (the fp64 accumulators hold flushed packed-fp32 sums: the second pass starts from nothing and takes every source in fp64)
+            for (int e = 0; e < NPT / 2; e++) fx[e] = fy[e] = fz[e] = fl[e] = float2v{0.f, 0.f};
+            // (the fp64 accumulators hold flushed packed-fp32 sums: the next pass starts from nothing -- cleared sums, an empty far list (the end-of-pass drain left no
+            // carry), no source pending a flush)
+            far_pending = 0;
 #pragma unroll
             for (int e = 0; e < NPT; e++) ax[e] = ay[e] = az[e] = 0.;
         }

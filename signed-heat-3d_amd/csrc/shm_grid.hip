@@ -55,7 +55,7 @@ shm_status shm_step1_plane_weights(const shm_sources* src, const shm_grid* grid,
         return SHM_ERR_INVALID;
     const char* tl = shm::knob("SHM_CONV_TIER_LOG");
     try {
-        shm::step1_plane_weights_host(src->S, src->pos, src->wnormal, src->lambda, grid->n, grid->bbox_min, grid->cell, precision, tl ? atof(tl) : 8.0, weights,
+        shm::step1_plane_weights_host(src->S, src->pos, src->wnormal, src->lambda, grid->n, grid->bbox_min, grid->cell, precision, tl ? atof(tl) : shm::kTierLogDefault, weights,
                                       precision == SHM_F32 && shm::knob("SHM_CONV32_CLASSIC") == nullptr);
     } catch (const std::bad_alloc&) {
         return SHM_ERR_NOMEM;

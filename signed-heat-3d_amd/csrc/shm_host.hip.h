@@ -25,6 +25,7 @@
 
 #include "../../include/shm_grid.h"
 #include "shm_constraints.h"   // Row
+#include "shm_tier_passes.h"   // kTierLogDefault, kTierRingDefault
 
 namespace shm {
 

@@ -86,6 +86,7 @@ struct Solver final : SolverBase {
     int64_t S = 0;
     std::vector<double> h_pos, h_wn, h_area;
     double area_sum = 0., conv_far_gap = 0., conv_skip_base = 3.0e38, last_host_setup_ms = 0., last_setup_wall_ms = 0.;
+    double conv_tier_ring = 0.;   // tiered fp64 Step 1: width (nats) of the ring pass behind a failed a-posteriori test (shm_tier_passes.h; 0: none)
     double conv_tier_log = 0., conv_tier_skip_base = 3.0e38;   // tiered fp64 Step 1: far threshold G (nats) and the drop threshold of rounds 3-5, ln(S / eps)
     double conv_drop_K = 64., conv_drop_eps64 = 2e-9, conv_drop_eps32 = 6.0e-8;   // tiered kernels, round 6: the accumulated drop rule (drop_rule_plan)
     double conv_w_span = 0.;                                   // ln(largest / smallest non-zero source weight)
@@ -391,7 +392,10 @@ struct Solver final : SolverBase {
                 // below 2e-9 of the dominant term are dropped (max|dY| does not move between 1.6e-13 and 2e-9: tools/tier_robustness.py).
                 // SHM_CONV_EXACT=1: every pair in the reference's fp64 arithmetic (conv_normalize_kernel<double>; Y to 1e-11 of the C oracle).
                 const char* tl = knob("SHM_CONV_TIER_LOG");
-                conv_tier_log = tl ? atof(tl) : 8.0;
+                conv_tier_log = tl ? atof(tl) : kTierLogDefault;
+                // a block that fails the a-posteriori test is first walked again with the threshold this much higher (the ring pass: shm_tier_passes.h)
+                const char* tr = knob("SHM_CONV_TIER_RING");
+                conv_tier_ring = std::max(0.0, tr ? atof(tr) : kTierRingDefault);
                 conv_tier_skip_base = sk ? 3.0e38 : std::log((double)S / 2e-9);
                 // Round 6 -- the tiered kernels drop by ACCUMULATED bound (shm_conv_tiered.hip.h): budgets eps (same values as above: 2e-9 of the dominant term in the fp64
                 // solve, one fp32 rounding unit in the fp32 solve; 0: nothing is dropped), and K, the number of sources a block is expected to find near the threshold -- the
@@ -765,6 +769,7 @@ struct Solver final : SolverBase {
             const double budget = step1_budget > 0. ? step1_budget : kTierBudget;
             const double g_shift = std::log(budget / kTierBudget);
             P.tier_log = conv_tier_exact ? 3.0e38f : conv_tiered32 ? -1.0e30f : (float)std::max(2.0, conv_tier_log - g_shift);   // (fp32 solve: every kept source that stays in the fp32 exponent range is "far")
+            P.tier_ring = conv_tier_exact || conv_tiered32 ? 0.f : (float)conv_tier_ring;   // (G + ring moves with the budget as G does; one pass where nothing is "far" or nothing is tested)
             P.wscale = conv_wscale;
             {   // a-posteriori test of the packed-fp32 tier (shm_conv_tiered.hip.h): budget on Y / calibrated relative error of a far term as it shows up in X
                 const double ratio = budget / kTierEpsFar;
