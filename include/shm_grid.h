@@ -250,6 +250,12 @@ shm_status shm_grid_get_constraints(shm_solver* s, int64_t* nodes, double* coeff
  * beside the tiered Step 1, 8192 otherwise), or wherever it fits under the experiment knob SHM_DUAL_DENSE_S_ALWAYS.  SHM_ERR_STATE when S would be applied
  * through the grid instead: several slabs, n = 2^k where the estimate says so or n > 512, or too many rows.  Test entry point (world==1). */
 shm_status shm_grid_get_schur(shm_solver* s, double* out, int32_t* m);
+/* u = S^-1 rhs for the caller's dense symmetric positive definite S (m x m doubles, row-major, on the host; 1 <= m <= 4096), computed as the direct dual
+ * solve computes it: form 0 factors S = L D L^T by 64 x 64 blocks, inverts the diagonal superblocks of L and solves by a fixed sequence of dense mat-vecs
+ * (csrc/shm_ldl_plan.h; m <= 4032), form 1 forms the explicit inverse by the blocked Gauss-Jordan and applies it.  *flag != 0: a pivot was not positive (S is
+ * not positive definite) and u is meaningless; the call still returns SHM_OK.  Test entry point, added within ABI 5 (detect it by its symbol), world==1; it
+ * needs no problem and leaves the handle's problem, set-up and phi alone. */
+shm_status shm_grid_spd_solve(shm_solver* s, const double* S, int32_t m, const double* rhs, int32_t form, double* u, int32_t* flag);
 /* v <- v - A^T (A A^T)^-1 A v on the device (the projector inside the CG); v: n^3 doubles, world==1. */
 shm_status shm_grid_apply_projector(shm_solver* s, double* v);
 

@@ -194,6 +194,12 @@ shm_status shm_grid_get_schur(shm_solver* s, double* out, int32_t* m) {
         s->impl->get_schur(out, m);
     });
 }
+shm_status shm_grid_spd_solve(shm_solver* s, const double* S, int32_t m, const double* rhs, int32_t form, double* u, int32_t* flag) {
+    return guard(s, [&] {
+        if (!S || !rhs || !u || !flag) throw shm::Error(SHM_ERR_INVALID, "null argument");
+        s->impl->spd_solve(S, m, rhs, form, u, flag);
+    });
+}
 shm_status shm_grid_apply_projector(shm_solver* s, double* v) {
     return guard(s, [&] {
         if (!v) throw shm::Error(SHM_ERR_INVALID, "null argument");

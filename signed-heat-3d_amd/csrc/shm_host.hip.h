@@ -558,6 +558,7 @@ struct SolverBase {
     virtual void apply_projector(double*) = 0;
     virtual void apply_preconditioner(const double*, double*) = 0;
     virtual void get_schur(double*, int32_t*) = 0;
+    virtual void spd_solve(const double*, int32_t, const double*, int32_t, double*, int32_t*) = 0;
     virtual void isosurface(double, int, int64_t*, int64_t*) = 0;
     virtual void get_isosurface(double*, int64_t*) = 0;
     virtual void sample(int64_t, const double*, double*, double*, int64_t*) = 0;

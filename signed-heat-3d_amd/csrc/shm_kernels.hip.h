@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "shm_constraints.h"   // kWave, kGJ, ShiftItem
+#include "shm_ldl_plan.h"
 #include "shm_mc_table.h"
 
 namespace shm {
@@ -1850,162 +1851,106 @@ __global__ __launch_bounds__(kBlock) void gj_update_kernel(double* __restrict__ 
 #endif
 constexpr int kGjStepScratch = 8 * (kGJ + 1);
 constexpr int kGjStepLds = kGJ * (kGJ + 1) + kGjStepScratch;
-static __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SHM_GJ_STEP_WAVES, SHM_GJ_STEP_WAVES))) void gj_step_kernel(
-    double* __restrict__ G, int ld, int nb, int k, const double* __restrict__ Rp /* [64][ld] of step k-1 */, const double* __restrict__ Cp /* [ld][64] */,
-    double* __restrict__ Rn, double* __restrict__ Cn, int* __restrict__ flag, int prio) {
-    __shared__ double smem[kGjStepLds];
-    static_assert(kGjStepLds >= kGjUpdateLds && kGjStepScratch >= 8 * kGJ, "LDS carve");
+// Second mode, gj_ldl_step_kernel (kGjStepLdl; shm_ldl_plan.h): the same chain link confined to the trailing matrix -- the block factorisation S = L D L^T instead of
+// the inverse.  Launch k < nb:
+//   * panel role, workgroups [0, nb - k), block b = k + blockIdx.x: b == k inverts the pivot tile and stores P_k = D_k^-1 in Pd[k] (the pivot tile itself is still being
+//     read by the others); b > k forms X_b = S_bk P_k as before (R_k[:, b] = X_b^T, C_k[b] = S_bk);
+//   * store role, the next nb - k workgroups (k >= 1): X_b of step k-1 from R_k-1 into tile (b, k-1), b >= k -- L's block column k-1;
+//   * update role: step k-1's update of the tiles bi >= bj >= k+1 only.
+// Same products, operand order and pivot inversion; there is no launch nb.  The body is shm_gj_step.inc.h, included once per mode (see there).
+enum GjStepMode : int { kGjStepInverse = 0, kGjStepLdl = 1 };
+#define SHM_GJ_STEP_NAME gj_step_kernel
+#define SHM_GJ_STEP_MODE 0
+#define SHM_GJ_STEP_EXTRA_PARAM
+#include "shm_gj_step.inc.h"
+#undef SHM_GJ_STEP_NAME
+#undef SHM_GJ_STEP_MODE
+#undef SHM_GJ_STEP_EXTRA_PARAM
+#define SHM_GJ_STEP_NAME gj_ldl_step_kernel
+#define SHM_GJ_STEP_MODE 1
+#define SHM_GJ_STEP_EXTRA_PARAM , double* __restrict__ Pd /* [nb][64][64] */
+#include "shm_gj_step.inc.h"
+#undef SHM_GJ_STEP_NAME
+#undef SHM_GJ_STEP_MODE
+#undef SHM_GJ_STEP_EXTRA_PARAM
+
+// The diagonal superblocks of L (unit block lower triangular), inverted in place: launch t of shm_ldl_plan.h's chain, blockIdx.y = superblock.  N = I - L_qq^-1:
+// N[t][j] = L[t][j] - sum_{j < l < t} L[t][l] N[l][j] is one gj_update_tile with K = 64 (t - j - 1), its C operand the copy of L's row t that launch t-1 left in
+// panel t & 1 (the tiles of row t are rewritten here while their neighbours would still read them), its R operand the finished rows above.
+// panels: [superblock][2][64][pld] doubles, pld = 64 * the longest superblock.
+static __global__ __launch_bounds__(kBlock) void ldl_tri_kernel(double* __restrict__ F, int ld, shm::LdlPlan plan, int t, double* __restrict__ panels, int pld, int prio) {
+    __shared__ double smem[kGjUpdateLds];
     if (prio) __builtin_amdgcn_s_setprio(3);   // (see gj_panels_kernel)
-    const int nN = k < nb ? nb : 0;
-    if ((int)blockIdx.x >= nN) {
-        // ---- update role: step k-1 on every tile (bi >= bj) without a block index k
-        int bi, bj;
-        gj_tri_decode(blockIdx.x - (unsigned)nN, bi, bj);   // over nb - 1 blocks (k < nb) or all nb (last launch)
-        if (k < nb) {
-            if (bi >= k) bi += 1;
-            if (bj >= k) bj += 1;
-        }
-        gj_update_tile(G, ld, bi, bj, k - 1, Rp, 0, Cp, kGJ, 0, kGJ, smem);
+    const int q = blockIdx.y, s = plan.len(q), xw = blockIdx.x;
+    double* Fq = F + ((size_t)plan.start[q] * kGJ) * ld + (size_t)plan.start[q] * kGJ;
+    double* pan = panels + (size_t)q * 2 * kGJ * pld;
+    if (xw < shm::ldl_tri_compute_count(t)) {
+        if (t >= s) return;
+        const int j = xw;
+        // (gj_update_tile addresses C by the tile's row block t; the panel holds that row block alone, so its base is moved back by t row blocks)
+        const double* Crow = pan + (size_t)(t & 1) * kGJ * pld - (size_t)t * kGJ * pld;
+        gj_update_tile(Fq, ld, t, j, -1, Fq, (j + 1) * kGJ, Crow, pld, (j + 1) * kGJ, (t - j - 1) * kGJ, smem);
         return;
     }
-    // ---- panel role
-    double(*x)[kGJ + 1] = reinterpret_cast<double(*)[kGJ + 1]>(smem);
-    double* scratch = smem + kGJ * (kGJ + 1);
-    double(*prow)[kGJ + 1] = reinterpret_cast<double(*)[kGJ + 1]>(scratch);
-    const int b = blockIdx.x;
-    const bool below = b >= k;
-    const int bi = below ? b : k, bj = below ? k : b;   // the stored tile of the cross
-    const size_t o = (size_t)k * kGJ, ob = (size_t)b * kGJ, oi = (size_t)bi * kGJ, oj = (size_t)bj * kGJ;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, wr = w >> 1, wc = w & 1, l15 = lane & 15, l4 = lane >> 4;
-    const int ty = threadIdx.x >> 4, tx = threadIdx.x & 15;
-    double r[4][4];      // the pivot tile, thread (ty, tx) owning the 4 x 4 block (ty, tx)
-    double* Cb = Cn + ob * kGJ;   // C_k[b], 64 x 64
-    if (k > 0) {
-        // accumulator layout: row = wr 32 + a 16 + l4 + 4 q, col = wc 32 + c 16 + l15.  Two products C[rows] R[:, cols], one after the other (together their
-        // accumulators and operands do not fit the register cap), each in two groups of eight k-steps whose 32 operand loads are issued together, ahead of the
-        // group's matrix instructions: left to itself the compiler waits for every k-step's loads before it issues the next ones -- 16 round trips to L2, a
-        // quarter of this role's time.
-        auto product = [&](gj_f64x4(&acc)[2][2], size_t orow, size_t ocol) {
+    if (t + 1 >= s) return;
+    const int c = xw - shm::ldl_tri_compute_count(t) + 1;
+    double* dst = pan + (size_t)((t + 1) & 1) * kGJ * pld + (size_t)c * kGJ;
+    const double* src = Fq + ((size_t)(t + 1) * kGJ) * ld + (size_t)c * kGJ;
+    for (int e = threadIdx.x; e < kGJ * kGJ; e += kBlock) {
+        const int i = e / kGJ, jj = e % kGJ;
+        dst[(size_t)i * pld + jj] = src[(size_t)i * ld + jj];
+    }
+}
+
+// One step of the solve with the factor (shm_ldl_plan.h, LdlStep): u[row] = a[row] - sum_c F[row][c] x[c] over the columns [c0, c1) -- for kLdlLower / kLdlUpper only
+// those in blocks before / after the row's own.  ginv_matvec_kernel's shape: one workgroup per row, four consecutive columns per lane and load, U loads in flight.
+template <int U>
+__global__ __launch_bounds__(kBlock) void ldl_matvec_kernel(int op, int row0, int c0, int c1, int ld, const double* __restrict__ F, const double* __restrict__ a,
+                                                           const double* __restrict__ x, double* __restrict__ u) {
+    __shared__ double lds[8];
+    const int row = row0 + blockIdx.x;
+    if (op == shm::kLdlLower) c1 = min(c1, row / kGJ * kGJ);
+    if (op == shm::kLdlUpper) c0 = max(c0, (row / kGJ + 1) * kGJ);
+    const double* g = F + (size_t)row * ld;
+    double s = 0.;
+    for (int cc = c0; cc < c1; cc += U * kBlock * 4) {
+        double gv[U][4];
 #pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int c = 0; c < 2; c++) acc[a][c] = gj_f64x4{0., 0., 0., 0.};
-#pragma unroll 1
-            for (int g = 0; g < 2; g++) {
-                double af[8][2], bf[8][2];
-#pragma unroll
-                for (int u = 0; u < 8; u++) {
-                    const int kk = 32 * g + 4 * u + l4;
-#pragma unroll
-                    for (int a = 0; a < 2; a++) af[u][a] = Cp[(orow + wr * 32 + a * 16 + l15) * kGJ + kk];
-#pragma unroll
-                    for (int c = 0; c < 2; c++) bf[u][c] = Rp[(size_t)kk * ld + ocol + wc * 32 + c * 16 + l15];
-                }
-#pragma unroll
-                for (int u = 0; u < 8; u++)
-#pragma unroll
-                    for (int a = 0; a < 2; a++)
-#pragma unroll
-                        for (int c = 0; c < 2; c++) acc[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[u][a], bf[u][c], acc[a][c], 0, 0, 0);
+        for (int e = 0; e < U; e++) {
+            const int c = cc + (threadIdx.x + e * kBlock) * 4;
+            if (c < c1) {
+                *reinterpret_cast<double2*>(gv[e]) = *reinterpret_cast<const double2*>(g + c);
+                *reinterpret_cast<double2*>(gv[e] + 2) = *reinterpret_cast<const double2*>(g + c + 2);
             }
-        };
-        {
-            gj_f64x4 accp[2][2];
-            product(accp, o, o);   // the pivot tile: G[k, k] - C[k] R[:, k]
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int c = 0; c < 2; c++)
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const size_t row = wr * 32 + a * 16 + l4 + 4 * q, col = wc * 32 + c * 16 + l15;
-                        x[row][col] = G[(o + row) * ld + o + col] - accp[a][c][q];
-                    }
-        }
-        gj_f64x4 accx[2][2];
-        product(accx, oi, oj);     // X_b: G[bi, bj] - C[bi] R[:, bj]
-        __syncthreads();
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) r[a][c] = x[ty * 4 + a][tx * 4 + c];
-        __syncthreads();
-        const double keep = b == k - 1 ? 0. : 1.;   // the tile (k, k-1) lies in the pivot column of step k-1: -C P, no base
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int c = 0; c < 2; c++)
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const size_t row = wr * 32 + a * 16 + l4 + 4 * q, col = wc * 32 + c * 16 + l15;
-                    // (keep = 0 instead of a select: a select lets the compiler branch around each load, and it then waited for the 16 loads one by one)
-                    x[row][col] = G[(oi + row) * ld + oj + col] * keep - accx[a][c][q];
-                }
-    } else {
-        for (int t = threadIdx.x; t < kGJ * kGJ; t += kBlock) {
-            const int i = t / kGJ, j = t % kGJ;
-            x[i][j] = G[(oi + i) * ld + oj + j];
         }
 #pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) r[a][c] = G[(o + ty * 4 + a) * ld + o + tx * 4 + c];
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < kGJ * kGJ; t += kBlock) {
-        const int i = t / kGJ, j = t % kGJ;
-        Cb[i * kGJ + j] = below ? x[i][j] : -x[j][i];
-    }
-    gj_invert64_scalar<4, SHM_GJ_STEP_PAIRS != 0>(r, scratch, flag);
-    if (b == k) {   // the pivot block's own R column carries P
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int c = 0; c < 4; c++) Rn[(size_t)(ty * 4 + a) * ld + ob + tx * 4 + c] = r[a][c];
-        return;
-    }
-    // P: registers -> scratch, 8 rows at a time -> the lanes that feed it to the matrix cores (rows wr 32 + a 16 + l15, k = 4 s + l4)
-    double pa[2][kGJ / 4];
-#pragma unroll
-    for (int pass = 0; pass < 8; pass++) {
-        __syncthreads();
-        if ((ty >> 1) == pass) {
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int c = 0; c < 4; c++) prow[(ty & 1) * 4 + a][tx * 4 + c] = r[a][c];
-        }
-        __syncthreads();
-        if (wr == (pass >> 2) && (l15 >> 3) == (pass & 1)) {
-#pragma unroll
-            for (int s4 = 0; s4 < kGJ / 4; s4++) pa[(pass >> 1) & 1][s4] = prow[l15 & 7][4 * s4 + l4];
+        for (int e = 0; e < U; e++) {
+            const int c = cc + (threadIdx.x + e * kBlock) * 4;
+            if (c < c1) {
+                double d = gv[e][0] * x[c];
+                if (c + 1 < c1) d += gv[e][1] * x[c + 1];
+                if (c + 2 < c1) d += gv[e][2] * x[c + 2];
+                if (c + 3 < c1) d += gv[e][3] * x[c + 3];
+                s += d;
+            }
         }
     }
-    gj_f64x4 acc[2][2];
+    s = block_sum(s, lds);
+    if (threadIdx.x == 0) u[row] = a[row] - s;
+}
+// z = D^-1 y: the block diagonal of the P_k ([nb][64][64]); one workgroup per block, four lanes per row
+static __global__ __launch_bounds__(kBlock) void ldl_diag_kernel(int m, const double* __restrict__ Pd, const double* __restrict__ y, double* __restrict__ z) {
+    const int blk = blockIdx.x, i = threadIdx.x >> 2, part = threadIdx.x & 3, row = blk * kGJ + i;
+    const double* p = Pd + (size_t)blk * kGJ * kGJ + (size_t)i * kGJ + part * 16;
+    double s = 0.;
 #pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int c = 0; c < 2; c++) acc[a][c] = gj_f64x4{0., 0., 0., 0.};
-#pragma unroll
-    for (int s4 = 0; s4 < kGJ / 4; s4++) {
-        const int kk = 4 * s4 + l4;
-        double bf[2];
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const int j = wc * 32 + c * 16 + l15;
-            bf[c] = (b > k) ? x[j][kk] : x[kk][j];   // R[:, b] = P X^T below the pivot block, P X above it
-        }
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int c = 0; c < 2; c++) acc[a][c] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[a][s4], bf[c], acc[a][c], 0, 0, 0);
+    for (int c = 0; c < 16; c++) {
+        const int col = blk * kGJ + part * 16 + c;
+        if (col < m) s += p[c] * y[col];
     }
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) Rn[(size_t)(wr * 32 + a * 16 + l4 + 4 * q) * ld + ob + wc * 32 + c * 16 + l15] = acc[a][c][q];
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    if (part == 0 && row < m) z[row] = s;
 }
 
 // after the last pivot block: G[bj, bi] = G[bi, bj]^T for bi > bj (the inverse is symmetric; only its block-lower triangle was kept)

@@ -6,8 +6,10 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 
 #include "../../include/shm_grid.h"
+#include "shm_ldl_plan.h"
 
 namespace shm {
 
@@ -19,6 +21,7 @@ struct PlanKnobs {
     bool no_direct = false;        // SHM_DUAL_NO_DIRECT: never the direct solve
     bool no_dense_s = false;       // SHM_DUAL_NO_DENSE_S: never the explicit S (S applied through the grid)
     bool dense_s_always = false;   // SHM_DUAL_DENSE_S_ALWAYS: the explicit S wherever it fits, whatever Step 1 hides
+    int s_form = 0;                // SHM_S_FORM=invert / factor: the direct solve keeps the explicit S^-1 (blocked Gauss-Jordan) / factors S = L D L^T wherever that applies; 0: the default
     int tl_min_m = 6144;           // SHM_TL_MIN_M: dense G^-1 up to here (m^2 fp32 = 150 MB: L2 / MALL friendly, 3 launches), two-level beyond
 };
 template <typename Get> PlanKnobs plan_knobs(Get knob) {
@@ -26,9 +29,13 @@ template <typename Get> PlanKnobs plan_knobs(Get knob) {
     k.no_direct = knob("SHM_DUAL_NO_DIRECT") != nullptr;
     k.no_dense_s = knob("SHM_DUAL_NO_DENSE_S") != nullptr;
     k.dense_s_always = knob("SHM_DUAL_DENSE_S_ALWAYS") != nullptr;
+    const char* s_form = knob("SHM_S_FORM");
+    if (s_form != nullptr) k.s_form = std::strcmp(s_form, "invert") == 0 ? 1 : std::strcmp(s_form, "factor") == 0 ? 2 : 0;
     if (knob("SHM_TL_MIN_M")) k.tl_min_m = atoi(knob("SHM_TL_MIN_M"));
     return k;
 }
+
+constexpr bool kSFactorDefault = true;   // the direct solve's form of S^-1 without SHM_S_FORM: the factorisation (plan_rows)
 
 struct PlanIn {
     bool f64 = true;                 // precision of the handle
@@ -59,6 +66,7 @@ struct Plan {
     int dual_form = SHM_DUAL_THROUGH_GRID;   // DIRECT / EXPLICIT_S_CG / THROUGH_GRID (plan_rows)
     bool explicit_S = false;         // S is assembled (the direct and explicit-S forms; plan_rows)
     bool two_level = false;          // G^-1 two-level (plan_rows)
+    bool s_factor = false;           // the direct solve factors S = L D L^T (shm_ldl_plan.h) instead of inverting it (plan_rows)
     double est_setup_ms = -1., est_step1_ms = -1.;   // the estimates the direct solve was weighed with (-1: not weighed)
 };
 
@@ -193,6 +201,10 @@ template <typename Est> void plan_rows(const PlanIn& in, int m, Est step1_ms, Pl
     p.explicit_S = plan_explicit_S(in, m, direct);
     p.dual_form = direct ? SHM_DUAL_DIRECT : p.explicit_S ? SHM_DUAL_EXPLICIT_S_CG : SHM_DUAL_THROUGH_GRID;
     p.two_level = !direct && m > in.knobs.tl_min_m;
+    // the direct solve applies S^-1 to two vectors per set-up: where the single-level Gauss-Jordan would run (fewer than 64 pivot blocks) the factorisation with
+    // inverted diagonal superblocks does a third of its work (ldl_tile_products against gj_tile_products); larger S keep the inverse
+    // (measured: profiles/NOTES_r10.md)
+    p.s_factor = direct && (in.knobs.s_form == 2 || (in.knobs.s_form == 0 && kSFactorDefault)) && ldl_applies((m + kLdlTile - 1) / kLdlTile);
 }
 
 inline const char* plan_path_name(PlanPath path) {

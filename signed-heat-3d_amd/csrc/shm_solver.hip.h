@@ -171,6 +171,8 @@ struct Solver final : SolverBase {
     std::vector<int> h_rowX;
     bool have_S = false;
     DevArray<double> Sinv, Sinv_ones /* S^-1 1: the border of the direct solve, formed once per set-up behind the inversion */;
+    // plan.s_factor: Sinv holds the factor of S = L D L^T instead (enqueue_ldl_factor); the P_k = D_k^-1, the row panels of the superblock inverses, y / t / z of apply_ldl
+    DevArray<double> ldlP, ldlPanels, ldlWork;
     PlanIn plan_in;   // the inputs and the plan of the set-up in progress (shm_plan.h): given to build_constraints(), read by the stages after it
     Plan plan;
     double conv_est_total_ms = 1e30;   // estimate of this rank's last Step-1 launch (1e30: none was launched -- stand-alone set-up, test entry points)
@@ -1388,6 +1390,45 @@ struct Solver final : SolverBase {
         if (nb > 1) hipLaunchKernelGGL(gj_mirror_kernel, dim3((unsigned)((size_t)nb * (nb - 1) / 2)), dim3(kBlock), 0, stream, M, mp);
         HIPCHK(hipGetLastError());
     }
+    // S = L D L^T in place of the SPD matrix M (mp x mp, identity tail) on the set-up stream, for apply_ldl(): the plan is shm_ldl_plan.h.  nb launches of the
+    // elimination confined to the trailing matrix (gj_ldl_step_kernel: L below the diagonal, P_k = D_k^-1 in Pd), the chain that inverts the diagonal superblocks of L
+    // in place, and the mirror, after which the backward sweep reads rows as the forward sweep does.  A non-positive pivot raises gjFlag[0] as in enqueue_gj_invert.
+    void enqueue_ldl_factor(double* M, int mp, DevArray<double>& Pd, DevArray<double>& panels) {
+        hipStream_t stream = stream2;
+        const int nb = mp / kGJ;
+        const LdlPlan lp = ldl_plan(nb);
+        gjR.alloc((size_t)2 * kGJ * mp);
+        gjC.alloc((size_t)2 * mp * kGJ);
+        gjFlag.alloc(2);
+        Pd.alloc((size_t)nb * kGJ * kGJ);
+        HIPCHK(hipMemsetAsync(gjFlag.p, 0, sizeof(int), stream));
+        for (int k = 0; k < nb; k++) {
+            const unsigned grid = (unsigned)(ldl_panel_count(nb, k) + ldl_store_count(nb, k) + ldl_update_count(nb, k));
+            double* Rn = gjR.p + (size_t)(k & 1) * kGJ * mp;
+            double* Cn = gjC.p + (size_t)(k & 1) * mp * kGJ;
+            const double* Rp = gjR.p + (size_t)((k + 1) & 1) * kGJ * mp;
+            const double* Cp = gjC.p + (size_t)((k + 1) & 1) * mp * kGJ;
+            hipLaunchKernelGGL(gj_ldl_step_kernel, dim3(grid), dim3(kBlock), 0, stream, M, mp, nb, k, Rp, Cp, Rn, Cn, gjFlag.p, plan.setup_prio, Pd.p);
+        }
+        const int pld = lp.max_len() * kGJ;
+        panels.alloc((size_t)lp.B * 2 * kGJ * pld);
+        for (int t = 1; t <= ldl_tri_launches(lp); t++)
+            hipLaunchKernelGGL(ldl_tri_kernel, dim3((unsigned)ldl_tri_grid(t), (unsigned)lp.B), dim3(kBlock), 0, stream, M, mp, lp, t, panels.p, pld, plan.setup_prio);
+        if (nb > 1) hipLaunchKernelGGL(gj_mirror_kernel, dim3((unsigned)((size_t)nb * (nb - 1) / 2)), dim3(kBlock), 0, stream, M, mp);
+        HIPCHK(hipGetLastError());
+    }
+    // u = S^-1 w with the factor (rows and columns clipped to m: the tail is the identity): the 4 B - 1 steps of ldl_solve_step().  work: 3 mp doubles; w != u.
+    void apply_ldl(hipStream_t st, int m, int mp, const double* F, const double* Pd, double* work, const double* w, double* u) {
+        const LdlPlan lp = ldl_plan(mp / kGJ);
+        auto vec = [&](int v) -> double* { return v == kLdlW ? const_cast<double*>(w) : v == kLdlU ? u : work + (size_t)(v - kLdlY) * mp; };
+        for (int i = 0; i < ldl_solve_steps(lp); i++) {
+            const LdlStep s = ldl_solve_step(lp, i);
+            const int r0 = s.rb0 * kGJ, r1 = std::min(s.rb1 * kGJ, m), c0 = s.cb0 * kGJ, c1 = std::min(s.cb1 * kGJ, m);
+            if (r1 <= r0) continue;
+            if (s.op == kLdlDiag) hipLaunchKernelGGL(ldl_diag_kernel, dim3((unsigned)((m + kGJ - 1) / kGJ)), dim3(kBlock), 0, st, m, Pd, vec(s.x), vec(s.u));
+            else hipLaunchKernelGGL(ldl_matvec_kernel<4>, dim3((unsigned)(r1 - r0)), dim3(kBlock), 0, st, s.op, r0, c0, c1, mp, F, vec(s.a), vec(s.x), vec(s.u));
+        }
+    }
     void enqueue_invert_G() {
         const int mp = ginv_ld;  // dense inverse: the padded m; two-level: the padded separator size
         enqueue_gj_invert(Ginv.p, mp);
@@ -1538,10 +1579,14 @@ struct Solver final : SolverBase {
             Sinv.alloc((size_t)mp * mp);
             HIPCHK(hipMemcpyAsync(Sinv.p, Sdense.p, (size_t)mp * mp * sizeof(double), hipMemcpyDeviceToDevice, st));
             if (mp > m) hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((mp - m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Sinv.p, mp, m, mp, 1.0);   // identity tail
-            enqueue_gj_invert(Sinv.p, mp, true);
+            if (plan.s_factor) enqueue_ldl_factor(Sinv.p, mp, ldlP, ldlPanels);
+            else enqueue_gj_invert(Sinv.p, mp, true);
             Sinv_ones.alloc((size_t)2 * mp);
             hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, Sinv_ones.p + mp, m, 1.0);
-            launch_ginv_matvec<double>(st, m, m, mp, Sinv.p, Sinv_ones.p + mp, Sinv_ones.p);
+            if (plan.s_factor) {
+                ldlWork.alloc((size_t)3 * mp);
+                apply_ldl(st, m, mp, Sinv.p, ldlP.p, ldlWork.p, Sinv_ones.p + mp, Sinv_ones.p);
+            } else launch_ginv_matvec<double>(st, m, m, mp, Sinv.p, Sinv_ones.p + mp, Sinv_ones.p);
         } else {
             e_sch_done->record(st);
             HIPCHK(hipStreamWaitEvent(stream2, e_sch_done->e, 0));   // "set-up done" on stream2 (what the solve waits for) now includes S
@@ -2358,7 +2403,11 @@ struct Solver final : SolverBase {
             // u = S^-1 r, v = S^-1 1 (formed behind the inversion, in the set-up), delta = u - (1^T u / 1^T v) v;  then r = Pm(g - S mu) again with the explicit S.
             // The first pass IS the solution (cond(S) ~ 5e2 ... 7e4 on the bunny grids: 1e-12 and better); further passes are iterative refinement, taken only
             // while the residual test of the CG path -- the same one -- is not met.
-            auto apply_Sinv = [&](const double* w, double* u) { launch_ginv_matvec<double>(stream, m, m, mp, Sinv.p, w, u); };
+            // (plan.s_factor: S^-1 w through the factor S = L D L^T -- the sweeps of apply_ldl over the same bytes)
+            auto apply_Sinv = [&](const double* w, double* u) {
+                if (plan.s_factor) apply_ldl(stream, m, mp, Sinv.p, ldlP.p, ldlWork.p, w, u);
+                else launch_ginv_matvec<double>(stream, m, m, mp, Sinv.p, w, u);
+            };
             // At most six passes, and never more than max_iters.  A tolerance below what the arithmetic can deliver (about eps * cond(S): cond is 5e2 ... 7e4
             // here) would otherwise end in SHM_ERR_NOCONV although mu is at rounding accuracy: when a pass no longer reduces the residual by at least a
             // factor of four and the residual already sits below 1e-9 of the right-hand side, the stagnation IS convergence; rel_residual reports what was reached.
@@ -2971,6 +3020,39 @@ struct Solver final : SolverBase {
         if (!have_S) throw Error(SHM_ERR_STATE, "no explicit Schur complement for this problem (several slabs, more than 16384 rows, or n = 2^k where the plan applies S through the grid: n > 512, or the estimate of plan_explicit_S without SHM_DUAL_DENSE_S_ALWAYS)");
         HIPCHK(hipMemcpy2DAsync(out, (size_t)m * sizeof(double), Sdense.p, (size_t)mp * sizeof(double), (size_t)m * sizeof(double), (size_t)m, hipMemcpyDeviceToHost, stream2));
         HIPCHK(hipStreamSynchronize(stream2));
+    }
+
+    // Test entry point: u = S^-1 rhs for a caller's dense SPD matrix (m x m, row-major, host), through the set-up and the apply of the direct dual solve -- the
+    // factorisation S = L D L^T (form 0: enqueue_ldl_factor, apply_ldl) or the blocked Gauss-Jordan inverse and its mat-vec (form 1).  *flag: the device flag of a
+    // non-positive pivot (u is then meaningless, nothing is thrown).  Arrays of its own; the handle's problem and set-up are left alone.
+    void spd_solve(const double* S, int32_t m_, const double* rhs, int32_t form, double* u, int32_t* flag) override {
+        if (cfg.world != 1) throw Error(SHM_ERR_INVALID, "spd_solve is a single-process test entry point");
+        if (m_ < 1 || m_ > 4096 || (form != 0 && form != 1)) throw Error(SHM_ERR_INVALID, "spd_solve: m in [1, 4096], form 0 (factor) or 1 (invert)");
+        const int mp_ = (m_ + kGJ - 1) / kGJ * kGJ;
+        if (form == 0 && !ldl_applies(mp_ / kGJ)) throw Error(SHM_ERR_INVALID, "spd_solve: the factorisation serves fewer than 64 pivot blocks");
+        HIPCHK(hipSetDevice(cfg.device));
+        hipStream_t st = stream2;
+        DevArray<double> M, Pd, panels, vecs;
+        M.alloc((size_t)mp_ * mp_);
+        vecs.alloc((size_t)5 * mp_);
+        HIPCHK(hipMemsetAsync(M.p, 0, (size_t)mp_ * mp_ * sizeof(double), st));
+        HIPCHK(hipMemsetAsync(vecs.p, 0, (size_t)5 * mp_ * sizeof(double), st));
+        HIPCHK(hipMemcpy2DAsync(M.p, (size_t)mp_ * sizeof(double), S, (size_t)m_ * sizeof(double), (size_t)m_ * sizeof(double), (size_t)m_, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(vecs.p, rhs, (size_t)m_ * sizeof(double), hipMemcpyHostToDevice, st));
+        if (mp_ > m_) hipLaunchKernelGGL(set_diagonal_kernel, dim3((unsigned)((mp_ - m_ + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, M.p, mp_, m_, mp_, 1.0);   // identity tail
+        if (form == 0) {
+            enqueue_ldl_factor(M.p, mp_, Pd, panels);
+            apply_ldl(st, m_, mp_, M.p, Pd.p, vecs.p + 2 * (size_t)mp_, vecs.p, vecs.p + mp_);
+        } else {
+            enqueue_gj_invert(M.p, mp_, true);
+            launch_ginv_matvec<double>(st, m_, m_, mp_, M.p, vecs.p, vecs.p + mp_);
+        }
+        HIPCHK(hipGetLastError());
+        int f = 0;
+        HIPCHK(hipMemcpyAsync(&f, gjFlag.p, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(u, vecs.p + mp_, (size_t)m_ * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        *flag = f;
     }
 
     void apply_projector(double* v) override {

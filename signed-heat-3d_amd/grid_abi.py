@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 # every symbol include/shm_grid.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
-               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
+               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
@@ -156,6 +156,8 @@ def load_library():
     lib.shm_grid_set_phi.argtypes = [C.c_void_p, C.c_void_p]
     lib.shm_grid_get_constraints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.shm_grid_get_schur.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+    if hasattr(lib, "shm_grid_spd_solve"):   # (a test entry point added within ABI 5: an older build named by SHM_GRID_LIB does without it)
+        lib.shm_grid_spd_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
     lib.shm_grid_apply_projector.argtypes = [C.c_void_p, C.c_void_p]
     lib.shm_grid_apply_preconditioner.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shm_grid_isosurface.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -380,6 +382,19 @@ class GridSolver:
         self._chk(self._lib.shm_grid_get_schur(self._h, out.ctypes.data, C.byref(mm)))
         assert mm.value == m
         return out
+
+    def spd_solve(self, S, rhs, form="factor"):
+        """(u, flag): u = S^-1 rhs for a dense SPD matrix through the set-up and apply of the direct dual solve (shm_grid_spd_solve): form "factor" (S = L D L^T) or
+        "invert" (the explicit inverse); flag != 0 reports a non-positive pivot.  Test entry point; no problem needed."""
+        S = np.ascontiguousarray(S, dtype=np.float64)
+        rhs = np.ascontiguousarray(rhs, dtype=np.float64).reshape(-1)
+        m = S.shape[0]
+        if S.shape != (m, m) or rhs.size != m:
+            raise ValueError("spd_solve: S must be m x m and rhs hold m values")
+        u = np.empty(m, dtype=np.float64)
+        flag = C.c_int32(0)
+        self._chk(self._lib.shm_grid_spd_solve(self._h, S.ctypes.data, m, rhs.ctypes.data, {"factor": 0, "invert": 1}[form], u.ctypes.data, C.byref(flag)))
+        return u, flag.value
 
     def apply_projector(self, v):
         v = _f64(v).reshape(-1).copy()
