@@ -575,7 +575,7 @@ shm_status shm_grid_isosurface_indexed_psi(shm_solver* s, double distance, int64
  *   one rounding per coordinate.  A query is answered iff dist < max_dist.  The minimum and the tie rule commute, so the answer is a function of M, q and
  *   max_dist alone: two calls give bit-identical buffers, and neither local_slabs nor the order in which the device meets the triangles can show.
  * The distance is UNSIGNED.  At a grid node the sign is phi < isovalue; at an arbitrary point the trilinear zero set and the marching-cubes mesh disagree
- *   within a cell, and a sign consistent with the mesh needs pseudonormals: not provided.
+ *   within a cell.  A sign consistent with the mesh is the parity of shm_grid_mesh_raycast's count (below): odd along a ray on which M is closed means inside.
  * Outputs, every entry written, in input order: dist_out[q]; cp_out (optional) the foot point; tri_out (optional) the triangle id, an index into the
  *   triangles of shm_grid_get_isosurface_indexed.  Unanswered entries hold NaN, NaN x 3 and -1.  *n_answered counts the finite answers.
  * A query may lie anywhere, outside the box included: it is answered iff M is within max_dist of it.  A query with a non-finite coordinate is unanswered,
@@ -608,6 +608,45 @@ shm_status shm_grid_closest_point(shm_solver* s, int64_t Q, const double* pts /*
                                   double* cp_out /* [3Q] or NULL */, int64_t* tri_out /* [Q] or NULL */, int64_t* n_answered);
 shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d_pts, double max_dist, void* d_dist, void* d_cp /* or NULL */,
                                          void* d_tri /* int64, or NULL */, int64_t* n_answered);
+
+/* --- ray casts against the resident indexed mesh ----------------------------------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * shm_grid_raycast intersects the trilinear level set of phi; this call intersects M, the mesh in the indexed slot (as shm_grid_closest_point reads it:
+ *   whatever is there, filtered or offset meshes included), names the triangle it hit and counts the crossings.  Kernels in csrc/shm_mesh_raycast.hip.h.
+ * The rule (csrc/shm_ray_tri.h; fp64, no contraction, sums of three terms taken (x + y) + z), for the ray o + t d, d not normalised, and a triangle whose
+ *   corners MINUS o are A, B, C:  kz = argmax |d_a| (ties to the lowest axis), kx, ky the next two axes cyclically, swapped when d[kz] < 0;
+ *   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz];  per corner Px = P[kx] - Sx P[kz], Py = P[ky] - Sy P[kz], Pz = Sz P[kz];
+ *   U = Cx By - Cy Bx, V = Ax Cy - Ay Cx, W = Bx Ay - By Ax.  A zero edge function takes the sign it has when the ray is displaced by (eps, eps^2) in the
+ *   sheared plane, eps -> 0+: for U sign(Cy - By), if that is zero sign(Bx - Cx), if both are zero the triangle is refused; V and W cyclically.
+ *   Hit iff the three adjusted signs agree, det = (U + V) + W != 0 and t_min <= t <= t_max with t = ((U Az + V Bz) + W Cz) / det;
+ *   (u, v) = (V / det, W / det), the point being (1 - u - v) A + u B + v C.  No face is culled; det has the sign of -(d . N), N = (B - A) x (C - A).
+ * Answer for a ray: t = min over the accepted triangles of M; tri = the SMALLEST triangle id attaining it; (u, v) that triangle's; count = the number of
+ *   accepted triangles.  A function of M, the ray and [t_min, t_max] alone: two calls give bit-identical buffers, whatever local_slabs is.
+ * Watertightness: the edge function of a shared edge is in one triangle bit for bit the negative of what it is in the other, and so is what the zero rule
+ *   reads.  On a closed, consistently oriented manifold a ray through a shared edge or vertex is counted once, a ray grazing a silhouette edge 0 or 2
+ *   times, a zero-area triangle never.  count & 1 is therefore inside / outside -- where M is closed along the ray.  A component that reaches the box is
+ *   open there (touches_box in shm_iso_component says so), and parity along a ray that leaves through such a hole means nothing.
+ * Outputs, every entry written, in input order: t_out[q]; tri_out (optional), an index into the triangles of shm_grid_get_isosurface_indexed; bary_out
+ *   (optional) u, v interleaved; count_out (optional, int32), always written, 0 for a miss.  A miss holds NaN, -1, NaN x 2.  Misses, not errors: a
+ *   non-finite origin or direction, d = 0, t_min > t_max (or a NaN among them).  t_max = +inf is valid.  *n_hits counts the hits.
+ *   Without count_out a ray stops at the first layer of cells that begins behind its nearest hit; with it the ray runs to t_max or out of the box.
+ * Errors: SHM_ERR_INVALID for Q < 0, Q > 2^48, or NULL origins / dirs / t_out with Q > 0.  Q = 0 is valid.  SHM_ERR_STATE without a valid indexed mesh and
+ *   with world > 1, as shm_grid_closest_point.  An empty mesh is SHM_OK with no hits.  Nothing else in the handle is touched.
+ * Index: the closest-point index, built at the first query of either kind and dropped by the same events.  A ray marches layers of cells along its
+ *   major axis and visits, per layer, the at most 3 x 3 cells its extent on the other two axes covers, every box grown by the slack
+ *   s = 2^-16 cell + 2^-46 R, R = max_a (|o_a| + max |box corner_a|): per ray, because the rule's noise grows with ulp(|o - box|).  A ray in a grid plane
+ *   is offered the cells on both sides, one along a grid line all four.  One bit per brick of 8^3 cells, derived from the mask (n^3 / 4096 bytes more),
+ *   lets the march pass over eight empty layers at once.  Slivers (see above) are tested by every ray.  csrc/shm_mesh_ray_walk.h holds the
+ *   walk and the argument that it offers a superset of what the rule can accept -- and names the one case outside it: a triangle seen exactly edge-on
+ *   from within its own, oblique plane, where the rule's three signs are rounding noise.
+ * shm_grid_mesh_raycast: host buffers, fp64; origins, dirs [3Q] xyz-interleaved; chunks of 2^20 through the pinned staging of shm_grid_raycast.
+ * shm_grid_mesh_raycast_device: device buffers of the handle's precision on the handle's device (d_tri int64, d_count int32); float inputs are promoted
+ *   first and the fp64 results rounded once on the store; synchronous; every pointer is checked as shm_grid_raycast_device checks its own. */
+shm_status shm_grid_mesh_raycast(shm_solver* s, int64_t Q, const double* origins /* [3Q] */, const double* dirs /* [3Q] */, double t_min, double t_max,
+                                 double* t_out /* [Q] */, int64_t* tri_out /* [Q] or NULL */, double* bary_out /* [2Q] or NULL */,
+                                 int32_t* count_out /* [Q] or NULL */, int64_t* n_hits);
+shm_status shm_grid_mesh_raycast_device(shm_solver* s, int64_t Q, const void* d_origins, const void* d_dirs, double t_min, double t_max, void* d_t,
+                                        void* d_tri /* int64, or NULL */, void* d_bary /* or NULL */, void* d_count /* int32, or NULL */, int64_t* n_hits);
 
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */

@@ -286,6 +286,15 @@ shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d
     return guard(s, [&] { s->impl->closest_point_device(Q, d_pts, max_dist, d_dist, d_cp, d_tri, n_answered); });
 }
 
+shm_status shm_grid_mesh_raycast(shm_solver* s, int64_t Q, const double* origins, const double* dirs, double t_min, double t_max, double* t_out, int64_t* tri_out,
+                                 double* bary_out, int32_t* count_out, int64_t* n_hits) {
+    return guard(s, [&] { s->impl->mesh_raycast(Q, origins, dirs, t_min, t_max, t_out, tri_out, bary_out, count_out, n_hits); });
+}
+shm_status shm_grid_mesh_raycast_device(shm_solver* s, int64_t Q, const void* d_origins, const void* d_dirs, double t_min, double t_max, void* d_t, void* d_tri,
+                                        void* d_bary, void* d_count, int64_t* n_hits) {
+    return guard(s, [&] { s->impl->mesh_raycast_device(Q, d_origins, d_dirs, t_min, t_max, d_t, d_tri, d_bary, d_count, n_hits); });
+}
+
 shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) {
     return guard(s, [&] { s->impl->audit_step1(count, nodes, dy_out, ratio_out, out); });
 }

@@ -580,6 +580,8 @@ struct SolverBase {
     virtual void isosurface_indexed_psi(double, int64_t*, int64_t*) = 0;
     virtual void closest_point(int64_t, const double*, double, double*, double*, int64_t*, int64_t*) = 0;
     virtual void closest_point_device(int64_t, const void*, double, void*, void*, void*, int64_t*) = 0;
+    virtual void mesh_raycast(int64_t, const double*, const double*, double, double, double*, int64_t*, double*, int32_t*, int64_t*) = 0;
+    virtual void mesh_raycast_device(int64_t, const void*, const void*, double, double, void*, void*, void*, void*, int64_t*) = 0;
 };
 
 // one per precision, each in its own translation unit (shm_solver_f64.hip / shm_solver_f32.hip)

@@ -29,6 +29,7 @@
 #include "shm_redistance.hip.h"
 #include "shm_redistance_exact.hip.h"
 #include "shm_closest.hip.h"
+#include "shm_mesh_raycast.hip.h"
 #include "shm_plan.h"
 
 namespace shm {
@@ -3632,9 +3633,10 @@ struct Solver final : SolverBase {
     }
 
     // the two staging slots, pinned and on the device, of C * 10 doubles each (closest_point streams through them as well: 8 doubles per query)
-    void ray_staging_reserve(int64_t C) {
+    void ray_staging_reserve(int64_t C, int per = 10) {
         for (auto& e : ray_done)
             if (!e) e.reset(new Event());
+        C = (C * per + 9) / 10;   // (mesh_raycast needs 11 doubles per ray: counted in units of 10)
         if (C <= ray_cap) return;
         for (int b = 0; b < 2; b++) {
             if (ray_pinned[b]) HIPCHK(hipHostFree(ray_pinned[b]));
@@ -4046,6 +4048,118 @@ struct Solver final : SolverBase {
         launch_closest<T>(Q, max_dist, (const T*)pts, (T*)dist, (T*)cpo, (int64_t*)tri);
         const int64_t a = closest_end(Q);
         if (n_answered) *n_answered = a;
+    }
+
+    // ---- ray casts against the resident indexed mesh (shm_mesh_raycast.hip.h) ------------------------------------------------------------------------------------
+    // Working memory: the closest-point index above (one build serves both kinds of query) and two counters.  The host entry streams through the ray
+    // casts' staging slots, 11 doubles per ray.  The mesh, phi, psi and every flag are left as they were.
+    DevArray<unsigned long long> d_mr_cnt, d_mr_bricks;   // the brick level: one bit per 8^3 cells, n^3 / 4096 bytes, derived from the index's mask
+    uint64_t mr_bricks_gen = 0;
+    bool mr_bricks_have = false;
+
+    void mesh_raycast_check(const char* who, int64_t Q, const void* org, const void* dir, const void* t) {
+        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
+        if (Q > ((int64_t)1 << 48)) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 rays", who));   // (the byte counts below must not wrap)
+        if (Q > 0 && (!org || !dir || !t)) throw Error(SHM_ERR_INVALID, fmt("%s: null origins, directions or output", who));
+        need_problem();
+        need_iso_indexed(who);
+        if (cfg.world != 1) throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: a ray crosses the planes of other ranks", who));
+    }
+    void mesh_raycast_begin() {
+        HIPCHK(hipSetDevice(cfg.device));
+        cp_index_build();
+        if (iso_idx_nt > 0 && !(mr_bricks_have && mr_bricks_gen == cp_gen)) {
+            const int nb = mr_brick_side(n);
+            const size_t nbricks = (size_t)nb * nb * nb, nbw = (nbricks + 63) / 64;
+            d_mr_bricks.alloc(nbw);
+            HIPCHK(hipMemsetAsync(d_mr_bricks.p, 0, nbw * sizeof(unsigned long long), stream));
+            hipLaunchKernelGGL((mr_bricks_kernel<kBlock>), dim3(grid_for(nbricks, 16384)), dim3(kBlock), 0, stream, n, d_cp_mask.p, d_mr_bricks.p);
+            HIPCHK(hipGetLastError());
+            mr_bricks_gen = cp_gen;
+            mr_bricks_have = true;
+        }
+        d_mr_cnt.alloc(kMrCounters);
+        HIPCHK(hipMemsetAsync(d_mr_cnt.p, 0, kMrCounters * sizeof(unsigned long long), stream));
+    }
+    int64_t mesh_raycast_end(int64_t Q) {
+        unsigned long long c[kMrCounters] = {};
+        HIPCHK(hipMemcpyAsync(c, d_mr_cnt.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        log("[shm] mesh_raycast: %lld rays, %llu hits, %llu triangle tests, %lld slivers, index build %.3f ms", (long long)Q, c[kMrHits], c[kMrTriTests],
+            (long long)cp_n_slivers, cp_build_ms);
+        cp_build_ms = 0.f;   // (reported by the call that paid for it)
+        return (int64_t)c[kMrHits];
+    }
+    template <typename TIO>
+    void launch_mesh_raycast(int64_t Q, double t_min, double t_max, const TIO* org, const TIO* dir, TIO* t, int64_t* tri, TIO* bary, int32_t* count) {
+        if (Q <= 0) return;
+        const CpGrid G = cp_grid(n, bbox_min, cell);
+        const CpIndex X{d_cp_mask.p, d_cp_rank.p, d_cp_first.p, d_cp_list.p, d_iso_V.p, d_iso_F.p, iso_idx_nt, cp_n_slivers};
+        const int grid = grid_for((size_t)Q, 16384);
+        if (iso_idx_nt > 0)
+            hipLaunchKernelGGL((mesh_raycast_kernel<TIO, true>), dim3(grid), dim3(kBlock), 0, stream, G, X, Q, t_min, t_max, org, dir, t, tri, bary, count, d_mr_cnt.p, d_mr_bricks.p);
+        else
+            hipLaunchKernelGGL((mesh_raycast_kernel<TIO, false>), dim3(grid), dim3(kBlock), 0, stream, G, X, Q, t_min, t_max, org, dir, t, tri, bary, count, d_mr_cnt.p, d_mr_bricks.p);
+        HIPCHK(hipGetLastError());
+    }
+    // host buffers: chunks of 2^20 rays through the ray casts' two staging slots; per slot origins [3C], directions [3C], t [C], triangles [C] (int64),
+    // barycentrics [2C], counts [C] (int32, in the last C doubles)
+    void mesh_raycast(int64_t Q, const double* org, const double* dir, double t_min, double t_max, double* t_out, int64_t* tri, double* bary, int32_t* count,
+                      int64_t* n_hits) override {
+        mesh_raycast_check("mesh_raycast", Q, org, dir, t_out);
+        mesh_raycast_begin();
+        const int64_t C = std::min(Q, kRayChunk);
+        ray_staging_reserve(C, 11);
+        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
+        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
+            const int b = (int)(c & 1);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            HIPCHK(hipEventSynchronize(ray_done[b]->e));
+            const double* hb = (const double*)ray_pinned[b];
+            memcpy(t_out + q0, hb + 6 * C, (size_t)m * sizeof(double));
+            if (tri) memcpy(tri + q0, hb + 7 * C, (size_t)m * sizeof(int64_t));
+            if (bary) memcpy(bary + 2 * q0, hb + 8 * C, (size_t)m * 2 * sizeof(double));
+            if (count) memcpy(count + q0, hb + 10 * C, (size_t)m * sizeof(int32_t));
+        };
+        for (int64_t c = 0; c < nchunks; c++) {
+            const int b = (int)(c & 1);
+            if (c >= 2) finish(c - 2);
+            const int64_t q0 = c * C, m = std::min(C, Q - q0);
+            double* hb = (double*)ray_pinned[b];
+            double* db = ray_dev[b].p;
+            memcpy(hb, org + 3 * q0, (size_t)m * 3 * sizeof(double));
+            memcpy(hb + 3 * C, dir + 3 * q0, (size_t)m * 3 * sizeof(double));
+            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+            HIPCHK(hipMemcpyAsync(db + 3 * C, hb + 3 * C, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+            launch_mesh_raycast<double>(m, t_min, t_max, db, db + 3 * C, db + 6 * C, tri ? (int64_t*)(db + 7 * C) : nullptr, bary ? db + 8 * C : nullptr,
+                                        count ? (int32_t*)(db + 10 * C) : nullptr);
+            HIPCHK(hipMemcpyAsync(hb + 6 * C, db + 6 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (tri) HIPCHK(hipMemcpyAsync(hb + 7 * C, db + 7 * C, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+            if (bary) HIPCHK(hipMemcpyAsync(hb + 8 * C, db + 8 * C, (size_t)m * 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
+            if (count) HIPCHK(hipMemcpyAsync(hb + 10 * C, db + 10 * C, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipEventRecord(ray_done[b]->e, stream));
+        }
+        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        const int64_t a = mesh_raycast_end(Q);
+        if (n_hits) *n_hits = a;
+    }
+    void mesh_raycast_device(int64_t Q, const void* org, const void* dir, double t_min, double t_max, void* t_out, void* tri, void* bary, void* count,
+                             int64_t* n_hits) override {
+        const char* who = "mesh_raycast_device";
+        mesh_raycast_check(who, Q, org, dir, t_out);
+        HIPCHK(hipSetDevice(cfg.device));
+        if (Q > 0) {
+            check_device_buffer(org, (size_t)Q * 3 * sizeof(T), "the origin buffer", who, "the Q rays asked for");
+            check_device_buffer(dir, (size_t)Q * 3 * sizeof(T), "the direction buffer", who, "the Q rays asked for");
+            check_device_buffer(t_out, (size_t)Q * sizeof(T), "the t buffer", who, "the Q rays asked for");
+            if (tri) check_device_buffer(tri, (size_t)Q * sizeof(int64_t), "the triangle buffer", who, "the Q rays asked for");
+            if (bary) check_device_buffer(bary, (size_t)Q * 2 * sizeof(T), "the barycentric buffer", who, "the Q rays asked for");
+            if (count) check_device_buffer(count, (size_t)Q * sizeof(int32_t), "the count buffer", who, "the Q rays asked for");
+        }
+        mesh_raycast_begin();
+        launch_mesh_raycast<T>(Q, t_min, t_max, (const T*)org, (const T*)dir, (T*)t_out, (int64_t*)tri, (T*)bary, (int32_t*)count);
+        const int64_t a = mesh_raycast_end(Q);
+        if (n_hits) *n_hits = a;
     }
 
     // ---- audit of Step 1 at sampled nodes (shm_audit.hip.h) --------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
-               "shm_grid_closest_point", "shm_grid_closest_point_device",
+               "shm_grid_closest_point", "shm_grid_closest_point_device", "shm_grid_mesh_raycast", "shm_grid_mesh_raycast_device",
                "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
@@ -191,6 +191,10 @@ def load_library():
     if hasattr(lib, "shm_grid_closest_point"):   # added within ABI 5: found by symbol
         lib.shm_grid_closest_point.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         lib.shm_grid_closest_point_device.argtypes = lib.shm_grid_closest_point.argtypes
+    if hasattr(lib, "shm_grid_mesh_raycast"):   # added within ABI 5: found by symbol
+        lib.shm_grid_mesh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.POINTER(C.c_int64)]
+        lib.shm_grid_mesh_raycast_device.argtypes = lib.shm_grid_mesh_raycast.argtypes
     lib.shm_grid_owned_planes.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.shm_comm_unique_id.argtypes = [C.c_void_p]
     lib.shm_plan_slab.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
@@ -617,8 +621,10 @@ class GridSolver:
         out[ok] = tc[tri[ok]]
         return out
 
-    def closest_point(self, points, max_dist=None, cp=True, tri=True, label=False):
-        """For every point of points [Q, 3] the distance to the resident indexed mesh (whatever isosurface_indexed, redistance_exact,
+    def closest_point(self, points, max_dist=None, cp=True, tri=True, label=False, signed=False):
+        """signed=True negates dist where mesh_inside(points) holds: the sign is the parity of the mesh's crossings along +x, meaningful where the mesh
+        is closed along that ray (see mesh_inside).  Otherwise:
+        For every point of points [Q, 3] the distance to the resident indexed mesh (whatever isosurface_indexed, redistance_exact,
         isosurface_indexed_psi or isosurface_keep left in the slot), the nearest point on it and its triangle (shm_grid_closest_point): returns
         (dist [Q], [cp [Q, 3],] [tri [Q] int64,] [component [Q] int64 or None,] n_answered), float64.  A point further than max_dist (length units, at
         most 16 cells, the default 4 cells) or with a non-finite coordinate is unanswered: NaN, NaN x 3, -1.  The distance is unsigned.  tri is the
@@ -638,7 +644,82 @@ class GridSolver:
         na = C.c_int64()
         self._chk(self._lib.shm_grid_closest_point(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, c.ctypes.data if cp else None,
                                                    t.ctypes.data if tri else None, C.byref(na)))
+        if signed:
+            dist[self.mesh_inside(pts)] *= -1.0   # (NaN stays NaN)
         return self._closest_result(dist, c, t, na.value, label)
+
+    def mesh_raycast(self, origins, dirs, t_min=0.0, t_max=float("inf"), tri=True, bary=True, count=False, label=False):
+        """Where each ray origins[q] + t dirs[q] first meets the resident indexed mesh (whatever isosurface_indexed, redistance_exact,
+        isosurface_indexed_psi or isosurface_keep left in the slot) within [t_min, t_max] (shm_grid_mesh_raycast): returns
+        (t [Q], [tri [Q] int64,] [bary [Q, 2],] [count [Q] int32,] [component [Q] int64 or None,] n_hits), float64.  t is in units of dirs[q], which need
+        not be normalised; the hit point is (1 - u - v) A + u B + v C of triangle tri, the smallest id among the nearest.  A miss holds NaN, -1, NaN x 2
+        and count 0; a non-finite ray, d = 0 and t_min > t_max are misses.  count is the number of triangles crossed within the range, each crossing
+        counted once -- through shared edges and vertices as well -- so count & 1 says inside / outside where the mesh is closed along the ray.
+        label=True (needs tri) adds the component rank of the hit triangle as closest_point does.  Keep neighbouring rays neighbours."""
+        if not hasattr(self._lib, "shm_grid_mesh_raycast"):
+            raise RuntimeError("mesh_raycast: this build of libshm_grid.so does not export shm_grid_mesh_raycast")
+        if label and not tri:
+            raise ValueError("mesh_raycast: label=True needs tri=True")
+        o, d = _f64(origins).reshape(-1, 3), _f64(dirs).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("mesh_raycast: origins and dirs must both be [Q, 3]")
+        Q = o.shape[0]
+        t = np.empty(Q, dtype=np.float64)
+        tr = np.empty(Q, dtype=np.int64) if tri else None
+        b = np.empty((Q, 2), dtype=np.float64) if bary else None
+        cn = np.empty(Q, dtype=np.int32) if count else None
+        nh = C.c_int64()
+        self._chk(self._lib.shm_grid_mesh_raycast(self._h, Q, o.ctypes.data, d.ctypes.data, float(t_min), float(t_max), t.ctypes.data,
+                                                  tr.ctypes.data if tri else None, b.ctypes.data if bary else None, cn.ctypes.data if count else None, C.byref(nh)))
+        out = (t,) + tuple(x for x in (tr, b, cn) if x is not None)
+        if label:
+            out += (self._closest_labels(tr),)
+        return out + (nh.value,)
+
+    def mesh_raycast_device(self, origins, dirs, t_min=0.0, t_max=float("inf"), tri=True, bary=True, count=False, label=False):
+        """The same on device memory (shm_grid_mesh_raycast_device), with raycast_device's conventions: contiguous [Q, 3] torch tensors on this handle's
+        device with its dtype; t and bary come back as tensors of that dtype (the fp64 answer rounded once), tri as int64, count as int32, on that
+        device; the component labels of label=True are a numpy array.  Import torch before this library is loaded."""
+        if not hasattr(self._lib, "shm_grid_mesh_raycast_device"):
+            raise RuntimeError("mesh_raycast_device: this build of libshm_grid.so does not export shm_grid_mesh_raycast_device")
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("mesh_raycast_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        if label and not tri:
+            raise ValueError("mesh_raycast_device: label=True needs tri=True")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        for x in (origins, dirs):
+            if x.dtype != dt or x.dim() != 2 or x.shape[1] != 3 or not x.is_contiguous():
+                raise ValueError("mesh_raycast_device: origins and dirs must be contiguous [Q, 3] %s tensors" % dt)
+        if origins.shape != dirs.shape or origins.device != dirs.device:
+            raise ValueError("mesh_raycast_device: origins and dirs must have one shape and one device")
+        Q = origins.shape[0]
+        dev = origins.device
+        t = torch.empty(Q, dtype=dt, device=dev)
+        tr = torch.empty(Q, dtype=torch.int64, device=dev) if tri else None
+        b = torch.empty((Q, 2), dtype=dt, device=dev) if bary else None
+        cn = torch.empty(Q, dtype=torch.int32, device=dev) if count else None
+        if origins.is_cuda:
+            torch.cuda.current_stream(dev).synchronize()   # the rays may still be in flight on torch's stream
+        nh = C.c_int64()
+        ptr = lambda x: x.data_ptr() if x is not None and Q else None
+        self._chk(self._lib.shm_grid_mesh_raycast_device(self._h, Q, ptr(origins), ptr(dirs), float(t_min), float(t_max), ptr(t), ptr(tr), ptr(b), ptr(cn),
+                                                         C.byref(nh)))
+        out = (t,) + tuple(x for x in (tr, b, cn) if x is not None)
+        if label:
+            out += (self._closest_labels(tr),)
+        return out + (nh.value,)
+
+    def mesh_inside(self, points, axis=0):
+        """Inside / outside of the resident indexed mesh by parity: one ray from every point along +axis, True where it crosses the mesh an odd number
+        of times (mesh_raycast's count & 1).  Meaningful only where the mesh is closed along that ray: a component that reaches the box is open there
+        (touches_box in the records of isosurface_components says so), and a ray that leaves through such an opening counts one crossing too few.
+        A point with a non-finite coordinate is outside."""
+        pts = _f64(points).reshape(-1, 3)
+        d = np.zeros_like(pts)
+        d[:, int(axis)] = 1.0
+        cn = self.mesh_raycast(pts, d, tri=False, bary=False, count=True)[1]
+        return (cn & 1).astype(bool)
 
     def closest_point_device(self, points, max_dist=None, cp=True, tri=True, label=False):
         """The same on device memory (shm_grid_closest_point_device), with sample_device's conventions: points is a contiguous [Q, 3] torch tensor on this

@@ -157,6 +157,31 @@ class SignedHeatGridSolver {
         return dist;
     }
 
+    // Where every ray origins[q] + t dirs[q], t in [tMin, tMax], first meets the indexed mesh resident on the device (the mesh closestPoints reads): t, NaN for a
+    // miss; optionally the face hit (-1), the barycentrics (u, v) of the hit and the number of faces crossed -- odd means origins[q] is inside, where the mesh
+    // is closed along the ray (shm_grid_mesh_raycast).
+    std::vector<double> castRaysMesh(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double tMin = 0.,
+                                     double tMax = std::numeric_limits<double>::infinity(), std::vector<int64_t>* triangles = nullptr,
+                                     std::vector<double>* bary = nullptr, std::vector<int32_t>* counts = nullptr) {
+        if (!handle) throw std::runtime_error("castRaysMesh: computeDistance has not been called");
+        if (origins.size() != dirs.size()) throw std::runtime_error("castRaysMesh: origins and dirs differ in length");
+        const size_t Q = origins.size();
+        std::vector<double> o(3 * Q), d(3 * Q), t(Q);
+        for (size_t a = 0; a < Q; a++)
+            for (int b = 0; b < 3; b++) {
+                o[3 * a + b] = origins[a][b];
+                d[3 * a + b] = dirs[a][b];
+            }
+        if (triangles) triangles->resize(Q);
+        if (bary) bary->resize(2 * Q);
+        if (counts) counts->resize(Q);
+        int64_t hits = 0;
+        if (shm_grid_mesh_raycast(handle, (int64_t)Q, o.data(), d.data(), tMin, tMax, t.data(), triangles ? triangles->data() : nullptr, bary ? bary->data() : nullptr,
+                                  counts ? counts->data() : nullptr, &hits) != SHM_OK)
+            throw std::runtime_error(shm_grid_last_error(handle));
+        return t;
+    }
+
     // Redistance the phi of the last computeDistance() on the device (shm_grid_redistance): psi with |grad psi| = 1 in the first-order upwind sense, psi < 0
     // exactly where phi < isoval, clamped to +-band; at the grid nodes, in computeDistance's order.  phi is left as it was.
     Vector<double> redistance(double isoval = 0., double band = std::numeric_limits<double>::infinity()) {

@@ -234,6 +234,36 @@ int shmh_closest_points(void* hv, int64_t Q, const double* pts, double max_dist,
     });
 }
 
+// castRaysMesh through the C++ class: rays against the device's resident indexed mesh -> t_out [Q], tri_out [Q], bary_out [2Q], count_out [Q] (each or NULL),
+// *n_hits finite answers.
+int shmh_cast_rays_mesh(void* hv, int64_t Q, const double* origins, const double* dirs, double t_min, double t_max, double* t_out, int64_t* tri_out, double* bary_out,
+                        int32_t* count_out, int64_t* n_hits) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> o((size_t)Q), d((size_t)Q);
+        for (int64_t a = 0; a < Q; a++) {
+            o[(size_t)a] = Vector3{origins[3 * a], origins[3 * a + 1], origins[3 * a + 2]};
+            d[(size_t)a] = Vector3{dirs[3 * a], dirs[3 * a + 1], dirs[3 * a + 2]};
+        }
+        std::vector<int64_t> tri;
+        std::vector<double> bary;
+        std::vector<int32_t> cnt;
+        const std::vector<double> t = h->solver.castRaysMesh(o, d, t_min, t_max, tri_out ? &tri : nullptr, bary_out ? &bary : nullptr, count_out ? &cnt : nullptr);
+        int64_t hits = 0;
+        for (int64_t a = 0; a < Q; a++) {
+            t_out[a] = t[(size_t)a];
+            hits += t[(size_t)a] == t[(size_t)a] ? 1 : 0;
+            if (tri_out) tri_out[a] = tri[(size_t)a];
+            if (bary_out) {
+                bary_out[2 * a] = bary[2 * (size_t)a];
+                bary_out[2 * a + 1] = bary[2 * (size_t)a + 1];
+            }
+            if (count_out) count_out[a] = cnt[(size_t)a];
+        }
+        if (n_hits) *n_hits = hits;
+    });
+}
+
 // redistance through the C++ class: psi of the last compute_distance's phi at the grid nodes -> psi_out [n^3]; stats may be NULL.
 int shmh_redistance(void* hv, double isoval, double band, double* psi_out, shm_redistance_stats* stats) {
     Host* h = (Host*)hv;

@@ -44,11 +44,13 @@ static void usage() {
                  "      --out-psi <file>  Raw float64 psi at the grid nodes, in the order of --out\n"
                  "      --closest <file>  With --iso-indexed: points to measure against the indexed mesh (filtered / offset as exported), in --query's format\n"
                  "      --closest-out <file> Raw float64, five values per point: distance (unsigned; NaN beyond --closest-max), nearest point xyz, triangle index (-1: none)\n"
-                 "      --closest-max <D> How far the mesh may be from a point, in cells (default 4, at most 16)\n";
+                 "      --closest-max <D> How far the mesh may be from a point, in cells (default 4, at most 16)\n"
+                 "      --mesh-rays <file> With --iso-indexed: rays to cast against the indexed mesh (filtered / offset as exported), in --rays' format, t in [0, inf)\n"
+                 "      --mesh-rays-out <file> Raw float64, five values per ray: t (NaN: no hit), triangle index (-1), barycentrics u v, number of triangles crossed\n";
 }
 
 int main(int argc, char** argv) {
-    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut, closestPath, closestOut;
+    std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut, closestPath, closestOut, meshRaysPath, meshRaysOut;
     double closestMax = 4.;
     double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
     bool redistance = false, redistanceExact = false, haveOffset = false;
@@ -97,6 +99,8 @@ int main(int argc, char** argv) {
         else if (s == "--closest") closestPath = need("--closest");
         else if (s == "--closest-out") closestOut = need("--closest-out");
         else if (s == "--closest-max") closestMax = atof(need("--closest-max"));
+        else if (s == "--mesh-rays") meshRaysPath = need("--mesh-rays");
+        else if (s == "--mesh-rays-out") meshRaysOut = need("--mesh-rays-out");
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
         else path = s;
     }
@@ -110,6 +114,10 @@ int main(int argc, char** argv) {
     }
     if (closestPath.empty() != closestOut.empty() || (!closestPath.empty() && !isoIndexed)) {
         std::cerr << "--closest and --closest-out go together and measure against the mesh of --iso-indexed." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (meshRaysPath.empty() != meshRaysOut.empty() || (!meshRaysPath.empty() && !isoIndexed)) {
+        std::cerr << "--mesh-rays and --mesh-rays-out go together and cast against the mesh of --iso-indexed." << std::endl;
         return EXIT_FAILURE;
     }
     if (redistance && redistanceExact) {
@@ -192,7 +200,7 @@ int main(int argc, char** argv) {
                       << rs.n_reached << " reached, max |psi| " << rs.max_abs << ", " << rs.n_candidate_pairs << " candidate pairs, " << rs.ms << " ms; psi written to "
                       << psiOut << std::endl;
         }
-        if (!exportPath.empty() || !closestPath.empty()) {   // (--closest needs the indexed mesh on the device whether or not it is exported)
+        if (!exportPath.empty() || !closestPath.empty() || !meshRaysPath.empty()) {   // (--closest needs the indexed mesh on the device whether or not it is exported)
             std::vector<Vector3> iv;
             std::vector<std::array<size_t, 3>> jf;
             if (isoIndexed && (haveOffset || keepLargest >= 0 || minTriangles >= 0)) {
@@ -236,6 +244,37 @@ int main(int argc, char** argv) {
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
             std::cerr << q.size() << " points measured against the indexed mesh within " << closestMax << " cells: " << answered
                       << " answered; distance, nearest point and triangle written to " << closestOut << std::endl;
+        }
+        if (!meshRaysPath.empty()) {
+            std::ifstream f(meshRaysPath, std::ios::binary | std::ios::ate);
+            if (!f) throw std::runtime_error("cannot read " + meshRaysPath);
+            const std::streamsize bytes = f.tellg();
+            if (bytes % (std::streamsize)(6 * sizeof(double)) != 0) throw std::runtime_error(meshRaysPath + ": size is not a multiple of 48 bytes (float64 origin xyz, direction xyz)");
+            std::vector<double> raw((size_t)bytes / sizeof(double));
+            f.seekg(0);
+            f.read((char*)raw.data(), bytes);
+            std::vector<Vector3> o(raw.size() / 6), d(raw.size() / 6);
+            for (size_t a = 0; a < o.size(); a++) {
+                o[a] = Vector3{raw[6 * a], raw[6 * a + 1], raw[6 * a + 2]};
+                d[a] = Vector3{raw[6 * a + 3], raw[6 * a + 4], raw[6 * a + 5]};
+            }
+            std::vector<int64_t> tri;
+            std::vector<double> bary;
+            std::vector<int32_t> cnt;
+            const std::vector<double> t = solver.castRaysMesh(o, d, 0., std::numeric_limits<double>::infinity(), &tri, &bary, &cnt);
+            std::vector<double> res(5 * o.size());
+            size_t hits = 0;
+            for (size_t a = 0; a < o.size(); a++) {
+                res[5 * a] = t[a];
+                hits += t[a] == t[a] ? 1 : 0;
+                res[5 * a + 1] = (double)tri[a];
+                res[5 * a + 2] = bary[2 * a];
+                res[5 * a + 3] = bary[2 * a + 1];
+                res[5 * a + 4] = (double)cnt[a];
+            }
+            std::ofstream out_f(meshRaysOut, std::ios::binary);
+            out_f.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
+            std::cerr << o.size() << " rays cast against the indexed mesh: " << hits << " hit; t, triangle, barycentrics and crossings written to " << meshRaysOut << std::endl;
         }
         if (!queryPath.empty()) {
             std::ifstream f(queryPath, std::ios::binary | std::ios::ate);

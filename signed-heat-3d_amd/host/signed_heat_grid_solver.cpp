@@ -232,6 +232,27 @@ std::vector<double> SignedHeatGridSolver::closestPoints(const std::vector<Vector
     return dist;
 }
 
+std::vector<double> SignedHeatGridSolver::castRaysMesh(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double tMin, double tMax,
+                                                       std::vector<int64_t>* triangles, std::vector<double>* bary, std::vector<int32_t>* counts) {
+    if (!handle) throw std::runtime_error("castRaysMesh: computeDistance has not been called");
+    if (origins.size() != dirs.size()) throw std::runtime_error("castRaysMesh: origins and dirs differ in length");
+    const size_t Q = origins.size();
+    std::vector<double> o(3 * Q), d(3 * Q), t(Q);
+    for (size_t a = 0; a < Q; a++)
+        for (int b = 0; b < 3; b++) {
+            o[3 * a + b] = origins[a][b];
+            d[3 * a + b] = dirs[a][b];
+        }
+    if (triangles) triangles->resize(Q);
+    if (bary) bary->resize(2 * Q);
+    if (counts) counts->resize(Q);
+    int64_t hits = 0;
+    if (shm_grid_mesh_raycast(handle, (int64_t)Q, o.data(), d.data(), tMin, tMax, t.data(), triangles ? triangles->data() : nullptr, bary ? bary->data() : nullptr,
+                              counts ? counts->data() : nullptr, &hits) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_mesh_raycast: ") + shm_grid_last_error(handle));
+    return t;
+}
+
 VectorXd SignedHeatGridSolver::redistance(double isoval, double band, shm_redistance_stats* stats) {
     if (!handle) throw std::runtime_error("redistance: computeDistance has not been called");
     if (shm_grid_redistance(handle, isoval, band, stats) != SHM_OK) throw std::runtime_error(std::string("shm_grid_redistance: ") + shm_grid_last_error(handle));

@@ -87,6 +87,15 @@ class SignedHeatGridSolver {
     // unanswered; the smallest index among equally near faces).  Keep neighbouring points neighbours in q.
     std::vector<double> closestPoints(const std::vector<Vector3>& q, double maxDist, std::vector<Vector3>* points = nullptr, std::vector<int64_t>* triangles = nullptr);
 
+    // For every ray origins[q] + t dirs[q], t in [tMin, tMax]: where it first meets the indexed mesh resident on the device (the mesh closestPoints reads),
+    // computed on the device (shm_grid_mesh_raycast; the rule and the contract in include/shm_grid.h).  Returns t, NaN for a miss; dirs need not be normalised.
+    // triangles (optional) receives the index of the face hit in that call's `faces` (-1 for a miss), bary (optional, 2 per ray) the barycentrics (u, v) of the
+    // hit -- the point is (1 - u - v) A + u B + v C -- and counts (optional) the number of faces crossed within the range, each crossing counted once:
+    // counts[q] & 1 says whether origins[q] is inside, where the mesh is closed along the ray.
+    std::vector<double> castRaysMesh(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double tMin = 0.,
+                                     double tMax = std::numeric_limits<double>::infinity(), std::vector<int64_t>* triangles = nullptr,
+                                     std::vector<double>* bary = nullptr, std::vector<int32_t>* counts = nullptr);
+
     // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
     // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).
     shm_step1_audit auditStep1(size_t count = 4096, uint64_t seed = 0);

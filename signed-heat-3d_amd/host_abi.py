@@ -45,6 +45,9 @@ def load_host_library():
     lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
     if hasattr(lib, "shmh_closest_points"):
         lib.shmh_closest_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "shmh_cast_rays_mesh"):
+        lib.shmh_cast_rays_mesh.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.POINTER(C.c_int64)]
     if hasattr(lib, "shmh_redistance_exact"):
         lib.shmh_redistance_exact.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceExactStats)]
         lib.shmh_isosurface_indexed_offset.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
@@ -158,6 +161,18 @@ class HostSolver:
         na = C.c_int64()
         self._chk(self._lib.shmh_closest_points(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, cp.ctypes.data, tri.ctypes.data, C.byref(na)))
         return dist, cp, tri, na.value
+
+    def cast_rays_mesh(self, origins, dirs, t_min=0.0, t_max=float("inf")):
+        """castRaysMesh of the C++ mirror: rays against the indexed mesh resident on the device (shm_grid_mesh_raycast).
+        Returns (t [Q], tri [Q] int64, bary [Q, 2], count [Q] int32, n_hits); NaN, -1, NaN x 2 and 0 for a miss."""
+        o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        Q = o.shape[0]
+        t, tri, bary, cnt = np.empty(Q), np.empty(Q, dtype=np.int64), np.empty((Q, 2)), np.empty(Q, dtype=np.int32)
+        nh = C.c_int64()
+        self._chk(self._lib.shmh_cast_rays_mesh(self._h, Q, o.ctypes.data, d.ctypes.data, float(t_min), float(t_max), t.ctypes.data, tri.ctypes.data,
+                                                bary.ctypes.data, cnt.ctypes.data, C.byref(nh)))
+        return t, tri, bary, cnt, nh.value
 
     def redistance(self, isovalue=0.0, band=float("inf")):
         """redistance of the C++ mirror: the phi of the last compute_distance redistanced on the device to its level set (shm_grid_redistance).

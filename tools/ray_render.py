@@ -3,7 +3,12 @@ shm_grid_raycast_device.  Orthographic or pinhole rays are generated on the devi
 tile, so the rays of a wavefront walk the same bricks -- cast against phi = iso, and shaded by -d . grad / (|d| |grad|) (1: the surface faces the eye).
 The image is written as a binary PPM with plain numpy.  camera_rays() is also the workload of tools/ray_bench.py.
 
+--mesh renders the resident indexed mesh instead -- the marching-cubes mesh of phi = iso, after --keep-largest K if given, or with --offset D the offset
+mesh psi = D of the exact redistance: what an export would write -- with shm_grid_mesh_raycast_device, shaded by d . N of the triangle hit and with
+--components coloured by the component it belongs to.
+
     python tools/ray_render.py data/bunny_small.obj --h 2 --out bunny.ppm [--size 512] [--ortho] [--iso 0] [--fp32] [--azimuth 30] [--elevation 20]
+                               [--mesh [--keep-largest K] [--offset D] [--components]]
 """
 import argparse
 import os
@@ -68,6 +73,29 @@ def shade(torch, D, t, g, pixel, size):
     return (img.reshape(size, size, 3) * 255).round().to(torch.uint8).cpu().numpy()
 
 
+PALETTE = np.array([[0.85, 0.85, 0.85], [0.9, 0.35, 0.3], [0.3, 0.7, 0.35], [0.3, 0.45, 0.9], [0.9, 0.75, 0.25], [0.7, 0.35, 0.8], [0.3, 0.8, 0.8]])
+
+
+def shade_mesh(torch, D, t, tri, V, F, pixel, size, comp=None):
+    """uint8 image [size, size, 3]: background dark blue; a hit is lit by |d . N| / (|d| |N|) of its triangle (V, F numpy, the mesh fetched from the handle),
+    grey, or in the palette colour of its component rank (comp: numpy [nt]) ; a triangle seen from behind (d . N > 0) is darkened."""
+    dev = t.device
+    hit = tri >= 0
+    Vt = torch.tensor(V, dtype=torch.float64, device=dev)
+    Ft = torch.tensor(F, dtype=torch.int64, device=dev)
+    f = Ft[tri.clamp(min=0)]
+    N = torch.cross(Vt[f[:, 1]] - Vt[f[:, 0]], Vt[f[:, 2]] - Vt[f[:, 0]], dim=1)
+    D = D.to(torch.float64)
+    cosv = (D * N).sum(1) / (D.norm(dim=1) * N.norm(dim=1)).clamp(min=1e-300)
+    lum = (0.15 + 0.85 * cosv.abs()).clamp(0, 1) * torch.where(cosv > 0, 0.5, 1.0)
+    base = torch.tensor(PALETTE, dtype=torch.float64, device=dev)
+    col = base[torch.tensor(comp, device=dev)[tri.clamp(min=0)] % len(PALETTE)] if comp is not None else base[0].expand(len(t), 3)
+    img = torch.zeros(size * size, 3, dtype=torch.float64, device=dev)
+    img[:, 2] = 0.25
+    img[pixel[hit]] = (col * lum[:, None])[hit]
+    return (img.reshape(size, size, 3) * 255).round().to(torch.uint8).cpu().numpy()
+
+
 def write_ppm(path, img):
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
@@ -85,6 +113,10 @@ def main():
     ap.add_argument("--fp32", action="store_true")
     ap.add_argument("--azimuth", type=float, default=30.0)
     ap.add_argument("--elevation", type=float, default=20.0)
+    ap.add_argument("--mesh", dest="cast_mesh", action="store_true", help="cast against the resident indexed mesh instead of the level set of phi")
+    ap.add_argument("--keep-largest", type=int, default=None)
+    ap.add_argument("--offset", type=float, default=None, help="with --mesh: the offset mesh psi = D (a length) of the exact redistance at --iso")
+    ap.add_argument("--components", action="store_true", help="with --mesh: colour by component")
     a = ap.parse_args()
     import torch   # before the library is loaded (grid_abi.GridSolver.sample_device)
     shm = shm_import.load()
@@ -95,9 +127,20 @@ def main():
     s.solve()
     O, D, pixel = camera_rays(torch, pre["n"], pre["bbox_min"], pre["cell"], a.size, a.ortho, a.azimuth, a.elevation,
                               torch.float32 if a.fp32 else torch.float64)
-    t, g, nh = s.raycast_device(O, D, a.iso, grad=True)
-    write_ppm(a.out, shade(torch, D, t, g, pixel, a.size))
-    print("%d x %d rays against phi = %g on %d^3: %d hits; written to %s" % (a.size, a.size, a.iso, pre["n"], nh, a.out))
+    if a.cast_mesh:
+        if a.offset is not None:
+            s.redistance_exact(a.iso, min(16.0 * pre["cell"], abs(a.offset) + 2.0 * pre["cell"]))
+            V, F = s.isosurface_indexed_psi(a.offset, keep_largest=a.keep_largest)
+        else:
+            V, F = s.isosurface_indexed(a.iso, keep_largest=a.keep_largest)
+        comp = s.isosurface_components(labels=True)[1] if a.components else None      # (labels the mesh in the slot; the mesh itself stays)
+        t, tri, nh = s.mesh_raycast_device(O, D, bary=False)
+        write_ppm(a.out, shade_mesh(torch, D, t, tri, V, F, pixel, a.size, comp))
+        print("%d x %d rays against the indexed mesh (%d triangles) on %d^3: %d hits; written to %s" % (a.size, a.size, len(F), pre["n"], nh, a.out))
+    else:
+        t, g, nh = s.raycast_device(O, D, a.iso, grad=True)
+        write_ppm(a.out, shade(torch, D, t, g, pixel, a.size))
+        print("%d x %d rays against phi = %g on %d^3: %d hits; written to %s" % (a.size, a.size, a.iso, pre["n"], nh, a.out))
     s.close()
 
 
