@@ -301,8 +301,9 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices /* [3*nv] */,
  * Precision: an SHM_F64 handle reads fp64 nodes, an SHM_F32 handle fp32 nodes; cell, weights and sums are always fp64 from the point as given
  *   (float points are promoted first), so the fp32 handle returns the exact trilinear value of its fp32 nodes (rounded to the output type).
  * shm_grid_sample: host buffers; pts [3Q] xyz-interleaved fp64, phi_out [Q] fp64, grad_out [3Q] fp64 or NULL.  The points stream through the
- *   device in chunks (2^20 points) through pinned staging buffers the handle keeps, so device memory stays bounded for any Q.  Q = 0 is valid;
- *   Q < 0, or NULL pts / phi_out with Q > 0, is SHM_ERR_INVALID.
+ *   device in chunks (2^20 points) through the one pair of pinned staging slots the handle keeps for all its host query entries (this one,
+ *   shm_grid_raycast, shm_grid_closest_point, shm_grid_mesh_raycast: at most 84 MiB per slot, pinned and on the device), so device memory stays bounded
+ *   for any Q.  Q = 0 is valid; Q < 0, Q > 2^48 (both calls), or NULL pts / phi_out with Q > 0, is SHM_ERR_INVALID.
  * shm_grid_sample_device: device buffers of the handle's precision (float for SHM_F32, double for SHM_F64) on the handle's device, same layouts;
  *   synchronous: the outputs are ready on return.  Each pointer is checked (hipPointerGetAttributes / hipMemGetAddressRange) before anything is
  *   launched: host memory, another device's memory or an allocation smaller than Q points is SHM_ERR_INVALID. */
@@ -451,7 +452,7 @@ int64_t shm_audit_sample_nodes(int32_t n, int32_t k_begin, int32_t k_end, int64_
  * Errors: SHM_ERR_INVALID for Q < 0 or Q > 2^48, for NULL origins / dirs / t_out with Q > 0, or for a NaN isovalue.  Q = 0 is valid.
  * Scope: world == 1 only (any local_slabs); with world > 1 both calls return SHM_ERR_STATE: a ray crosses other ranks' planes.
  * shm_grid_raycast: host buffers, fp64; origins and dirs [3Q] xyz-interleaved, t_out [Q], grad_out [3Q] or NULL.  The rays stream through the device in
- *   chunks of 2^20 through pinned staging buffers the handle keeps.
+ *   chunks of 2^20 through the pair of pinned staging slots the handle's host query entries share (see shm_grid_sample).
  * shm_grid_raycast_device: device buffers of the handle's precision on the handle's device, same layouts; synchronous.  Every pointer is checked
  *   (hipPointerGetAttributes / hipMemGetAddressRange) before anything is enqueued: host memory, another device's memory or an allocation smaller than Q
  *   rays is SHM_ERR_INVALID. */
@@ -600,7 +601,7 @@ shm_status shm_grid_isosurface_indexed_psi(shm_solver* s, double distance, int64
  *   no cell and every query tests them: the result equals brute force over all triangles on such meshes as well.  (shm_grid_redistance_exact culls them by
  *   their cell like any other triangle.)  Ordinary fields have none.
  * shm_grid_closest_point: host buffers, fp64; pts [3Q] xyz-interleaved.  The queries stream through the device in chunks of 2^20 through the pinned staging
- *   buffers the handle keeps for shm_grid_raycast.
+ *   slots the handle's host query entries share (see shm_grid_sample).
  * shm_grid_closest_point_device: device buffers of the handle's precision on the handle's device, same layouts, d_tri int64; float points are promoted
  *   first and the fp64 outputs rounded once on the store; synchronous.  Every pointer is checked as shm_grid_sample_device checks its own before anything is
  *   enqueued: host memory, another device's memory or an allocation smaller than Q queries is SHM_ERR_INVALID. */
@@ -639,7 +640,7 @@ shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d
  *   lets the march pass over eight empty layers at once.  Slivers (see above) are tested by every ray.  csrc/shm_mesh_ray_walk.h holds the
  *   walk and the argument that it offers a superset of what the rule can accept -- and names the one case outside it: a triangle seen exactly edge-on
  *   from within its own, oblique plane, where the rule's three signs are rounding noise.
- * shm_grid_mesh_raycast: host buffers, fp64; origins, dirs [3Q] xyz-interleaved; chunks of 2^20 through the pinned staging of shm_grid_raycast.
+ * shm_grid_mesh_raycast: host buffers, fp64; origins, dirs [3Q] xyz-interleaved; chunks of 2^20 through the shared pinned staging slots (see shm_grid_sample).
  * shm_grid_mesh_raycast_device: device buffers of the handle's precision on the handle's device (d_tri int64, d_count int32); float inputs are promoted
  *   first and the fp64 results rounded once on the store; synchronous; every pointer is checked as shm_grid_raycast_device checks its own. */
 shm_status shm_grid_mesh_raycast(shm_solver* s, int64_t Q, const double* origins /* [3Q] */, const double* dirs /* [3Q] */, double t_min, double t_max,

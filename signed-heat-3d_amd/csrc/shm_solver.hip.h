@@ -31,6 +31,8 @@
 #include "shm_closest.hip.h"
 #include "shm_mesh_raycast.hip.h"
 #include "shm_plan.h"
+#include "shm_query_stage.h"
+#include <array>
 
 namespace shm {
 
@@ -223,9 +225,7 @@ struct Solver final : SolverBase {
         (void)hipSetDevice(cfg.device);
         if (comm) (void)Rccl::get().CommDestroy(comm);
         if (h_pinned) (void)hipHostFree(h_pinned);
-        for (void* b : smp_pinned)
-            if (b) (void)hipHostFree(b);
-        for (void* b : ray_pinned)
+        for (void* b : stage.pinned)
             if (b) (void)hipHostFree(b);
         slabs.clear();
         if (stream) (void)hipStreamDestroy(stream);
@@ -553,9 +553,7 @@ struct Solver final : SolverBase {
         precond_ready = false;
         have_problem = true;
         have_conv = have_div = have_phi = have_constraints = false;
-        iso_idx_valid = false;
-        ray_bricks_valid = false;
-        redist_valid = false;
+        drop_phi_derived();
         audit_src_ready = false;
         // (round 6: the whole-grid solver of the gathered multi-rank solve is created when a solve first takes that path -- ensure_full() -- so that a run whose solves
         // all take the slab-distributed forms never allocates whole-grid arrays on every rank)
@@ -638,6 +636,13 @@ struct Solver final : SolverBase {
     void need_problem() const {
         if (!have_problem) throw Error(SHM_ERR_STATE, "shm_grid_set_problem has not been called");
     }
+    void need_phi() const {
+        need_problem();
+        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+    }
+    // What is derived from the resident phi falls when q is about to hold something else: the indexed mesh with its labelling, the ray casts' bricks, psi.
+    // (have_phi and the flags of Y, the divergence and the constraints are the caller's: the sites differ on them.)
+    void drop_phi_derived() { iso_idx_valid = cmp_valid = ray_bricks_valid = redist_valid = false; }
 
     // ------------------------------------------------------------------------------------------
     // Steps 1+2
@@ -2822,9 +2827,7 @@ struct Solver final : SolverBase {
         PlanIn in = plan_inputs(&o);   // (the options are checked here, before anything is launched)
         const Plan p = plan_solve(in);
         if (p.status != SHM_OK) throw Error(p.status, p.error);
-        iso_idx_valid = false;   // q is about to be overwritten: the indexed mesh no longer belongs to the resident phi
-        ray_bricks_valid = false;
-        redist_valid = false;
+        drop_phi_derived();   // q is about to be overwritten: the indexed mesh no longer belongs to the resident phi
         const bool pre = p.precond;
         if (!(o.tol > 0.)) o.tol = sizeof(T) == 8 ? 1e-8 : 1e-5;
         if (o.max_iters <= 0) o.max_iters = 20 * n;
@@ -2931,8 +2934,7 @@ struct Solver final : SolverBase {
         if (ke) *ke = slabs.back().k1;
     }
     void get_phi(double* out, int32_t* kb, int32_t* ke) override {
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         HIPCHK(hipSetDevice(cfg.device));
         copy_owned_to_host(SHM_FIELD_PHI, out);
         if (kb) *kb = slabs.front().k0;
@@ -2982,9 +2984,7 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_phi = false;  // q now holds L u, not phi
-        iso_idx_valid = false;
-        ray_bricks_valid = false;
-        redist_valid = false;
+        drop_phi_derived();
     }
 
     // Test and tooling entry point: the caller's field becomes the resident phi (q of every slab), as if a solve had produced it.  Y, the divergence, the
@@ -2995,10 +2995,7 @@ struct Solver final : SolverBase {
         HIPCHK(hipSetDevice(cfg.device));
         upload_owned(phi, 2);
         have_phi = true;
-        iso_idx_valid = false;
-        cmp_valid = false;
-        ray_bricks_valid = false;
-        redist_valid = false;
+        drop_phi_derived();
     }
 
     void get_constraints(int64_t* nodes, double* coeffs, int32_t* m_out) override {
@@ -3077,7 +3074,7 @@ struct Solver final : SolverBase {
         need_problem();
         if (method != SHM_ISO_MARCHING_CUBES && method != SHM_ISO_MARCHING_TETS) throw Error(SHM_ERR_INVALID, fmt("isosurface: unknown method %d", method));
         const bool mc = method == SHM_ISO_MARCHING_CUBES;
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         HIPCHK(hipSetDevice(cfg.device));
         halo_exchange(ARR_Q);  // phi lives in q; cells of the top owned plane need the plane above
         iso_vertices.clear();
@@ -3131,17 +3128,104 @@ struct Solver final : SolverBase {
         if (nt) *nt = (int64_t)(iso_triangles.size() / 3);
     }
 
-    // ---- point queries of the resident phi (shm_sample.hip.h) ------------------------------------------------------------------------------------------
-    static constexpr int64_t kSampleChunk = (int64_t)1 << 20;   // points per chunk of the host entry: 56 MiB of pinned staging and as much device memory (two slots)
-    DevArray<unsigned long long> d_sample_count;
-    DevArray<double> smp_dev[2];                 // per slot: points [3C], phi [C], gradient [3C]
-    void* smp_pinned[2] = {nullptr, nullptr};    // the same layout in pinned host memory
-    int64_t smp_cap = 0;
-    std::unique_ptr<Event> smp_done[2];
+    // ---- what the query entries share: the argument checks, and the staging pipeline of the host entries (shm_query_stage.h) --------------------------------------
+    // An entry describes its arrays as a table of columns; the table drives the argument check, the device-buffer checks of the *_device entry and the slot
+    // layout of the host entry.  One pair of staging slots serves sample, raycast, closest_point and mesh_raycast: pinned host memory and device memory of
+    // the same layout, grown to the largest slot a call has needed (84 MiB for 2^20 mesh rays) and freed with the handle.
+    struct QueryStage {
+        void* pinned[2] = {nullptr, nullptr};
+        DevArray<char> dev[2];
+        size_t cap = 0;                    // bytes per slot
+        std::unique_ptr<Event> done[2];    // the results of the chunk in slot b have reached pinned[b]
+    } stage;
 
+    // Q in [0, 2^48] and no required column null with Q > 0.  noun: what a query is called ("points", "rays", "queries"); nulls: the entry's list of its required columns.
+    template <size_t NC> void query_check(const char* who, const char* noun, const char* nulls, int64_t Q, const std::array<QueryCol, NC>& cols) {
+        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
+        if (Q > kQueryMaxQ) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 %s", who, noun));   // (the byte counts below must not wrap)
+        for (const QueryCol& c : cols)
+            if (Q > 0 && !c.optional && !c.ptr) throw Error(SHM_ERR_INVALID, fmt("%s: null %s", who, nulls));
+    }
+    void check_device_buffer(const void* p, size_t bytes, const char* what, const char* who, const char* short_of) {
+        hipPointerAttribute_t at;
+        memset(&at, 0, sizeof at);
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != cfg.device)
+            throw Error(SHM_ERR_INVALID, fmt("%s: %s is not device memory of device %d", who, what, cfg.device));
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
+            (void)hipGetLastError();
+            throw Error(SHM_ERR_INVALID, fmt("%s: %s is not a device allocation", who, what));
+        }
+        if ((const char*)p + bytes > (const char*)base + size) throw Error(SHM_ERR_INVALID, fmt("%s: %s holds fewer than %s", who, what, short_of));
+    }
+    // every present column of a *_device entry: reals are of type T there
+    template <size_t NC> void check_device_columns(const char* who, const char* noun, int64_t Q, const std::array<QueryCol, NC>& cols) {
+        if (Q <= 0) return;
+        const std::string short_of = fmt("the Q %s asked for", noun);
+        for (const QueryCol& c : cols)
+            if (c.ptr) check_device_buffer(c.ptr, (size_t)Q * (c.real ? c.bytes / sizeof(double) * sizeof(T) : c.bytes), c.name, who, short_of.c_str());
+    }
+    void stage_reserve(size_t bytes) {
+        for (auto& e : stage.done)
+            if (!e) e.reset(new Event());
+        if (bytes <= stage.cap) return;
+        for (int b = 0; b < 2; b++) {
+            if (stage.pinned[b]) HIPCHK(hipHostFree(stage.pinned[b]));
+            stage.pinned[b] = nullptr;
+            stage.dev[b].release();
+        }
+        stage.cap = 0;
+        for (int b = 0; b < 2; b++) {
+            HIPCHK(hipHostMalloc(&stage.pinned[b], bytes));
+            stage.dev[b].alloc(bytes);
+        }
+        stage.cap = bytes;
+    }
+    // The host entries: Q queries in chunks of 2^20 through the two slots, so that the host copies of one chunk overlap the device work of the other.
+    // launch(m, d) enqueues the kernels of one chunk of m queries; d[i] is the device address of column i, null for an absent one.
+    template <size_t NC, typename Launch> void query_stream(int64_t Q, const std::array<QueryCol, NC>& cols, Launch&& launch) {
+        const QueryChunks ch = query_chunks(Q);
+        if (ch.n == 0) return;
+        const QueryLayout L = query_layout(cols.data(), (int)NC, ch.C);
+        stage_reserve(L.slot_bytes);
+        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
+            const int b = (int)(c & 1);
+            const size_t q0 = (size_t)ch.q0(c), m = (size_t)ch.m(c);
+            HIPCHK(hipEventSynchronize(stage.done[b]->e));
+            for (size_t i = 0; i < NC; i++)
+                if (cols[i].out && cols[i].ptr) memcpy((char*)const_cast<void*>(cols[i].ptr) + q0 * cols[i].bytes, (const char*)stage.pinned[b] + L.off[i], m * cols[i].bytes);
+        };
+        for (int64_t c = 0; c < ch.n; c++) {
+            const int b = (int)(c & 1);
+            if (c >= 2) finish(c - 2);
+            const size_t q0 = (size_t)ch.q0(c), m = (size_t)ch.m(c);
+            char* hb = (char*)stage.pinned[b];
+            char* db = stage.dev[b].p;
+            void* d[NC];
+            for (size_t i = 0; i < NC; i++) d[i] = query_col_addr(db, L, cols.data(), (int)i);
+            for (size_t i = 0; i < NC; i++)
+                if (!cols[i].out) memcpy(hb + L.off[i], (const char*)cols[i].ptr + q0 * cols[i].bytes, m * cols[i].bytes);
+            for (size_t i = 0; i < NC; i++)
+                if (!cols[i].out) HIPCHK(hipMemcpyAsync(d[i], hb + L.off[i], m * cols[i].bytes, hipMemcpyHostToDevice, stream));
+            launch((int64_t)m, d);
+            for (size_t i = 0; i < NC; i++)
+                if (cols[i].out && cols[i].ptr) HIPCHK(hipMemcpyAsync(hb + L.off[i], d[i], m * cols[i].bytes, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipEventRecord(stage.done[b]->e, stream));
+        }
+        for (int64_t c = std::max<int64_t>(0, ch.n - 2); c < ch.n; c++) finish(c);
+    }
+
+    // ---- point queries of the resident phi (shm_sample.hip.h) ------------------------------------------------------------------------------------------
+    DevArray<unsigned long long> d_sample_count;
+
+    static std::array<QueryCol, 3> sample_cols(const void* pts, const void* out, const void* grad) {
+        return {{query_in(pts, 24, "the point buffer"), query_out(out, 8, "the phi buffer"), query_out(grad, 24, "the gradient buffer", true)}};
+    }
     void sample_begin() {
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         HIPCHK(hipSetDevice(cfg.device));
         halo_exchange(ARR_Q);  // phi lives in q; cells of the top owned plane read the plane above (collective with world > 1)
         d_sample_count.alloc(1);
@@ -3175,81 +3259,21 @@ struct Solver final : SolverBase {
         }
         HIPCHK(hipGetLastError());
     }
-
-    // host buffers: the points stream through two pinned staging slots, so that the host copies of one chunk overlap the device work of the other
     void sample(int64_t Q, const double* pts, double* out, double* grad, int64_t* n_answered) override {
-        if (Q < 0) throw Error(SHM_ERR_INVALID, "sample: Q < 0");
-        if (Q > 0 && (!pts || !out)) throw Error(SHM_ERR_INVALID, "sample: null points or output");
+        const auto cols = sample_cols(pts, out, grad);
+        query_check("sample", "points", "points or output", Q, cols);
         sample_begin();
-        const int64_t C = std::min(Q, kSampleChunk);
-        if (C > smp_cap) {
-            for (int b = 0; b < 2; b++) {
-                if (smp_pinned[b]) HIPCHK(hipHostFree(smp_pinned[b]));
-                smp_pinned[b] = nullptr;
-                smp_dev[b].release();
-            }
-            smp_cap = 0;
-            for (int b = 0; b < 2; b++) {
-                HIPCHK(hipHostMalloc(&smp_pinned[b], (size_t)C * 7 * sizeof(double)));
-                smp_dev[b].alloc((size_t)C * 7);
-                if (!smp_done[b]) smp_done[b].reset(new Event());
-            }
-            smp_cap = C;
-        }
-        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
-        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
-            const int b = (int)(c & 1);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            HIPCHK(hipEventSynchronize(smp_done[b]->e));
-            const double* hb = (const double*)smp_pinned[b];
-            memcpy(out + q0, hb + 3 * C, (size_t)m * sizeof(double));
-            if (grad) memcpy(grad + 3 * q0, hb + 4 * C, (size_t)m * 3 * sizeof(double));
-        };
-        for (int64_t c = 0; c < nchunks; c++) {
-            const int b = (int)(c & 1);
-            if (c >= 2) finish(c - 2);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            double* hb = (double*)smp_pinned[b];
-            double* db = smp_dev[b].p;
-            memcpy(hb, pts + 3 * q0, (size_t)m * 3 * sizeof(double));
-            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-            launch_sample<double>(m, db, db + 3 * C, grad ? db + 4 * C : nullptr);
-            HIPCHK(hipMemcpyAsync(hb + 3 * C, db + 3 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (grad) HIPCHK(hipMemcpyAsync(hb + 4 * C, db + 4 * C, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipEventRecord(smp_done[b]->e, stream));
-        }
-        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        query_stream(Q, cols, [&](int64_t m, void* const* d) { launch_sample<double>(m, (const double*)d[0], (double*)d[1], (double*)d[2]); });
         const int64_t a = sample_end();
         if (n_answered) *n_answered = a;
     }
-
-    // device buffers of type T, checked to lie in device memory of this handle's device and to hold Q points before anything is launched
-    void check_device_buffer(const void* p, size_t bytes, const char* what, const char* who = "sample_device", const char* short_of = "the Q points asked for") {
-        hipPointerAttribute_t at;
-        memset(&at, 0, sizeof at);
-        const hipError_t e = hipPointerGetAttributes(&at, p);
-        if (e != hipSuccess) (void)hipGetLastError();
-        if (e != hipSuccess || (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeManaged) || at.device != cfg.device)
-            throw Error(SHM_ERR_INVALID, fmt("%s: %s is not device memory of device %d", who, what, cfg.device));
-        hipDeviceptr_t base = nullptr;
-        size_t size = 0;
-        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) {
-            (void)hipGetLastError();
-            throw Error(SHM_ERR_INVALID, fmt("%s: %s is not a device allocation", who, what));
-        }
-        if ((const char*)p + bytes > (const char*)base + size) throw Error(SHM_ERR_INVALID, fmt("%s: %s holds fewer than %s", who, what, short_of));
-    }
     void sample_device(int64_t Q, const void* pts, void* out, void* grad, int64_t* n_answered) override {
-        if (Q < 0) throw Error(SHM_ERR_INVALID, "sample_device: Q < 0");
-        if (Q > 0 && (!pts || !out)) throw Error(SHM_ERR_INVALID, "sample_device: null points or output");
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        const char* who = "sample_device";
+        const auto cols = sample_cols(pts, out, grad);
+        query_check(who, "points", "points or output", Q, cols);
+        need_phi();
         HIPCHK(hipSetDevice(cfg.device));
-        if (Q > 0) {
-            check_device_buffer(pts, (size_t)Q * 3 * sizeof(T), "the point buffer");
-            check_device_buffer(out, (size_t)Q * sizeof(T), "the phi buffer");
-            if (grad) check_device_buffer(grad, (size_t)Q * 3 * sizeof(T), "the gradient buffer");
-        }
+        check_device_columns(who, "points", Q, cols);
         sample_begin();
         launch_sample<T>(Q, (const T*)pts, (T*)out, (T*)grad);
         const int64_t a = sample_end();
@@ -3270,8 +3294,7 @@ struct Solver final : SolverBase {
     uint64_t iso_idx_gen = 0;   // counts the meshes the slot has held (a build, a compaction)
 
     void isosurface_indexed(double iso, int64_t* nv_out, int64_t* nt_out) override {
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         HIPCHK(hipSetDevice(cfg.device));
         halo_exchange(ARR_Q);  // phi lives in q; cells of the top owned plane need the plane above (collective with world > 1)
         iso_idx_build(iso, false);
@@ -3561,25 +3584,29 @@ struct Solver final : SolverBase {
     }
 
     // ---- ray casts against a level set of the resident phi (shm_raycast.hip.h) ----------------------------------------------------------------------------
-    // Working memory: one {min, max} pair per brick of 8^3 cells (1/256 of phi), the slab table, and for the host entry two staging slots of 2^20 rays.
+    // Working memory: one {min, max} pair per brick of 8^3 cells (1/256 of phi) and the slab table; the host entry streams through the shared staging slots.
     // The bricks are built at the first cast of a phi and kept until phi is replaced (ray_bricks_valid falls with iso_idx_valid); freed with the handle.
-    static constexpr int64_t kRayChunk = (int64_t)1 << 20;   // rays per chunk of the host entry: 80 MiB of pinned staging and as much device memory (two slots)
     DevArray<T> d_ray_minmax;
     DevArray<RaySlab<T>> d_ray_slabs;
     DevArray<unsigned long long> d_ray_hits;
-    DevArray<double> ray_dev[2];                 // per slot: origins [3C], directions [3C], t [C], gradient [3C]
-    void* ray_pinned[2] = {nullptr, nullptr};
-    int64_t ray_cap = 0;
-    std::unique_ptr<Event> ray_done[2];
     bool ray_bricks_valid = false;
 
-    void raycast_check(const char* who, int64_t Q, const void* org, const void* dir, const void* t, double iso) {
-        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
-        if (Q > ((int64_t)1 << 48)) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 rays", who));   // (the byte counts below must not wrap)
-        if (Q > 0 && (!org || !dir || !t)) throw Error(SHM_ERR_INVALID, fmt("%s: null origins, directions or output", who));
+    // The table through which the ray casts and the redistancing passes read phi: one {q, k0, k1} per slab.  It is kept in two device arrays of the same
+    // contents because their lifetimes differ: d_ray_slabs is written with the bricks and read by every cast until ray_bricks_valid falls, d_rd_slabs
+    // (below) is written again by every redistance call; neither call depends on the other having run.
+    void upload_ray_slabs(DevArray<RaySlab<T>>& d) {
+        std::vector<RaySlab<T>> tab(slabs.size());
+        for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
+        d.upload(tab, stream);
+    }
+    static std::array<QueryCol, 4> raycast_cols(const void* org, const void* dir, const void* t, const void* grad) {
+        return {{query_in(org, 24, "the origin buffer"), query_in(dir, 24, "the direction buffer"), query_out(t, 8, "the t buffer"),
+                 query_out(grad, 24, "the gradient buffer", true)}};
+    }
+    void raycast_check(const char* who, int64_t Q, const std::array<QueryCol, 4>& cols, double iso) {
+        query_check(who, "rays", "origins, directions or output", Q, cols);
         if (iso != iso) throw Error(SHM_ERR_INVALID, fmt("%s: the isovalue is NaN", who));
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         if (cfg.world != 1)
             throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: a ray crosses the planes of other ranks (gather phi, or cast on a single-process handle)", who));
     }
@@ -3599,13 +3626,9 @@ struct Solver final : SolverBase {
         P.t_min = t_min;
         P.t_max = t_max;
         if (!ray_bricks_valid) {
-            std::vector<RaySlab<T>> tab(slabs.size());
-            for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
-            d_ray_slabs.upload(tab, stream);
+            upload_ray_slabs(d_ray_slabs);
             const size_t nbricks = (size_t)P.nb * P.nb * P.nb;
             d_ray_minmax.alloc(2 * nbricks);
-            for (auto& e : ray_done)
-                if (!e) e.reset(new Event());
             hipLaunchKernelGGL((ray_bricks_kernel<T>), dim3((unsigned)((nbricks + kBlock / kWave - 1) / (kBlock / kWave))), dim3(kBlock), 0, stream, P, d_ray_slabs.p,
                                d_ray_minmax.p);
             HIPCHK(hipGetLastError());
@@ -3632,69 +3655,20 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
     }
 
-    // the two staging slots, pinned and on the device, of C * 10 doubles each (closest_point streams through them as well: 8 doubles per query)
-    void ray_staging_reserve(int64_t C, int per = 10) {
-        for (auto& e : ray_done)
-            if (!e) e.reset(new Event());
-        C = (C * per + 9) / 10;   // (mesh_raycast needs 11 doubles per ray: counted in units of 10)
-        if (C <= ray_cap) return;
-        for (int b = 0; b < 2; b++) {
-            if (ray_pinned[b]) HIPCHK(hipHostFree(ray_pinned[b]));
-            ray_pinned[b] = nullptr;
-            ray_dev[b].release();
-        }
-        ray_cap = 0;
-        for (int b = 0; b < 2; b++) {
-            HIPCHK(hipHostMalloc(&ray_pinned[b], (size_t)C * 10 * sizeof(double)));
-            ray_dev[b].alloc((size_t)C * 10);
-        }
-        ray_cap = C;
-    }
-
-    // host buffers: the rays stream through two pinned staging slots of their own (a ray is 6 + 4 doubles against sample's 3 + 4), as in sample()
     void raycast(int64_t Q, const double* org, const double* dir, double iso, double t_min, double t_max, double* t_out, double* grad, int64_t* n_hits) override {
-        raycast_check("raycast", Q, org, dir, t_out, iso);
+        const auto cols = raycast_cols(org, dir, t_out, grad);
+        raycast_check("raycast", Q, cols, iso);
         const RayParams P = raycast_begin(iso, t_min, t_max);
-        const int64_t C = std::min(Q, kRayChunk);
-        ray_staging_reserve(C);
-        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
-        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
-            const int b = (int)(c & 1);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            HIPCHK(hipEventSynchronize(ray_done[b]->e));
-            const double* hb = (const double*)ray_pinned[b];
-            memcpy(t_out + q0, hb + 6 * C, (size_t)m * sizeof(double));
-            if (grad) memcpy(grad + 3 * q0, hb + 7 * C, (size_t)m * 3 * sizeof(double));
-        };
-        for (int64_t c = 0; c < nchunks; c++) {
-            const int b = (int)(c & 1);
-            if (c >= 2) finish(c - 2);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            double* hb = (double*)ray_pinned[b];
-            double* db = ray_dev[b].p;
-            memcpy(hb, org + 3 * q0, (size_t)m * 3 * sizeof(double));
-            memcpy(hb + 3 * C, dir + 3 * q0, (size_t)m * 3 * sizeof(double));
-            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(db + 3 * C, hb + 3 * C, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-            launch_raycast<double>(P, m, db, db + 3 * C, db + 6 * C, grad ? db + 7 * C : nullptr);
-            HIPCHK(hipMemcpyAsync(hb + 6 * C, db + 6 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (grad) HIPCHK(hipMemcpyAsync(hb + 7 * C, db + 7 * C, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipEventRecord(ray_done[b]->e, stream));
-        }
-        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        query_stream(Q, cols, [&](int64_t m, void* const* d) { launch_raycast<double>(P, m, (const double*)d[0], (const double*)d[1], (double*)d[2], (double*)d[3]); });
         const int64_t a = raycast_end();
         if (n_hits) *n_hits = a;
     }
     void raycast_device(int64_t Q, const void* org, const void* dir, double iso, double t_min, double t_max, void* t_out, void* grad, int64_t* n_hits) override {
         const char* who = "raycast_device";
-        raycast_check(who, Q, org, dir, t_out, iso);
+        const auto cols = raycast_cols(org, dir, t_out, grad);
+        raycast_check(who, Q, cols, iso);
         HIPCHK(hipSetDevice(cfg.device));
-        if (Q > 0) {
-            check_device_buffer(org, (size_t)Q * 3 * sizeof(T), "the origin buffer", who, "the Q rays asked for");
-            check_device_buffer(dir, (size_t)Q * 3 * sizeof(T), "the direction buffer", who, "the Q rays asked for");
-            check_device_buffer(t_out, (size_t)Q * sizeof(T), "the t buffer", who, "the Q rays asked for");
-            if (grad) check_device_buffer(grad, (size_t)Q * 3 * sizeof(T), "the gradient buffer", who, "the Q rays asked for");
-        }
+        check_device_columns(who, "rays", Q, cols);
         const RayParams P = raycast_begin(iso, t_min, t_max);
         launch_raycast<T>(P, Q, (const T*)org, (const T*)dir, (T*)t_out, (T*)grad);
         const int64_t a = raycast_end();
@@ -3715,8 +3689,7 @@ struct Solver final : SolverBase {
     void redistance(double iso, double band, shm_redistance_stats* out) override {
         if (!(iso - iso == 0.)) throw Error(SHM_ERR_INVALID, "redistance: the isovalue is not finite");
         if (!(band > 0.)) throw Error(SHM_ERR_INVALID, "redistance: the band must be positive (+inf: the whole grid)");
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         if (cfg.world != 1)
             throw Error(SHM_ERR_STATE, "redistance: world > 1 is not supported: a distance crosses the planes of other ranks (gather phi, or use a single-process handle)");
         HIPCHK(hipSetDevice(cfg.device));
@@ -3730,9 +3703,7 @@ struct Solver final : SolverBase {
         P.band = band;
         const size_t nblocks = (size_t)P.nb * P.nb * P.nb;
         const int cap = 24 * P.nb + 16;   // rounds: a value crosses at least one block per round, and a causal chain is at most 3 nb blocks long
-        std::vector<RaySlab<T>> tab(slabs.size());
-        for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
-        d_rd_slabs.upload(tab, stream);
+        upload_ray_slabs(d_rd_slabs);
         d_psi.alloc((size_t)n * n * n);
         d_rd_active.alloc(nblocks);
         d_rd_any.alloc((size_t)cap);
@@ -3828,8 +3799,7 @@ struct Solver final : SolverBase {
     void redistance_exact(double iso, double band, shm_redistance_exact_stats* out) override {
         const char* who = "redistance_exact";
         if (!(iso - iso == 0.)) throw Error(SHM_ERR_INVALID, fmt("%s: the isovalue is not finite", who));
-        need_problem();
-        if (!have_phi) throw Error(SHM_ERR_STATE, "no phi: shm_grid_solve has not completed");
+        need_phi();
         if (cfg.world != 1)
             throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: a distance crosses the planes of other ranks (gather phi, or use a single-process handle)", who));
         if (!(band > 0.) || !(band <= kRdxMaxBandCells * cell))
@@ -3852,9 +3822,7 @@ struct Solver final : SolverBase {
         P.band = band;
         P.cull2 = band * band * (1. + 0x1p-18) / (cell * cell);
         const size_t N = (size_t)n * n * n;
-        std::vector<RaySlab<T>> tab(slabs.size());
-        for (size_t s = 0; s < slabs.size(); s++) tab[s] = RaySlab<T>{slabs[s].q.p, slabs[s].k0, slabs[s].k1};
-        d_rd_slabs.upload(tab, stream);
+        upload_ray_slabs(d_rd_slabs);
         d_psi.alloc(N);
         d_rdx_cnt.alloc(kRdxCounters);
         HIPCHK(hipMemsetAsync(d_rdx_cnt.p, 0, kRdxCounters * sizeof(unsigned long long), stream));
@@ -3903,7 +3871,7 @@ struct Solver final : SolverBase {
     // ---- closest-point queries against the resident indexed mesh (shm_closest.hip.h) ----------------------------------------------------------------------------
     // Working memory: the index -- n^3 / 8 bytes of mask, n^3 / 16 of its popcount prefix, 16 bytes per triangle -- built at the first query of a mesh and
     // kept until the slot holds another mesh (cp_gen against iso_idx_gen; anything that replaces phi makes the mesh itself invalid); freed with the handle.
-    // The host entry streams through the ray casts' staging slots.  The mesh, phi, psi and every flag are left as they were.
+    // The host entry streams through the shared staging slots.  The mesh, phi, psi and every flag are left as they were.
     DevArray<unsigned long long> d_cp_mask, d_cp_cnt;
     DevArray<uint32_t> d_cp_rank, d_cp_key, d_cp_list, d_cp_count, d_cp_first, d_cp_tile, d_cp_ns;
     int64_t cp_n_slivers = 0;   // triangles filed under no cell: every query tests them (shm_closest_index.h)
@@ -3912,10 +3880,12 @@ struct Solver final : SolverBase {
     std::unique_ptr<Event> cp_ev[3];
     float cp_build_ms = 0.f;
 
-    void closest_check(const char* who, int64_t Q, const void* pts, const void* dist, double max_dist) {
-        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
-        if (Q > ((int64_t)1 << 48)) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 queries", who));   // (the byte counts below must not wrap)
-        if (Q > 0 && (!pts || !dist)) throw Error(SHM_ERR_INVALID, fmt("%s: null points or distance output", who));
+    static std::array<QueryCol, 4> closest_cols(const void* pts, const void* dist, const void* cpo, const void* tri) {
+        return {{query_in(pts, 24, "the point buffer"), query_out(dist, 8, "the distance buffer"), query_out(cpo, 24, "the foot-point buffer", true),
+                 query_out(tri, 8, "the triangle buffer", true, false)}};
+    }
+    void closest_check(const char* who, int64_t Q, const std::array<QueryCol, 4>& cols, double max_dist) {
+        query_check(who, "queries", "points or distance output", Q, cols);
         need_problem();
         if (!(max_dist > 0.) || !(max_dist <= kCpMaxDistCells * cell))
             throw Error(SHM_ERR_INVALID, fmt("%s: max_dist must be finite, positive and at most %d cells (a walk visits (2 max_dist / cell + 3)^3 cells at worst)", who, kCpMaxDistCells));
@@ -4000,50 +3970,20 @@ struct Solver final : SolverBase {
         else hipLaunchKernelGGL((closest_point_kernel<TIO, false>), dim3(grid), dim3(kBlock), 0, stream, G, X, Q, max_dist, pts, dist, cpo, tri, d_cp_cnt.p);
         HIPCHK(hipGetLastError());
     }
-    // host buffers: chunks of 2^20 queries through the ray casts' two staging slots; per slot points [3C], dist [C], foot points [3C], triangles [C] (int64)
     void closest_point(int64_t Q, const double* pts, double max_dist, double* dist, double* cpo, int64_t* tri, int64_t* n_answered) override {
-        closest_check("closest_point", Q, pts, dist, max_dist);
+        const auto cols = closest_cols(pts, dist, cpo, tri);
+        closest_check("closest_point", Q, cols, max_dist);
         closest_begin();
-        const int64_t C = std::min(Q, kRayChunk);
-        ray_staging_reserve(C);
-        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
-        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
-            const int b = (int)(c & 1);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            HIPCHK(hipEventSynchronize(ray_done[b]->e));
-            const double* hb = (const double*)ray_pinned[b];
-            memcpy(dist + q0, hb + 3 * C, (size_t)m * sizeof(double));
-            if (cpo) memcpy(cpo + 3 * q0, hb + 4 * C, (size_t)m * 3 * sizeof(double));
-            if (tri) memcpy(tri + q0, hb + 7 * C, (size_t)m * sizeof(int64_t));
-        };
-        for (int64_t c = 0; c < nchunks; c++) {
-            const int b = (int)(c & 1);
-            if (c >= 2) finish(c - 2);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            double* hb = (double*)ray_pinned[b];
-            double* db = ray_dev[b].p;
-            memcpy(hb, pts + 3 * q0, (size_t)m * 3 * sizeof(double));
-            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-            launch_closest<double>(m, max_dist, db, db + 3 * C, cpo ? db + 4 * C : nullptr, tri ? (int64_t*)(db + 7 * C) : nullptr);
-            HIPCHK(hipMemcpyAsync(hb + 3 * C, db + 3 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (cpo) HIPCHK(hipMemcpyAsync(hb + 4 * C, db + 4 * C, (size_t)m * 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (tri) HIPCHK(hipMemcpyAsync(hb + 7 * C, db + 7 * C, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipEventRecord(ray_done[b]->e, stream));
-        }
-        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        query_stream(Q, cols, [&](int64_t m, void* const* d) { launch_closest<double>(m, max_dist, (const double*)d[0], (double*)d[1], (double*)d[2], (int64_t*)d[3]); });
         const int64_t a = closest_end(Q);
         if (n_answered) *n_answered = a;
     }
     void closest_point_device(int64_t Q, const void* pts, double max_dist, void* dist, void* cpo, void* tri, int64_t* n_answered) override {
         const char* who = "closest_point_device";
-        closest_check(who, Q, pts, dist, max_dist);
+        const auto cols = closest_cols(pts, dist, cpo, tri);
+        closest_check(who, Q, cols, max_dist);
         HIPCHK(hipSetDevice(cfg.device));
-        if (Q > 0) {
-            check_device_buffer(pts, (size_t)Q * 3 * sizeof(T), "the point buffer", who, "the Q queries asked for");
-            check_device_buffer(dist, (size_t)Q * sizeof(T), "the distance buffer", who, "the Q queries asked for");
-            if (cpo) check_device_buffer(cpo, (size_t)Q * 3 * sizeof(T), "the foot-point buffer", who, "the Q queries asked for");
-            if (tri) check_device_buffer(tri, (size_t)Q * sizeof(int64_t), "the triangle buffer", who, "the Q queries asked for");
-        }
+        check_device_columns(who, "queries", Q, cols);
         closest_begin();
         launch_closest<T>(Q, max_dist, (const T*)pts, (T*)dist, (T*)cpo, (int64_t*)tri);
         const int64_t a = closest_end(Q);
@@ -4051,16 +3991,19 @@ struct Solver final : SolverBase {
     }
 
     // ---- ray casts against the resident indexed mesh (shm_mesh_raycast.hip.h) ------------------------------------------------------------------------------------
-    // Working memory: the closest-point index above (one build serves both kinds of query) and two counters.  The host entry streams through the ray
-    // casts' staging slots, 11 doubles per ray.  The mesh, phi, psi and every flag are left as they were.
+    // Working memory: the closest-point index above (one build serves both kinds of query) and two counters.  The host entry streams through the shared
+    // staging slots.  The mesh, phi, psi and every flag are left as they were.
     DevArray<unsigned long long> d_mr_cnt, d_mr_bricks;   // the brick level: one bit per 8^3 cells, n^3 / 4096 bytes, derived from the index's mask
     uint64_t mr_bricks_gen = 0;
     bool mr_bricks_have = false;
 
-    void mesh_raycast_check(const char* who, int64_t Q, const void* org, const void* dir, const void* t) {
-        if (Q < 0) throw Error(SHM_ERR_INVALID, fmt("%s: Q < 0", who));
-        if (Q > ((int64_t)1 << 48)) throw Error(SHM_ERR_INVALID, fmt("%s: Q exceeds 2^48 rays", who));   // (the byte counts below must not wrap)
-        if (Q > 0 && (!org || !dir || !t)) throw Error(SHM_ERR_INVALID, fmt("%s: null origins, directions or output", who));
+    static std::array<QueryCol, 6> mesh_raycast_cols(const void* org, const void* dir, const void* t, const void* tri, const void* bary, const void* count) {
+        return {{query_in(org, 24, "the origin buffer"), query_in(dir, 24, "the direction buffer"), query_out(t, 8, "the t buffer"),
+                 query_out(tri, 8, "the triangle buffer", true, false), query_out(bary, 16, "the barycentric buffer", true),
+                 query_out(count, 4, "the count buffer", true, false)}};
+    }
+    void mesh_raycast_check(const char* who, int64_t Q, const std::array<QueryCol, 6>& cols) {
+        query_check(who, "rays", "origins, directions or output", Q, cols);
         need_problem();
         need_iso_indexed(who);
         if (cfg.world != 1) throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: a ray crosses the planes of other ranks", who));
@@ -4102,60 +4045,24 @@ struct Solver final : SolverBase {
             hipLaunchKernelGGL((mesh_raycast_kernel<TIO, false>), dim3(grid), dim3(kBlock), 0, stream, G, X, Q, t_min, t_max, org, dir, t, tri, bary, count, d_mr_cnt.p, d_mr_bricks.p);
         HIPCHK(hipGetLastError());
     }
-    // host buffers: chunks of 2^20 rays through the ray casts' two staging slots; per slot origins [3C], directions [3C], t [C], triangles [C] (int64),
-    // barycentrics [2C], counts [C] (int32, in the last C doubles)
     void mesh_raycast(int64_t Q, const double* org, const double* dir, double t_min, double t_max, double* t_out, int64_t* tri, double* bary, int32_t* count,
                       int64_t* n_hits) override {
-        mesh_raycast_check("mesh_raycast", Q, org, dir, t_out);
+        const auto cols = mesh_raycast_cols(org, dir, t_out, tri, bary, count);
+        mesh_raycast_check("mesh_raycast", Q, cols);
         mesh_raycast_begin();
-        const int64_t C = std::min(Q, kRayChunk);
-        ray_staging_reserve(C, 11);
-        const int64_t nchunks = Q > 0 ? (Q + C - 1) / C : 0;
-        auto finish = [&](int64_t c) {   // copy the results of chunk c out of its slot
-            const int b = (int)(c & 1);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            HIPCHK(hipEventSynchronize(ray_done[b]->e));
-            const double* hb = (const double*)ray_pinned[b];
-            memcpy(t_out + q0, hb + 6 * C, (size_t)m * sizeof(double));
-            if (tri) memcpy(tri + q0, hb + 7 * C, (size_t)m * sizeof(int64_t));
-            if (bary) memcpy(bary + 2 * q0, hb + 8 * C, (size_t)m * 2 * sizeof(double));
-            if (count) memcpy(count + q0, hb + 10 * C, (size_t)m * sizeof(int32_t));
-        };
-        for (int64_t c = 0; c < nchunks; c++) {
-            const int b = (int)(c & 1);
-            if (c >= 2) finish(c - 2);
-            const int64_t q0 = c * C, m = std::min(C, Q - q0);
-            double* hb = (double*)ray_pinned[b];
-            double* db = ray_dev[b].p;
-            memcpy(hb, org + 3 * q0, (size_t)m * 3 * sizeof(double));
-            memcpy(hb + 3 * C, dir + 3 * q0, (size_t)m * 3 * sizeof(double));
-            HIPCHK(hipMemcpyAsync(db, hb, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-            HIPCHK(hipMemcpyAsync(db + 3 * C, hb + 3 * C, (size_t)m * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
-            launch_mesh_raycast<double>(m, t_min, t_max, db, db + 3 * C, db + 6 * C, tri ? (int64_t*)(db + 7 * C) : nullptr, bary ? db + 8 * C : nullptr,
-                                        count ? (int32_t*)(db + 10 * C) : nullptr);
-            HIPCHK(hipMemcpyAsync(hb + 6 * C, db + 6 * C, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (tri) HIPCHK(hipMemcpyAsync(hb + 7 * C, db + 7 * C, (size_t)m * sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-            if (bary) HIPCHK(hipMemcpyAsync(hb + 8 * C, db + 8 * C, (size_t)m * 2 * sizeof(double), hipMemcpyDeviceToHost, stream));
-            if (count) HIPCHK(hipMemcpyAsync(hb + 10 * C, db + 10 * C, (size_t)m * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipEventRecord(ray_done[b]->e, stream));
-        }
-        for (int64_t c = std::max<int64_t>(0, nchunks - 2); c < nchunks; c++) finish(c);
+        query_stream(Q, cols, [&](int64_t m, void* const* d) {
+            launch_mesh_raycast<double>(m, t_min, t_max, (const double*)d[0], (const double*)d[1], (double*)d[2], (int64_t*)d[3], (double*)d[4], (int32_t*)d[5]);
+        });
         const int64_t a = mesh_raycast_end(Q);
         if (n_hits) *n_hits = a;
     }
     void mesh_raycast_device(int64_t Q, const void* org, const void* dir, double t_min, double t_max, void* t_out, void* tri, void* bary, void* count,
                              int64_t* n_hits) override {
         const char* who = "mesh_raycast_device";
-        mesh_raycast_check(who, Q, org, dir, t_out);
+        const auto cols = mesh_raycast_cols(org, dir, t_out, tri, bary, count);
+        mesh_raycast_check(who, Q, cols);
         HIPCHK(hipSetDevice(cfg.device));
-        if (Q > 0) {
-            check_device_buffer(org, (size_t)Q * 3 * sizeof(T), "the origin buffer", who, "the Q rays asked for");
-            check_device_buffer(dir, (size_t)Q * 3 * sizeof(T), "the direction buffer", who, "the Q rays asked for");
-            check_device_buffer(t_out, (size_t)Q * sizeof(T), "the t buffer", who, "the Q rays asked for");
-            if (tri) check_device_buffer(tri, (size_t)Q * sizeof(int64_t), "the triangle buffer", who, "the Q rays asked for");
-            if (bary) check_device_buffer(bary, (size_t)Q * 2 * sizeof(T), "the barycentric buffer", who, "the Q rays asked for");
-            if (count) check_device_buffer(count, (size_t)Q * sizeof(int32_t), "the count buffer", who, "the Q rays asked for");
-        }
+        check_device_columns(who, "rays", Q, cols);
         mesh_raycast_begin();
         launch_mesh_raycast<T>(Q, t_min, t_max, (const T*)org, (const T*)dir, (T*)t_out, (int64_t*)tri, (T*)bary, (int32_t*)count);
         const int64_t a = mesh_raycast_end(Q);
@@ -4274,9 +4181,7 @@ struct Solver final : SolverBase {
         for (Slab<T>& sl : slabs) HIPCHK(hipMemcpyAsync(sl.q.p, sl.z.p, sl.ntot * sizeof(T), hipMemcpyDeviceToDevice, stream));
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_conv = have_div = have_phi = false;
-        iso_idx_valid = false;
-        ray_bricks_valid = false;
-        redist_valid = false;
+        drop_phi_derived();
     }
 };
 

@@ -18,6 +18,8 @@ except ImportError:
 
 from conftest import ROOT, c_, load_golden
 
+SHM_ERR_INVALID = 1
+
 
 # ---- the numpy restatement of evaluateFunction and its gradient, with the box rules of include/shm_grid.h -------------------------------------------------
 def eval_ref(phi, n, bbox_min, cell, pts, grad=False):
@@ -365,6 +367,56 @@ def test_sample_device_equals_the_host_path(shm, precision):
     rc = s._lib.shm_grid_sample_device(s._h, 1 << 40, t.data_ptr(), tv.data_ptr(), None, C.byref(na))
     assert rc == 1
     assert np.array_equal(s.sample(pio.astype(np.float64))[0], hv, equal_nan=True)
+
+
+@pytest.mark.gpu
+def test_sample_host_entry_in_chunks(shm):
+    """Three chunks of the host entry (2 * 2^20 + 301 points: both staging slots, a slot used a second time, a short last chunk) against one launch of the
+    device entry on the same points: bit-equal, NaNs included, and n_answered summed over the chunks is the number of finite outputs."""
+    if torch is None or not torch.cuda.is_available():
+        pytest.fail("torch with a HIP device is needed for the device entry point")
+    d, s, phi = _case(shm, 32, 64)
+    Q = 2 * (1 << 20) + 301
+    base = np.concatenate([_points(d, Q=50000, seed=31), np.array([[np.nan, 0., 0.], [1e9, 0., 0.]]), np.asarray(d["bbox_min"])[None] - 1.0])
+    pts = np.tile(base, (Q // len(base) + 1, 1))[:Q]
+    pts[len(base):] += np.random.default_rng(32).uniform(-0.5, 0.5, (Q - len(base), 3)) * d["cell"]   # (no two chunks hold the same points)
+    hv, hg, hna = s.sample(pts, grad=True)
+    tv, tg, tna = s.sample_device(torch.from_numpy(pts).to("cuda:0"), grad=True)
+    tv, tg = tv.cpu().numpy(), tg.cpu().numpy()
+    assert hv.shape == (Q,) and hg.shape == (Q, 3)
+    assert np.array_equal(hv, tv, equal_nan=True) and np.array_equal(hg, tg, equal_nan=True)
+    assert hna == tna == np.isfinite(hv).sum()
+    assert 0 < hna < Q and np.isnan(hv[-301:]).any() and np.isfinite(hv[-301:]).any()
+    assert np.array_equal(np.isfinite(hg).all(axis=1), np.isfinite(hv))
+
+
+@pytest.mark.gpu
+def test_sample_refuses_a_q_whose_byte_counts_would_wrap(shm):
+    """Q beyond 2^48 is refused with SHM_ERR_INVALID by both entries before anything is multiplied, checked or launched (24 Q wraps in 64 bits for the
+    last two: a wrapped byte count would pass the device entry's allocation check); *n_answered is untouched and the handle goes on working."""
+    if torch is None or not torch.cuda.is_available():
+        pytest.fail("torch with a HIP device is needed for the device entry point")
+    d, s, phi = _case(shm, 32, 64)
+    Q = 64
+    pts = _points(d, Q=Q, seed=41)
+    before = s.sample(pts, grad=True)
+    dev = torch.device("cuda", 0)
+    p_d = torch.from_numpy(pts).to(dev)
+    v_d, g_d = torch.empty(Q, dtype=p_d.dtype, device=dev), torch.empty((Q, 3), dtype=p_d.dtype, device=dev)
+    hv, hg = np.empty(Q), np.empty((Q, 3))
+    lib, h = s._lib, s._h
+    na = C.c_int64(-5)
+    for big in ((1 << 40) + (1 << 48), (1 << 61) // 3 + 1, (1 << 63) - 1):
+        assert lib.shm_grid_sample_device(h, big, p_d.data_ptr(), v_d.data_ptr(), g_d.data_ptr(), C.byref(na)) == SHM_ERR_INVALID
+        assert b"2^48" in lib.shm_grid_last_error(h)
+        assert lib.shm_grid_sample_device(h, big, p_d.data_ptr(), v_d.data_ptr(), None, C.byref(na)) == SHM_ERR_INVALID
+        assert lib.shm_grid_sample(h, big, pts.ctypes.data, hv.ctypes.data, hg.ctypes.data, C.byref(na)) == SHM_ERR_INVALID
+        assert b"2^48" in lib.shm_grid_last_error(h)
+    assert na.value == -5
+    after = s.sample(pts, grad=True)
+    assert after[2] == before[2] and np.array_equal(after[0], before[0], equal_nan=True) and np.array_equal(after[1], before[1], equal_nan=True)
+    tv, tg, tna = s.sample_device(p_d, grad=True)
+    assert tna == before[2] and np.array_equal(tv.cpu().numpy(), before[0], equal_nan=True) and np.array_equal(tg.cpu().numpy(), before[1], equal_nan=True)
 
 
 @pytest.mark.gpu

@@ -111,6 +111,12 @@ def run(a):
                         times.append((time.perf_counter() - t0) * 1e3)
                         tests = info[2]
                     query_ms = float(np.median(times))
+                    host_ms = None
+                    if a.host:
+                        s.closest_point(p64, md)
+                        t0 = time.perf_counter()
+                        s.closest_point(p64, md)
+                        host_ms = round((time.perf_counter() - t0) * 1e3, 2)
                     dist = out[0].cpu().numpy().astype(np.float64)
                     ans = np.isfinite(dist)
                     t0 = time.perf_counter()
@@ -122,7 +128,8 @@ def run(a):
                                build_ms=round(build_ms, 3), query_ms=round(query_ms, 3), Mq_per_s=round(Q / query_ms / 1e3, 2), tests_per_query=round(tests / Q, 2),
                                build_share=round(build_ms / (build_ms + query_ms), 3), old_ms=round(st["ms"] + t_fetch + t_blend, 1),
                                old_parts_ms=[round(st["ms"], 2), round(t_fetch, 1), round(t_blend, 1)], blend_compared=int(both.sum()),
-                               blend_err_max=round(float(err.max()), 4), blend_err_mean=round(float(err.mean()), 5), psi_of="unfiltered mesh" if keep else "the same mesh")
+                               blend_err_max=round(float(err.max()), 4), blend_err_mean=round(float(err.mean()), 5), psi_of="unfiltered mesh" if keep else "the same mesh",
+                               host_ms=host_ms)
                     print(json.dumps(row), flush=True)
                     rows.append(row)
         s.close()
@@ -135,6 +142,7 @@ def main():
     ap.add_argument("--cases", default="bunny_small:256:64,bunny_small:512:64,rocker:512:32")
     ap.add_argument("--max-dists", default="2,4,8")
     ap.add_argument("--out", default="")
+    ap.add_argument("--host", type=int, default=0, help="also time the host entry point on the same queries, once after a warm-up call (host_ms)")
     a = ap.parse_args()
     rows = run(a)
     if a.out:

@@ -91,8 +91,15 @@ def run(a):
                 s.raycast_device(o, d, iso)
                 phi_ms = median_ms(lambda: s.raycast_device(o, d, iso), a.reps)
                 Q = len(o)
+                host_ms = None
+                if a.host:
+                    o64, d64 = o.cpu().numpy().astype(np.float64), d.cpu().numpy().astype(np.float64)
+                    host_cast = lambda: s.mesh_raycast(o64, d64, tri=True, bary=False, count=count)    # noqa: E731
+                    host_cast()
+                    host_ms = round(median_ms(host_cast, 1), 2)
                 row = dict(case=case, mesh=label, n_triangles=int(len(F)), n_slivers=int(info[3]), rays=rname, n_rays=Q, hits=int(info[1]), build_ms=round(build_ms, 3),
-                           cast_ms=round(cast_ms, 3), Mrays_per_s=round(Q / cast_ms / 1e3, 2), tests_per_ray=round(info[2] / Q, 2), phi_cast_ms=round(phi_ms, 3))
+                           cast_ms=round(cast_ms, 3), Mrays_per_s=round(Q / cast_ms / 1e3, 2), tests_per_ray=round(info[2] / Q, 2), phi_cast_ms=round(phi_ms, 3),
+                           host_ms=host_ms)
                 print(json.dumps(row), flush=True)
                 rows.append(row)
         s.close()
@@ -105,6 +112,7 @@ def main():
     ap.add_argument("--cases", default="bunny_small:256:64,bunny_small:512:64")
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--out", default="")
+    ap.add_argument("--host", type=int, default=0, help="also time the host entry point on the same rays, once after a warm-up call (host_ms)")
     a = ap.parse_args()
     rows = run(a)
     if a.out:
