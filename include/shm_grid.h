@@ -649,6 +649,55 @@ shm_status shm_grid_mesh_raycast(shm_solver* s, int64_t Q, const double* origins
 shm_status shm_grid_mesh_raycast_device(shm_solver* s, int64_t Q, const void* d_origins, const void* d_dirs, double t_min, double t_max, void* d_t,
                                         void* d_tri /* int64, or NULL */, void* d_bary /* or NULL */, void* d_count /* int32, or NULL */, int64_t* n_hits);
 
+/* --- Steps 1-2 at arbitrary points: the diffused normal field off the grid ---------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * What it answers: X(q) = sum_s (N_s A_s) exp(-lambda |q - b_s|) / |q - b_s| and Y(q) = X(q) / |X(q)| at Q points of the caller's choosing -- the double loop of
+ *   the reference's tet solver at its barycentres (signed_heat_tet_solver.cpp:54-72, :131-147), of anyone who orients normals near a broken surface or
+ *   seeds a narrow band, from flat arrays.  INTEGRATION.md binds those loops to this entry.
+ * State:
+ *   needs shm_grid_set_problem and nothing else: no solve, no run_conv.  SHM_ERR_STATE before a problem is set.
+ *   reads the problem's sources only; the grid block is not read (a caller without a grid passes any small grid that holds the sources).
+ *   touches no resident field: have_conv, phi, Y, psi and the mesh slot are as they were, bit for bit.
+ *   no collective: with world > 1 or local_slabs > 1 every process answers all of its own Q points (the sources are replicated).
+ * Arguments:
+ *   lambda: 0 means the problem's lambda; a positive finite value overrides it (the tet solver derives its own from its node spacing); negative or
+ *     non-finite is SHM_ERR_INVALID.
+ *   arith: SHM_STEP1_EXACT_F64 sums every (point, source) pair, SHM_STEP1_REFERENCE_F64 is taken as the same mode; SHM_STEP1_AUTO may drop sources under
+ *     `budget`; anything else is SHM_ERR_INVALID.
+ *   budget: 0 means 1e-8; otherwise within [1e-12, 1e-3] or SHM_ERR_INVALID.  Ignored in exact mode (stats->budget is then 0).
+ *   arithmetic is fp64 in handles of both precisions.
+ *   Q = 0 is fine and launches nothing; Q < 0, a null required pointer with Q > 0 or a device buffer that is too short is SHM_ERR_INVALID.
+ * Per point:
+ *   q - b_s is formed from the caller's fp64 coordinates and the caller's fp64 source positions, as the reference forms it (not from grid-centred copies).
+ *   a non-finite coordinate, or a point that coincides with a source (r = 0), gives Y = NaN x 3 and ratio = NaN and is not counted in `answered`.
+ *   no exponent offset: fp64 underflows as the reference's does.  A point with lambda * r_min >= 335 is counted in out_of_zone and receives whatever plain
+ *     fp64 yields, possibly NaN.  (Under AUTO r_min is taken over the sources evaluated.)
+ *   ratio_out[q] = |X| / sum_s |w_s|_1 g_s over the sources evaluated: the cancellation depth, as shm_grid_audit_step1 reports it.
+ *   a point's outputs are a function of that point, the sources, lambda, arith and budget alone: not of Q, of its position or its neighbours in the array,
+ *     of the chunks of 2^20, of host against device entry or of the call count.  Two evaluations of the same point are bit-identical.
+ * Accuracy (price: 2 * 2^-53 * sum_s |w_s|_1 g_s (lambda r_s + S_padded + 8) / |X|, the rounding of a plain fp64 sum; tests/field_points_ref.py):
+ *   EXACT: |Y - Y_ref|_inf <= price at every in-zone finite point.
+ *   AUTO:  |Y - Y_ref|_inf <= budget + price; ratio within a relative budget + price + l1_rel of the full sum's (l1_rel: what two plain fp64 sums of L1 may
+ *     differ by, relative to it: 2 * 2^-53 * sum_s |w_s|_1 g_s (lambda r_s + S_padded + 8) / L1).  Per point, whole clusters of 64 sources are
+ *     dropped while the sum R of their bounds stays within budget / 5 of the largest term of the nearest cluster, and the point is accepted only if
+ *     3 R <= budget |X_kept|; otherwise it is summed again over every source and counted in points_redone (csrc/shm_field_cull.h).
+ * shm_grid_field_at_points: host buffers, fp64, xyz-interleaved; chunks of 2^20 through the shared pinned staging slots (see shm_grid_sample).
+ * shm_grid_field_at_points_device: device buffers of the handle's precision on the handle's device; float points are promoted exactly, the fp64 results are
+ *   rounded once on the store; synchronous; every pointer is checked as shm_grid_sample_device checks its own. */
+typedef struct {
+    int64_t points, answered;        /* Q; points whose three components of Y are finite */
+    int64_t out_of_zone;             /* points with lambda * r_min >= 335: Y as plain fp64 gives it, possibly NaN */
+    int64_t points_redone;           /* AUTO: points whose dropped bound failed the a-posteriori test and were summed again over every source */
+    double  pairs_evaluated, pairs_dropped;   /* (point, source) pairs; padding excluded */
+    double  lambda, budget;          /* what was in force */
+    int32_t arith;                   /* what ran */
+    double  ms;                      /* device time of the call's kernels (hipEvents), copies excluded */
+} shm_field_stats;
+shm_status shm_grid_field_at_points(shm_solver* s, int64_t Q, const double* pts /* [3Q] */, double lambda, int32_t arith, double budget,
+                                    double* Y_out /* [3Q] */, double* ratio_out /* [Q] or NULL */, shm_field_stats* stats /* or NULL */);
+shm_status shm_grid_field_at_points_device(shm_solver* s, int64_t Q, const void* d_pts, double lambda, int32_t arith, double budget,
+                                           void* d_Y, void* d_ratio /* or NULL */, shm_field_stats* stats);
+
 /* --- multi-GPU bootstrap ------------------------------------------------------------------------ */
 /* Fill 128 bytes with a fresh ncclUniqueId (rank 0 calls this, the launcher broadcasts the bytes). */
 shm_status shm_comm_unique_id(void* out128);

@@ -11,5 +11,5 @@ Layout:
   host_abi.py   ctypes binding of the C++ host layer's flat wrapper
 """
 from .grid_abi import (GridSolver, ShmError, ShmStats, lib_path, load_library, SHM_F32, SHM_F64,  # noqa: F401
-                       plan_slab, comm_unique_id, step1_plane_weights, plan_slab_weighted, audit_sample_nodes, ShmStep1Audit, ShmRedistanceStats,
+                       plan_slab, comm_unique_id, step1_plane_weights, plan_slab_weighted, audit_sample_nodes, ShmStep1Audit, ShmFieldStats, ShmRedistanceStats,
                        ShmIsoComponent, ISO_COMPONENT_DTYPE, largest_components_mask)

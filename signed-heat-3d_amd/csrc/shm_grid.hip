@@ -295,6 +295,15 @@ shm_status shm_grid_mesh_raycast_device(shm_solver* s, int64_t Q, const void* d_
     return guard(s, [&] { s->impl->mesh_raycast_device(Q, d_origins, d_dirs, t_min, t_max, d_t, d_tri, d_bary, d_count, n_hits); });
 }
 
+shm_status shm_grid_field_at_points(shm_solver* s, int64_t Q, const double* pts, double lambda, int32_t arith, double budget, double* Y_out, double* ratio_out,
+                                    shm_field_stats* stats) {
+    return guard(s, [&] { s->impl->field_at_points(Q, pts, lambda, arith, budget, Y_out, ratio_out, stats); });
+}
+shm_status shm_grid_field_at_points_device(shm_solver* s, int64_t Q, const void* d_pts, double lambda, int32_t arith, double budget, void* d_Y, void* d_ratio,
+                                           shm_field_stats* stats) {
+    return guard(s, [&] { s->impl->field_at_points_device(Q, d_pts, lambda, arith, budget, d_Y, d_ratio, stats); });
+}
+
 shm_status shm_grid_audit_step1(shm_solver* s, int64_t count, const int64_t* nodes, double* dy_out, double* ratio_out, shm_step1_audit* out) {
     return guard(s, [&] { s->impl->audit_step1(count, nodes, dy_out, ratio_out, out); });
 }

@@ -10,6 +10,7 @@
 //   raycast        origins 24 | directions 24 | t 8 | gradient 24                              80
 //   closest_point  points 24 | distance 8 | foot points 24 | triangles 8 (int64)               64
 //   mesh_raycast   origins 24 | directions 24 | t 8 | triangles 8 (int64) | barycentrics 16 | counts 4 (int32)    84
+//   field_at_points  points 24 | Y 24 | ratio 8                                                56
 #pragma once
 #include <algorithm>
 #include <cstddef>

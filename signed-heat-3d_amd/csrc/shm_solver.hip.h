@@ -30,6 +30,7 @@
 #include "shm_redistance_exact.hip.h"
 #include "shm_closest.hip.h"
 #include "shm_mesh_raycast.hip.h"
+#include "shm_field_points.hip.h"
 #include "shm_plan.h"
 #include "shm_query_stage.h"
 #include <array>
@@ -88,6 +89,7 @@ struct Solver final : SolverBase {
     double conv_wscale = 1.;          // power of two that brings the largest source weight into (0.5, 1]
     int64_t S = 0;
     std::vector<double> h_pos, h_wn, h_area;
+    std::vector<int64_t> src_order;   // the sources' indices in the Morton order Step 1 clusters them in
     double area_sum = 0., conv_far_gap = 0., conv_skip_base = 3.0e38, last_host_setup_ms = 0., last_setup_wall_ms = 0.;
     double conv_tier_ring = 0.;   // tiered fp64 Step 1: width (nats) of the ring pass behind a failed a-posteriori test (shm_tier_passes.h; 0: none)
     double conv_tier_log = 0., conv_tier_skip_base = 3.0e38;   // tiered fp64 Step 1: far threshold G (nats) and the drop threshold of rounds 3-5, ln(S / eps)
@@ -311,6 +313,8 @@ struct Solver final : SolverBase {
                 order[(size_t)s] = {code, s};
             }
             std::sort(order.begin(), order.end());
+            src_order.resize((size_t)S);   // (kept for shm_grid_field_at_points, which builds its own copy of the sources in this order on first use)
+            for (int64_t s = 0; s < S; s++) src_order[(size_t)s] = order[(size_t)s].second;
             // Step 1 only ever needs DIFFERENCES node - source.  Its device copies of the sources and its node coordinates are therefore taken relative to the
             // grid's centre: the fp32 arithmetic (fp32 solve; packed-fp32 tier of the fp64 solve) then rounds coordinates of magnitude <= half the grid's
             // diagonal instead of |centroid| + that -- a mesh that sits far from the origin loses nothing (tests: test_step1_is_translation_invariant).
@@ -555,6 +559,7 @@ struct Solver final : SolverBase {
         have_conv = have_div = have_phi = have_constraints = false;
         drop_phi_derived();
         audit_src_ready = false;
+        field_src_ready = false;
         // (round 6: the whole-grid solver of the gathered multi-rank solve is created when a solve first takes that path -- ensure_full() -- so that a run whose solves
         // all take the slab-distributed forms never allocates whole-grid arrays on every rank)
         full_problem_set = false;
@@ -3216,6 +3221,151 @@ struct Solver final : SolverBase {
             HIPCHK(hipEventRecord(stage.done[b]->e, stream));
         }
         for (int64_t c = std::max<int64_t>(0, ch.n - 2); c < ch.n; c++) finish(c);
+    }
+
+    // ---- Steps 1-2 at arbitrary points (shm_field_points.hip.h) -----------------------------------------------------------------------------------------------
+    // This path's own view of the sources, uploaded at the first call of a problem: fp64 in handles of both precisions, NOT centred on the grid, in the Morton
+    // cluster order of Step 1 (src_order), six planes of 64 doubles per cluster; and one fp64 record per cluster (centre, radius rounded up, weight sum
+    // rounded up).  Padding repeats the last source with zero weight.  Nothing else of the handle is read or written.
+    DevArray<double> d_field_src, d_field_cl;
+    DevArray<unsigned long long> d_field_ctr;
+    bool field_src_ready = false;
+    int field_clusters = 0;
+    std::vector<std::unique_ptr<Event>> field_ev;   // a pair per launch of the call in progress
+    size_t field_ev_used = 0;
+
+    static std::array<QueryCol, 3> field_cols(const void* pts, const void* Y, const void* ratio) {
+        return {{query_in(pts, 24, "the point buffer"), query_out(Y, 24, "the Y buffer"), query_out(ratio, 8, "the ratio buffer", true)}};
+    }
+    FieldParams field_begin(const char* who, double lam, int32_t arith, double budget) {
+        need_problem();
+        if (!(lam >= 0.) || !std::isfinite(lam)) throw Error(SHM_ERR_INVALID, fmt("%s: lambda must be 0 (the problem's) or positive and finite", who));
+        if (arith != SHM_STEP1_AUTO && arith != SHM_STEP1_EXACT_F64 && arith != SHM_STEP1_REFERENCE_F64) throw Error(SHM_ERR_INVALID, fmt("%s: unknown arith", who));
+        if (arith == SHM_STEP1_AUTO && budget != 0. && !(budget >= kFieldBudgetMin && budget <= kFieldBudgetMax))   // (exact mode ignores it)
+            throw Error(SHM_ERR_INVALID, fmt("%s: budget must be 0 (1e-8) or within [1e-12, 1e-3]", who));
+        HIPCHK(hipSetDevice(cfg.device));
+        if (!field_src_ready) {
+            field_clusters = (int)((S + kFieldCluster - 1) / kFieldCluster);
+            std::vector<double> rec((size_t)field_clusters * kFieldSrcRec, 0.), cl((size_t)field_clusters * kFieldClusterRec, 0.);
+            for (int c = 0; c < field_clusters; c++) {
+                double* r = rec.data() + (size_t)c * kFieldSrcRec;
+                double cc[3] = {0, 0, 0}, rad = 0., wsum = 0.;
+                for (int e = 0; e < kFieldCluster; e++) {
+                    const int64_t t = (int64_t)c * kFieldCluster + e;
+                    const int64_t sidx = src_order[(size_t)std::min<int64_t>(t, S - 1)];
+                    for (int a = 0; a < 3; a++) {
+                        r[a * kFieldCluster + e] = h_pos[3 * sidx + a];
+                        if (t < S) r[(3 + a) * kFieldCluster + e] = h_wn[3 * sidx + a];
+                        cc[a] += h_pos[3 * sidx + a] / kFieldCluster;
+                    }
+                }
+                for (int e = 0; e < kFieldCluster; e++) {
+                    double d2 = 0., w2 = 0.;
+                    for (int a = 0; a < 3; a++) {
+                        d2 += (r[a * kFieldCluster + e] - cc[a]) * (r[a * kFieldCluster + e] - cc[a]);
+                        w2 += r[(3 + a) * kFieldCluster + e] * r[(3 + a) * kFieldCluster + e];
+                    }
+                    rad = std::max(rad, std::sqrt(d2));
+                    wsum += std::sqrt(w2);
+                }
+                double* o = cl.data() + (size_t)c * kFieldClusterRec;
+                for (int a = 0; a < 3; a++) o[a] = cc[a];
+                o[3] = field_round_up(rad);
+                o[4] = field_round_up(wsum);
+            }
+            d_field_src.upload(rec, stream);
+            d_field_cl.upload(cl, stream);
+            HIPCHK(hipStreamSynchronize(stream));
+            field_src_ready = true;
+        }
+        d_field_ctr.alloc(kFieldCtrCount);
+        HIPCHK(hipMemsetAsync(d_field_ctr.p, 0, kFieldCtrCount * sizeof(unsigned long long), stream));
+        field_ev_used = 0;
+        FieldParams F;
+        F.lambda = lam > 0. ? lam : lambda;
+        F.cexp = -F.lambda * 2048.0 / 0.693147180559945309417;
+        F.lam2 = F.lambda * F.lambda;
+        F.budget = arith == SHM_STEP1_AUTO ? (budget > 0. ? budget : kFieldBudgetDefault) : 0.;
+        F.S = S;
+        F.n_clusters = field_clusters;
+        return F;
+    }
+    // Points per wave: a point's bits do not depend on it (shm_field_points.hip.h), so it is chosen for speed alone -- the measured best of each mode
+    // (profiles/field_points.txt: 8 where every pair is summed, 4 where the per-point classification holds registers too) where that leaves every SIMD
+    // several waves, fewer for a short list.  SHM_FIELD_P = 1, 2, 4 or 8 fixes it (tools/field_points_bench.py measures them).
+    int field_points_per_wave(int64_t Q, bool autom) const {
+        if (const char* k = knob("SHM_FIELD_P")) {
+            const int v = atoi(k);
+            if (v == 1 || v == 2 || v == 4 || v == 8) return v;
+        }
+        int P = autom ? 4 : 8;
+        while (P > 1 && Q / P < (int64_t)num_cus * 16) P >>= 1;
+        return P;
+    }
+    template <int P, typename TIO> void launch_field_p(const FieldParams& F, bool autom, int64_t Q, const TIO* pts, TIO* Y, TIO* ratio) {
+        const int waves = kBlock / 64;
+        // (as many workgroups as the list needs, at most 32 per CU: the waves stride over the groups of P points, so a long list fills the exponent table once
+        // per several groups and still leaves the dispatcher enough workgroups to even out the SIMDs)
+        const unsigned grid = (unsigned)std::min<int64_t>((Q + (int64_t)waves * P - 1) / ((int64_t)waves * P), (int64_t)num_cus * 32);
+        if (autom)
+            hipLaunchKernelGGL((field_points_kernel<P, true, TIO>), dim3(grid), dim3(kBlock), 0, stream, F, Q, pts, d_field_src.p, d_field_cl.p, d_exptab.p, Y, ratio, d_field_ctr.p);
+        else
+            hipLaunchKernelGGL((field_points_kernel<P, false, TIO>), dim3(grid), dim3(kBlock), 0, stream, F, Q, pts, d_field_src.p, d_field_cl.p, d_exptab.p, Y, ratio, d_field_ctr.p);
+    }
+    // one launch for up to 2^22 points (the grid stays far below 2^31 workgroups whatever Q a device entry is given), between a pair of events
+    template <typename TIO> void launch_field(const FieldParams& F, bool autom, int64_t Q, const TIO* pts, TIO* Y, TIO* ratio) {
+        const int64_t step = (int64_t)1 << 22;
+        for (int64_t q0 = 0; q0 < Q; q0 += step) {
+            const int64_t m = std::min(step, Q - q0);
+            while (field_ev.size() < field_ev_used + 2) field_ev.emplace_back(new Event());
+            field_ev[field_ev_used]->record(stream);
+            TIO* r = ratio ? ratio + q0 : nullptr;
+            switch (field_points_per_wave(m, autom)) {
+                case 1: launch_field_p<1, TIO>(F, autom, m, pts + 3 * q0, Y + 3 * q0, r); break;
+                case 2: launch_field_p<2, TIO>(F, autom, m, pts + 3 * q0, Y + 3 * q0, r); break;
+                case 4: launch_field_p<4, TIO>(F, autom, m, pts + 3 * q0, Y + 3 * q0, r); break;
+                default: launch_field_p<8, TIO>(F, autom, m, pts + 3 * q0, Y + 3 * q0, r); break;
+            }
+            HIPCHK(hipGetLastError());
+            field_ev[field_ev_used + 1]->record(stream);
+            field_ev_used += 2;
+        }
+    }
+    void field_end(const FieldParams& F, int32_t arith, int64_t Q, shm_field_stats* st) {
+        unsigned long long c[kFieldCtrCount];
+        HIPCHK(hipMemcpyAsync(c, d_field_ctr.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (!st) return;
+        memset(st, 0, sizeof *st);
+        st->points = Q;
+        st->answered = (int64_t)c[kFieldCtrAnswered];
+        st->out_of_zone = (int64_t)c[kFieldCtrOutOfZone];
+        st->points_redone = (int64_t)c[kFieldCtrRedone];
+        st->pairs_evaluated = (double)c[kFieldCtrEvaluated];
+        st->pairs_dropped = (double)c[kFieldCtrDropped];
+        st->lambda = F.lambda;
+        st->budget = F.budget;
+        st->arith = arith == SHM_STEP1_AUTO ? SHM_STEP1_AUTO : SHM_STEP1_EXACT_F64;
+        for (size_t i = 0; i + 1 < field_ev_used; i += 2) st->ms += (double)elapsed(*field_ev[i], *field_ev[i + 1]);
+    }
+    void field_at_points(int64_t Q, const double* pts, double lam, int32_t arith, double budget, double* Y_out, double* ratio_out, shm_field_stats* st) override {
+        const char* who = "field_at_points";
+        const auto cols = field_cols(pts, Y_out, ratio_out);
+        query_check(who, "points", "points or Y_out", Q, cols);
+        const FieldParams F = field_begin(who, lam, arith, budget);
+        query_stream(Q, cols, [&](int64_t m, void* const* d) { launch_field<double>(F, arith == SHM_STEP1_AUTO, m, (const double*)d[0], (double*)d[1], (double*)d[2]); });
+        field_end(F, arith, Q, st);
+    }
+    void field_at_points_device(int64_t Q, const void* pts, double lam, int32_t arith, double budget, void* Y_out, void* ratio_out, shm_field_stats* st) override {
+        const char* who = "field_at_points_device";
+        const auto cols = field_cols(pts, Y_out, ratio_out);
+        query_check(who, "points", "points or Y", Q, cols);
+        need_problem();
+        HIPCHK(hipSetDevice(cfg.device));
+        check_device_columns(who, "points", Q, cols);
+        const FieldParams F = field_begin(who, lam, arith, budget);
+        launch_field<T>(F, arith == SHM_STEP1_AUTO, Q, (const T*)pts, (T*)Y_out, (T*)ratio_out);
+        field_end(F, arith, Q, st);
     }
 
     // ---- point queries of the resident phi (shm_sample.hip.h) ------------------------------------------------------------------------------------------

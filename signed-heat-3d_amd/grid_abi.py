@@ -25,6 +25,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
                "shm_grid_closest_point", "shm_grid_closest_point_device", "shm_grid_mesh_raycast", "shm_grid_mesh_raycast_device",
+               "shm_grid_field_at_points", "shm_grid_field_at_points_device",
                "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
 
@@ -70,6 +71,16 @@ class ShmStep1Audit(C.Structure):
     _fields_ = [("n_audited", C.c_int64), ("n_not_owned", C.c_int64), ("n_nonfinite", C.c_int64), ("n_out_of_zone", C.c_int64),
                 ("n_finite_mismatch", C.c_int64), ("max_dy", C.c_double), ("worst_node", C.c_int64), ("worst_ratio", C.c_double), ("min_ratio", C.c_double),
                 ("budget", C.c_double), ("step1_arith", C.c_int32), ("within_budget", C.c_int32), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ShmFieldStats(C.Structure):
+    """shm_field_stats of include/shm_grid.h (shm_grid_field_at_points)."""
+    _fields_ = [("points", C.c_int64), ("answered", C.c_int64), ("out_of_zone", C.c_int64), ("points_redone", C.c_int64),
+                ("pairs_evaluated", C.c_double), ("pairs_dropped", C.c_double), ("lambda", C.c_double), ("budget", C.c_double), ("arith", C.c_int32),
+                ("ms", C.c_double)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -174,6 +185,10 @@ def load_library():
         lib.shm_grid_isosurface_components.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.shm_grid_get_isosurface_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.shm_grid_isosurface_keep_components.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(lib, "shm_grid_field_at_points"):   # added within ABI 5: found by symbol
+        lib.shm_grid_field_at_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(ShmFieldStats)]
+        lib.shm_grid_field_at_points_device.argtypes = lib.shm_grid_field_at_points.argtypes
     if hasattr(lib, "shm_grid_audit_step1"):   # added within ABI 5: found by symbol (another build named by SHM_GRID_LIB may predate it)
         lib.shm_grid_audit_step1.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmStep1Audit)]
         lib.shm_audit_sample_nodes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p]
@@ -762,6 +777,44 @@ class GridSolver:
         psi = torch.empty(N, dtype=torch.float64 if self.precision == SHM_F64 else torch.float32, device=torch.device("cuda", self.device))
         self._chk(self._lib.shm_grid_get_redistanced_device(self._h, psi.data_ptr() if N else None))
         return psi
+
+    _FIELD_ARITH = {"auto": 0, "exact": 1, "exact_f64": 1, "reference": 2, "reference_f64": 2}
+
+    def field_at_points(self, points, lam=0.0, arith="auto", budget=0.0, ratio=False, stats=False):
+        """Y = X / |X| of Steps 1-2 at points [Q, 3] of the caller's choosing (shm_grid_field_at_points), float64; needs set_problem only.  lam=0: the
+        problem's lambda.  arith "exact" sums every (point, source) pair, "auto" may drop sources under budget (0: 1e-8).  Returns Y [Q, 3], followed by
+        ratio [Q] (|X| / L1) with ratio=True and by the ShmFieldStats as a dict with stats=True.  NaN rows: a non-finite point or a point on a source."""
+        pts = _f64(points).reshape(-1, 3)
+        Q = pts.shape[0]
+        Y = np.empty((Q, 3), dtype=np.float64)
+        r = np.empty(Q, dtype=np.float64) if ratio else None
+        st = ShmFieldStats()
+        a = self._FIELD_ARITH[arith] if isinstance(arith, str) else int(arith)
+        self._chk(self._lib.shm_grid_field_at_points(self._h, Q, pts.ctypes.data if Q else None, float(lam), a, float(budget), Y.ctypes.data if Q else None,
+                                                     r.ctypes.data if ratio and Q else None, C.byref(st)))
+        out = (Y,) + ((r,) if ratio else ()) + ((st.as_dict(),) if stats else ())
+        return out[0] if len(out) == 1 else out
+
+    def field_at_points_device(self, points, lam=0.0, arith="auto", budget=0.0, ratio=False, stats=False):
+        """The same on device memory (shm_grid_field_at_points_device), with sample_device's conventions: points is a contiguous [Q, 3] torch tensor on this
+        handle's device with its dtype; the results are torch tensors of that dtype on that device (the arithmetic is fp64 whatever the dtype)."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("field_at_points_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if points.dtype != dt or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise ValueError("field_at_points_device: points must be a contiguous [Q, 3] %s tensor" % dt)
+        Q = points.shape[0]
+        Y = torch.empty((Q, 3), dtype=dt, device=points.device)
+        r = torch.empty(Q, dtype=dt, device=points.device) if ratio else None
+        if points.is_cuda:
+            torch.cuda.current_stream(points.device).synchronize()   # the points may still be in flight on torch's stream
+        st = ShmFieldStats()
+        a = self._FIELD_ARITH[arith] if isinstance(arith, str) else int(arith)
+        self._chk(self._lib.shm_grid_field_at_points_device(self._h, Q, points.data_ptr() if Q else None, float(lam), a, float(budget),
+                                                            Y.data_ptr() if Q else None, r.data_ptr() if ratio and Q else None, C.byref(st)))
+        out = (Y,) + ((r,) if ratio else ()) + ((st.as_dict(),) if stats else ())
+        return out[0] if len(out) == 1 else out
 
     def audit_step1(self, nodes=None, count=4096, seed=0, per_node=False):
         """What the Step 1 behind the resident Y cost at sampled nodes (shm_grid_audit_step1): the struct as a dict, plus "nodes", "dy" and "ratio" with

@@ -99,6 +99,22 @@ class SignedHeatGridSolver {
         return a;
     }
 
+    // Y = X / |X| of Steps 1-2 at the points of q -- anywhere, e.g. the tet barycentres of signed_heat_tet_solver.cpp:54-72 / :131-147 in the order of that
+    // solver's Y -- over the sources of the last computeDistance() (shm_grid_field_at_points).  lambda = 0: that call's lambda; the tet solver passes its own.
+    std::vector<Vector3> vectorFieldAt(const std::vector<Vector3>& q, double lambda = 0., std::vector<double>* ratio = nullptr, shm_field_stats* stats = nullptr,
+                                       int arith = SHM_STEP1_AUTO, double budget = 0.) {
+        if (!handle) throw std::runtime_error("vectorFieldAt: computeDistance has not been called");
+        std::vector<double> pts(3 * q.size()), Y(3 * q.size());
+        for (size_t a = 0; a < q.size(); a++)
+            for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+        if (ratio) ratio->resize(q.size());
+        if (shm_grid_field_at_points(handle, (int64_t)q.size(), pts.data(), lambda, arith, budget, Y.data(), ratio ? ratio->data() : nullptr, stats) != SHM_OK)
+            throw std::runtime_error(shm_grid_last_error(handle));
+        std::vector<Vector3> out(q.size());
+        for (size_t a = 0; a < q.size(); a++) out[a] = Vector3{Y[3 * a], Y[3 * a + 1], Y[3 * a + 2]};
+        return out;
+    }
+
     // Marching-cubes isosurface of the phi of the last computeDistance(), welded and numbered on the device in a canonical order
     // (shm_grid_isosurface_indexed): vertices ascend in 3*(i + j n + k n^2) + axis of their grid edge, faces in (cell, position in the case's table entry).
     void isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces) {

@@ -190,6 +190,20 @@ int shmh_sample(void* hv, int64_t Q, const double* pts, double* phi_out, double*
     });
 }
 
+// vectorFieldAt through the C++ class: Y of Steps 1-2 at pts [3Q] over the sources of the last compute_distance -> Y_out [3Q], ratio_out [Q] or NULL, stats or NULL.
+int shmh_vector_field_at(void* hv, int64_t Q, const double* pts, double lambda, int32_t arith, double budget, double* Y_out, double* ratio_out, shm_field_stats* stats) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> q((size_t)Q);
+        for (int64_t a = 0; a < Q; a++) q[(size_t)a] = Vector3{pts[3 * a], pts[3 * a + 1], pts[3 * a + 2]};
+        std::vector<double> r;
+        const std::vector<Vector3> Y = h->solver.vectorFieldAt(q, lambda, ratio_out ? &r : nullptr, stats, arith, budget);
+        for (int64_t a = 0; a < Q; a++)
+            for (int b = 0; b < 3; b++) Y_out[3 * a + b] = Y[(size_t)a][b];
+        if (ratio_out && Q > 0) std::memcpy(ratio_out, r.data(), r.size() * sizeof(double));
+    });
+}
+
 // castRays through the C++ class: rays [3Q] + [3Q] against phi = isoval of the last compute_distance -> t_out [Q], grad_out [3Q] or NULL, *n_hits finite answers.
 int shmh_raycast(void* hv, int64_t Q, const double* origins, const double* dirs, double isoval, double t_min, double t_max, double* t_out, double* grad_out,
                  int64_t* n_hits) {

@@ -46,11 +46,18 @@ static void usage() {
                  "      --closest-out <file> Raw float64, five values per point: distance (unsigned; NaN beyond --closest-max), nearest point xyz, triangle index (-1: none)\n"
                  "      --closest-max <D> How far the mesh may be from a point, in cells (default 4, at most 16)\n"
                  "      --mesh-rays <file> With --iso-indexed: rays to cast against the indexed mesh (filtered / offset as exported), in --rays' format, t in [0, inf)\n"
-                 "      --mesh-rays-out <file> Raw float64, five values per ray: t (NaN: no hit), triangle index (-1), barycentrics u v, number of triangles crossed\n";
+                 "      --mesh-rays-out <file> Raw float64, five values per ray: t (NaN: no hit), triangle index (-1), barycentrics u v, number of triangles crossed\n"
+                 "      --field-at <file> Points to evaluate the diffused normal field Y of Steps 1-2 at, anywhere in space, in --query's format\n"
+                 "      --field-out <file> Raw float64, three values per point: Y = X / |X| (NaN x 3 on a source or for a non-finite coordinate)\n"
+                 "      --field-lambda <L> The lambda of that sum (default 0: the solve's own)\n"
+                 "      --field-arith <auto|exact> auto drops far sources under --field-budget with a test per point (default), exact sums every pair\n"
+                 "      --field-budget <B> Error budget on Y under auto, within [1e-12, 1e-3] (default 0: 1e-8)\n";
 }
 
 int main(int argc, char** argv) {
     std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut, closestPath, closestOut, meshRaysPath, meshRaysOut;
+    std::string fieldPath, fieldOut, fieldArith = "auto";
+    double fieldLambda = 0., fieldBudget = 0.;
     double closestMax = 4.;
     double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
     bool redistance = false, redistanceExact = false, haveOffset = false;
@@ -101,6 +108,11 @@ int main(int argc, char** argv) {
         else if (s == "--closest-max") closestMax = atof(need("--closest-max"));
         else if (s == "--mesh-rays") meshRaysPath = need("--mesh-rays");
         else if (s == "--mesh-rays-out") meshRaysOut = need("--mesh-rays-out");
+        else if (s == "--field-at") fieldPath = need("--field-at");
+        else if (s == "--field-out") fieldOut = need("--field-out");
+        else if (s == "--field-lambda") fieldLambda = atof(need("--field-lambda"));
+        else if (s == "--field-arith") fieldArith = need("--field-arith");
+        else if (s == "--field-budget") fieldBudget = atof(need("--field-budget"));
         else if (!s.empty() && s[0] == '-') { std::cerr << "Flag could not be matched: " << s << std::endl; usage(); return 1; }
         else path = s;
     }
@@ -118,6 +130,10 @@ int main(int argc, char** argv) {
     }
     if (meshRaysPath.empty() != meshRaysOut.empty() || (!meshRaysPath.empty() && !isoIndexed)) {
         std::cerr << "--mesh-rays and --mesh-rays-out go together and cast against the mesh of --iso-indexed." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (fieldPath.empty() != fieldOut.empty() || (fieldArith != "auto" && fieldArith != "exact")) {
+        std::cerr << "--field-at and --field-out go together; --field-arith is auto or exact." << std::endl;
         return EXIT_FAILURE;
     }
     if (redistance && redistanceExact) {
@@ -296,6 +312,30 @@ int main(int argc, char** argv) {
             std::ofstream o(queryOut, std::ios::binary);
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
             std::cerr << "phi and its gradient at " << q.size() << " points written to " << queryOut << std::endl;
+        }
+        if (!fieldPath.empty()) {
+            std::ifstream f(fieldPath, std::ios::binary | std::ios::ate);
+            if (!f) throw std::runtime_error("cannot read " + fieldPath);
+            const std::streamsize bytes = f.tellg();
+            if (bytes % (std::streamsize)(3 * sizeof(double)) != 0) throw std::runtime_error(fieldPath + ": size is not a multiple of 24 bytes (float64 xyz triples)");
+            std::vector<double> raw((size_t)bytes / sizeof(double));
+            f.seekg(0);
+            f.read((char*)raw.data(), bytes);
+            std::vector<Vector3> q(raw.size() / 3);
+            for (size_t a = 0; a < q.size(); a++) q[a] = Vector3{raw[3 * a], raw[3 * a + 1], raw[3 * a + 2]};
+            shm_field_stats fs{};
+            const std::vector<Vector3> Y = solver.vectorFieldAt(q, fieldLambda, nullptr, &fs, fieldArith == "exact" ? SHM_STEP1_EXACT_F64 : SHM_STEP1_AUTO, fieldBudget);
+            for (size_t a = 0; a < q.size(); a++)
+                for (int b = 0; b < 3; b++) raw[3 * a + b] = Y[a][b];
+            std::ofstream o(fieldOut, std::ios::binary);
+            o.write((const char*)raw.data(), (std::streamsize)(raw.size() * sizeof(double)));
+            char line[512];
+            snprintf(line, sizeof line,
+                     "field at points: points %lld answered %lld out_of_zone %lld points_redone %lld pairs_evaluated %.0f pairs_dropped %.0f lambda %.17g budget %.3g "
+                     "arith %d ms %.3f; Y written to %s",
+                     (long long)fs.points, (long long)fs.answered, (long long)fs.out_of_zone, (long long)fs.points_redone, fs.pairs_evaluated, fs.pairs_dropped, fs.lambda,
+                     fs.budget, (int)fs.arith, fs.ms, fieldOut.c_str());
+            std::cerr << line << std::endl;
         }
         if (!raysPath.empty()) {
             std::ifstream f(raysPath, std::ios::binary | std::ios::ate);

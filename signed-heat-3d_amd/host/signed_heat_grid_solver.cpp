@@ -194,6 +194,20 @@ std::vector<double> SignedHeatGridSolver::evaluateFunction(const std::vector<Vec
     return phi;
 }
 
+std::vector<Vector3> SignedHeatGridSolver::vectorFieldAt(const std::vector<Vector3>& q, double lam, std::vector<double>* ratio, shm_field_stats* st, int arith,
+                                                         double budget) {
+    if (!handle) throw std::runtime_error("vectorFieldAt: computeDistance has not been called");
+    std::vector<double> pts(3 * q.size()), Y(3 * q.size());
+    for (size_t a = 0; a < q.size(); a++)
+        for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+    if (ratio) ratio->resize(q.size());
+    if (shm_grid_field_at_points(handle, (int64_t)q.size(), pts.data(), lam, arith, budget, Y.data(), ratio ? ratio->data() : nullptr, st) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_field_at_points: ") + shm_grid_last_error(handle));
+    std::vector<Vector3> out(q.size());
+    for (size_t a = 0; a < q.size(); a++) out[a] = Vector3{Y[3 * a], Y[3 * a + 1], Y[3 * a + 2]};
+    return out;
+}
+
 std::vector<double> SignedHeatGridSolver::castRays(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double isoval, double tMin, double tMax,
                                                    std::vector<Vector3>* gradients) {
     if (!handle) throw std::runtime_error("castRays: computeDistance has not been called");

@@ -96,6 +96,14 @@ class SignedHeatGridSolver {
                                      double tMax = std::numeric_limits<double>::infinity(), std::vector<int64_t>* triangles = nullptr,
                                      std::vector<double>* bary = nullptr, std::vector<int32_t>* counts = nullptr);
 
+    // The diffused, normalised normal field Y = X / |X| of Steps 1-2 at every point of q -- anywhere, not only at grid nodes -- summed on the device over the
+    // sources of the LAST computeDistance() call (shm_grid_field_at_points; contract in include/shm_grid.h).  What the reference's tet solver sums at its tet
+    // barycentres (signed_heat_tet_solver.cpp:54-72, :131-147).  lambda = 0: the lambda of that call; a positive value overrides it.  arith: SHM_STEP1_AUTO
+    // drops far clusters of sources under budget (0: 1e-8) with an a-posteriori test per point, SHM_STEP1_EXACT_F64 sums every pair.  ratio (optional) receives
+    // |X| / sum_s |w_s|_1 g_s per point; a point on a source or with a non-finite coordinate gets NaN x 3.  No resident field is touched.
+    std::vector<Vector3> vectorFieldAt(const std::vector<Vector3>& q, double lambda = 0., std::vector<double>* ratio = nullptr, shm_field_stats* stats = nullptr,
+                                       int arith = SHM_STEP1_AUTO, double budget = 0.);
+
     // What the Step 1 of the LAST computeDistance() call cost on the normalised field Y, audited on the device at a deterministic stratified sample of `count`
     // grid nodes (shm_audit_sample_nodes + shm_grid_audit_step1: max |dY| against the reference's arithmetic over every source, the budget in force, the verdict).
     shm_step1_audit auditStep1(size_t count = 4096, uint64_t seed = 0);

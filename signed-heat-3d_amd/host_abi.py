@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .grid_abi import ISO_COMPONENT_DTYPE, ShmRedistanceExactStats, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
+from .grid_abi import ISO_COMPONENT_DTYPE, ShmFieldStats, ShmRedistanceExactStats, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -43,6 +43,8 @@ def load_host_library():
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
+    if hasattr(lib, "shmh_vector_field_at"):
+        lib.shmh_vector_field_at.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(ShmFieldStats)]
     if hasattr(lib, "shmh_closest_points"):
         lib.shmh_closest_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     if hasattr(lib, "shmh_cast_rays_mesh"):
@@ -137,6 +139,18 @@ class HostSolver:
         g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
         self._chk(self._lib.shmh_sample(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None))
         return (phi, g) if grad else phi
+
+    def vector_field_at(self, points, lam=0.0, arith="auto", budget=0.0, ratio=False, stats=False):
+        """vectorFieldAt of the C++ mirror at points [Q, 3]: Y of Steps 1-2 over the sources of the last compute_distance (shm_grid_field_at_points).
+        Returns Y [Q, 3], followed by ratio [Q] with ratio=True and the ShmFieldStats as a dict with stats=True."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        Y = np.empty((pts.shape[0], 3), dtype=np.float64)
+        r = np.empty(pts.shape[0], dtype=np.float64) if ratio else None
+        st = ShmFieldStats()
+        self._chk(self._lib.shmh_vector_field_at(self._h, pts.shape[0], pts.ctypes.data, float(lam), {"auto": 0, "exact": 1}[arith], float(budget), Y.ctypes.data,
+                                                 r.ctypes.data if ratio else None, C.byref(st)))
+        out = (Y,) + ((r,) if ratio else ()) + ((st.as_dict(),) if stats else ())
+        return out[0] if len(out) == 1 else out
 
     def raycast(self, origins, dirs, isovalue=0.0, t_min=0.0, t_max=float("inf"), grad=False):
         """castRays of the C++ mirror: where each ray origins[q] + t dirs[q] first meets phi = isovalue of the last compute_distance (shm_grid_raycast).
