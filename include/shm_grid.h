@@ -261,6 +261,17 @@ shm_status shm_grid_apply_projector(shm_solver* s, double* v);
 
 /* out = M^-1 v with the DCT preconditioner alone (no projection); v,out: n^3 doubles on the host (world==1). */
 shm_status shm_grid_apply_preconditioner(shm_solver* s, const double* v, double* out);
+/* The operator the iterative dual solver applies once per iteration, S = A K^+ A^T through the grid, by the launches of that iteration.  Test entry points,
+ * added within ABI 5 (no struct changed, SHM_GRID_ABI_VERSION stays 5; detect them by their symbols), world==1.  Both set the constraints up as
+ * shm_grid_get_schur does and leave no Y, divergence or phi behind.  SHM_ERR_STATE before shm_grid_set_problem; SHM_ERR_INVALID for NULL, world != 1, a grid
+ * without the FFT line transforms (n not 2^k in [16, 1024], or slabs that are not a power-of-two number of equal ones), and for the sparse sweeps on several slabs.
+ *   shm_grid_apply_kplus_sparse: the five sparse sweeps alone.  v, out: n^3 doubles on the host.  Only the nodes the constraint rows touch (the corners of
+ *     shm_grid_get_constraints) are read; they are stored, rounded once to the handle's precision, into a field that is zero everywhere else -- the iteration's
+ *     A^T mu.  out = K^+ of that field on the touched nodes, 0 on every other node (the sweeps compute nothing meaningful there).
+ *   shm_grid_apply_schur_grid: out[0..m) = S v for v[0..m), m the rows of shm_grid_get_constraints: scatter A^T v, the sweeps, gather.  sweeps 0: the sparse
+ *     sweeps (what the iteration runs on one slab); sweeps 1: the dense sweeps of shm_grid_apply_preconditioner (what it runs on several slabs). */
+shm_status shm_grid_apply_kplus_sparse(shm_solver* s, const double* v /* [n^3] */, double* out /* [n^3] */);
+shm_status shm_grid_apply_schur_grid(shm_solver* s, const double* v /* [m] */, int32_t sweeps, double* out /* [m] */);
 
 /* --- isosurface of the resident phi (headless stand-in for the demo's contour, src/main.cpp:116-128,167-191: Polyscope's marching cubes on the node
  * scalar quantity, setIsosurfaceLevel + registerIsosurfaceAsMesh).  inside = phi < isovalue, normals towards increasing phi, one vertex per cut grid edge

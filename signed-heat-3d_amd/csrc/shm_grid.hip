@@ -213,6 +213,19 @@ shm_status shm_grid_apply_preconditioner(shm_solver* s, const double* v, double*
         s->impl->apply_preconditioner(v, out);
     });
 }
+shm_status shm_grid_apply_kplus_sparse(shm_solver* s, const double* v, double* out) {
+    return guard(s, [&] {
+        if (!v || !out) throw shm::Error(SHM_ERR_INVALID, "null argument");
+        s->impl->apply_kplus_sparse(v, out);
+    });
+}
+shm_status shm_grid_apply_schur_grid(shm_solver* s, const double* v, int32_t sweeps, double* out) {
+    return guard(s, [&] {
+        if (!v || !out) throw shm::Error(SHM_ERR_INVALID, "null argument");
+        if (sweeps != 0 && sweeps != 1) throw shm::Error(SHM_ERR_INVALID, "apply_schur_grid: sweeps 0 (sparse) or 1 (dense)");
+        s->impl->apply_schur_grid(v, sweeps == 0, out);
+    });
+}
 
 shm_status shm_grid_isosurface(shm_solver* s, double isovalue, int64_t* n_vertices, int64_t* n_triangles) {
     return guard(s, [&] { s->impl->isosurface(isovalue, SHM_ISO_MARCHING_CUBES, n_vertices, n_triangles); });

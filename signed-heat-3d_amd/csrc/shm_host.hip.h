@@ -557,6 +557,8 @@ struct SolverBase {
     virtual void get_constraints(int64_t*, double*, int32_t*) = 0;
     virtual void apply_projector(double*) = 0;
     virtual void apply_preconditioner(const double*, double*) = 0;
+    virtual void apply_kplus_sparse(const double*, double*) = 0;
+    virtual void apply_schur_grid(const double*, int32_t, double*) = 0;
     virtual void get_schur(double*, int32_t*) = 0;
     virtual void spd_solve(const double*, int32_t, const double*, int32_t, double*, int32_t*) = 0;
     virtual void isosurface(double, int, int64_t*, int64_t*) = 0;

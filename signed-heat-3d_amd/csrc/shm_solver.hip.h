@@ -2313,6 +2313,19 @@ struct Solver final : SolverBase {
         launch_dct<DCT_INV, TP, T, false, true>(Q, sl.n_act_x, sl.S4.p, arr(sl, out_sel), (const T*)nullptr, nullptr, sl.act_x.p);
     }
 
+    // The two ends of one application of S = A K^+ A^T through the grid (solve_dual, apply_schur_grid); vec: the m-vector's slot in sl.dv
+    void gather(int sel) {  // red[1..m] = A * arr(sel), all-reduced
+        for (Slab<T>& sl : slabs)
+            hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(1 + (8 * m + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m, sl.row_ptr.p, sl.ent_node.p,
+                               sl.ent_coef.p, arr(sl, sel), sl.partials.p, 0, sl.red.p);
+        allreduce(0, 1 + m);
+    }
+    void scatter(int vec, int sel, int accumulate, double scale = 1.0, bool save = false) {  // arr(sel) (+)= scale A^T v
+        for (Slab<T>& sl : slabs)
+            hipLaunchKernelGGL((scatter_rows_to_nodes_kernel<T>), dim3((sl.n_touched + kBlock - 1) / kBlock + 1), dim3(kBlock), 0, stream, sl.n_touched,
+                               sl.node_id.p, sl.node_ptr.p, sl.ent_row.p, sl.nent_coef.p, sl.dv.p + (size_t)vec * mp, accumulate, arr(sl, sel), scale, save ? sl.touched_save.p : (T*)nullptr);
+    }
+
     // ------------------------------------------------------------------------------------------
     // Dual solver (see the block comment above the dual_* kernels): CG on S = A K^+ A^T for the multipliers.
     void solve_dual(const shm_opts& o, shm_stats* st, SolveClock& clk) {
@@ -2321,17 +2334,6 @@ struct Solver final : SolverBase {
         auto mv = [&](Slab<T>& sl, int k) { return sl.dv.p + (size_t)k * mp; };
         enum { V_MU = 0, V_R = 1, V_P = 2, V_Z = 3, V_T1 = 4, V_T2 = 5, V_G = 6 };
         const std::vector<int> nopart(slabs.size(), 0);
-        auto gather = [&](int sel) {  // red[1..m] = A * arr(sel), all-reduced
-            for (Slab<T>& sl : slabs)
-                hipLaunchKernelGGL((gather_rows_kernel<T>), dim3(1 + (8 * m + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, m, sl.row_ptr.p, sl.ent_node.p,
-                                   sl.ent_coef.p, arr(sl, sel), sl.partials.p, 0, sl.red.p);
-            allreduce(0, 1 + m);
-        };
-        auto scatter = [&](int vec, int sel, int accumulate, double scale = 1.0, bool save = false) {  // arr(sel) (+)= scale A^T v
-            for (Slab<T>& sl : slabs)
-                hipLaunchKernelGGL((scatter_rows_to_nodes_kernel<T>), dim3((sl.n_touched + kBlock - 1) / kBlock + 1), dim3(kBlock), 0, stream, sl.n_touched,
-                                   sl.node_id.p, sl.node_ptr.p, sl.ent_row.p, sl.nent_coef.p, mv(sl, vec), accumulate, arr(sl, sel), scale, save ? sl.touched_save.p : (T*)nullptr);
-        };
         auto precondition = [&](int init) {  // z = Pm(G^-1 B G^-1 r); p = z (+ beta p)
             for (Slab<T>& sl : slabs) {
                 apply_Ginv(mv(sl, V_R), mv(sl, V_T1), true, stream);
@@ -4330,6 +4332,60 @@ struct Solver final : SolverBase {
         HIPCHK(hipGetLastError());
         for (Slab<T>& sl : slabs) HIPCHK(hipMemcpyAsync(sl.q.p, sl.z.p, sl.ntot * sizeof(T), hipMemcpyDeviceToDevice, stream));
         copy_owned_to_host(SHM_FIELD_PHI, out);
+        have_conv = have_div = have_phi = false;
+        drop_phi_derived();
+    }
+
+    // What the two entry points below share: one process, the FFT transforms, the constraint set-up of the stage entry points (never the direct form, so the
+    // active tiles exist on a single slab) and the transform tables
+    void setup_dual_operator(const char* who) {
+        need_problem();
+        if (cfg.world != 1) throw Error(SHM_ERR_INVALID, fmt("%s is a single-process test entry point", who));
+        if (!fft_available()) throw Error(SHM_ERR_INVALID, fmt("%s: the sweeps of the dual iteration need n = 2^k in [16,1024] and a power-of-two number of equal z-slabs dividing n", who));
+        HIPCHK(hipSetDevice(cfg.device));
+        build_constraints(plan_inputs(nullptr), Plan());
+        setup_precond();
+    }
+    bool sparse_sweeps_ready() const { return total_slabs == 1 && slabs[0].n_act_x > 0; }   // solve_dual's sparse_ok
+
+    // Test entry point: the sparse sweeps of the dual iteration alone.  p = v on the touched nodes and 0 elsewhere (as solve_dual prepares it),
+    // launch_precond_sparse(ARR_P, ARR_Z), out = z on the touched nodes and 0 elsewhere.
+    void apply_kplus_sparse(const double* v, double* out) override {
+        setup_dual_operator("apply_kplus_sparse");
+        if (!sparse_sweeps_ready()) throw Error(SHM_ERR_INVALID, "apply_kplus_sparse: the sparse sweeps serve a single z-slab");
+        std::vector<double> w(N, 0.);
+        for (const Row& r : rows)
+            for (int e = 0; e < 8; e++) w[(size_t)r.nodes[e]] = v[(size_t)r.nodes[e]];
+        upload_owned(w.data(), 0);
+        launch_precond_sparse(ARR_P, ARR_Z);
+        HIPCHK(hipGetLastError());
+        Slab<T>& sl = slabs[0];
+        HIPCHK(hipMemcpyAsync(sl.q.p, sl.z.p, sl.ntot * sizeof(T), hipMemcpyDeviceToDevice, stream));
+        copy_owned_to_host(SHM_FIELD_PHI, w.data());
+        std::fill(out, out + N, 0.);
+        for (const Row& r : rows)
+            for (int e = 0; e < 8; e++) out[(size_t)r.nodes[e]] = w[(size_t)r.nodes[e]];
+        have_conv = have_div = have_phi = false;
+        drop_phi_derived();
+    }
+
+    // Test entry point: out[0..m) = S v with S = A K^+ A^T applied through the grid, launch for launch what one iteration of solve_dual does: p = 0, scatter,
+    // the sweeps (sparse: launch_precond_sparse, the iteration's choice on one slab; otherwise launch_precond, the form several slabs take), gather.
+    void apply_schur_grid(const double* v, int32_t sparse, double* out) override {
+        setup_dual_operator("apply_schur_grid");
+        if (sparse && !sparse_sweeps_ready()) throw Error(SHM_ERR_INVALID, "apply_schur_grid: the sparse sweeps serve a single z-slab");
+        const int vec = 2;   // (solve_dual's V_P)
+        for (Slab<T>& sl : slabs) {
+            HIPCHK(hipMemsetAsync(sl.p.p, 0, sl.ntot * sizeof(T), stream));
+            HIPCHK(hipMemcpyAsync(sl.dv.p + (size_t)vec * mp, v, (size_t)m * sizeof(double), hipMemcpyHostToDevice, stream));
+        }
+        scatter(vec, ARR_P, 0);
+        if (sparse) launch_precond_sparse(ARR_P, ARR_Z);
+        else launch_precond(false, ARR_P, ARR_Z);
+        gather(ARR_Z);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(out, slabs[0].red.p + 1, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
         have_conv = have_div = have_phi = false;
         drop_phi_derived();
     }

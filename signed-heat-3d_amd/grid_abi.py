@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 # every symbol include/shm_grid.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
-               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_isosurface", "shm_grid_isosurface_ex", "shm_grid_get_isosurface",
+               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_apply_kplus_sparse", "shm_grid_apply_schur_grid", "shm_grid_isosurface","shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
@@ -171,6 +171,9 @@ def load_library():
         lib.shm_grid_spd_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]
     lib.shm_grid_apply_projector.argtypes = [C.c_void_p, C.c_void_p]
     lib.shm_grid_apply_preconditioner.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "shm_grid_apply_kplus_sparse"):   # added within ABI 5: found by symbol
+        lib.shm_grid_apply_kplus_sparse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.shm_grid_apply_schur_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
     lib.shm_grid_isosurface.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.shm_grid_isosurface_ex.argtypes = [C.c_void_p, C.c_double, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.shm_grid_get_isosurface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -424,6 +427,27 @@ class GridSolver:
         v = _f64(v).reshape(-1)
         out = np.empty_like(v)
         self._chk(self._lib.shm_grid_apply_preconditioner(self._h, v.ctypes.data, out.ctypes.data))
+        return out
+
+    def apply_kplus_sparse(self, v):
+        """K^+ by the sparse sweeps of the dual iteration alone (shm_grid_apply_kplus_sparse): v [n^3] is read on the nodes the constraint rows touch, the rest
+        counts as zero; the result holds K^+ of that field on the touched nodes and zeros elsewhere.  Test entry point."""
+        v = _f64(v).reshape(-1)
+        if self.n and v.size != self.n ** 3:
+            raise ValueError("apply_kplus_sparse: v must hold n^3 = %d values, got %d" % (self.n ** 3, v.size))
+        out = np.empty_like(v)
+        self._chk(self._lib.shm_grid_apply_kplus_sparse(self._h, v.ctypes.data, out.ctypes.data))
+        return out
+
+    def apply_schur_grid(self, mu, sweeps="sparse"):
+        """S mu [m] with S = A K^+ A^T applied through the grid as one iteration of the dual solver applies it (shm_grid_apply_schur_grid): sweeps "sparse"
+        (the iteration's own on one slab) or "dense" (what several slabs run).  Test entry point."""
+        mu = _f64(mu).reshape(-1)
+        m = len(self.get_constraints()[0])
+        if mu.size != m:
+            raise ValueError("apply_schur_grid: mu must hold m = %d values, got %d" % (m, mu.size))
+        out = np.empty(m, dtype=np.float64)
+        self._chk(self._lib.shm_grid_apply_schur_grid(self._h, mu.ctypes.data, {"sparse": 0, "dense": 1}[sweeps], out.ctypes.data))
         return out
 
     ISO_METHOD = {"marching_cubes": 0, "marching_tets": 1}
