@@ -567,7 +567,6 @@ struct Solver final : SolverBase {
         log("[shm] problem set: n=%d N=%zu S=%lld slabs=%d(local %d) vec=%d", n, N, (long long)S, total_slabs, cfg.local_slabs, vec);
     }
 
-    // shm_opts.step1_arith: the tiered kernel unless the caller (or SHM_CONV_EXACT=1, read per call: tests flip it inside one process) asks for the reference's arithmetic
     // the whole-grid solver behind solve_gathered(): created and given the current problem on first use
     bool full_wanted() const { return cfg.world > 1 && !solve_only && n >= 4 && n <= 1024; }
     void ensure_full() {
@@ -609,6 +608,7 @@ struct Solver final : SolverBase {
         in.knobs = plan_knobs(knob);
         return in;
     }
+    // shm_opts.step1_arith: the tiered kernel unless the caller (or SHM_CONV_EXACT=1, read per call: tests flip it inside one process) asks for the reference's arithmetic
     void select_step1_arith(int arith) {
         if (arith != SHM_STEP1_AUTO && arith != SHM_STEP1_EXACT_F64 && arith != SHM_STEP1_REFERENCE_F64) throw Error(SHM_ERR_INVALID, "unknown step1_arith");
         // SHM_STEP1_REFERENCE_F64: the all-fp64 kernel (conv_normalize_kernel<double>, the cubic body: what SHM_CONV_EXACT_CLASSIC=1 selects under EXACT_F64), and in
