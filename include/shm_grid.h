@@ -321,6 +321,43 @@ shm_status shm_grid_get_isosurface(shm_solver* s, double* vertices /* [3*nv] */,
 shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered);
 shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered);
 
+/* --- C1 cubic reads of the resident phi: value, gradient and Hessian ---------------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
+ * Interpolant: the Keys cubic convolution (Catmull-Rom, a = -1/2), separable over 4 x 4 x 4 nodes of the phi shm_grid_get_phi returns.  It passes through
+ *   the nodes, is C1 over the whole box (shm_grid_sample's gradient jumps at every cell face), reproduces quadratics exactly, and needs no prefilter pass:
+ *   it reads the resident phi as it stands.  It smooths nothing, it interpolates: a kink the nodes hold at the scale of a cell (around the constraint
+ *   cells) stays a kink.  Value, gradient and Hessian come from the same loads.
+ * Cell and t per axis: shm_grid_sample's.  i = floor((q - bbox_min) / cell); i > n-2 -> i = n-2, t = 1; otherwise t = (q - (i*cell + bbox_min)) / cell.
+ * Weights on the nodes at offsets -1, 0, 1, 2 from i (Horner forms, fp64, unfused):
+ *   w   = ( ((-t+2)t-1)t/2,  ((3t-5)t*t+2)/2,  ((-3t+4)t+1)t/2,  (t-1)t*t/2 )
+ *   w'  = ( ((-3t+4)t-1)/2,  (9t-10)t/2,       ((-9t+8)t+1)/2,   (3t-2)t/2 )
+ *   w'' = ( -3t+2,           9t-5,             -9t+4,            3t-1 )
+ * Faces: Keys' ghost node f(-1) = 3 f(0) - 3 f(1) + f(2), and f(n) = 3 f(n-1) - 3 f(n-2) + f(n-3) at the top, which keeps quadratics exact in the cells
+ *   at the faces.  It is folded into the weights, so only nodes of the grid are read: at i = 0 the nodes 0, 1, 2 carry (w0 + 3 w-1, w1 - 3 w-1, w2 + w-1),
+ *   at i = n-2 the nodes n-3, n-2, n-1 carry (w-1 + w2, w0 - 3 w2, w1 + 3 w2), and the same for w' and w''.  A face cell reads three nodes on that
+ *   axis, not four; the absent node is neither loaded nor multiplied by zero.  n >= 4.
+ * Nesting (the order of operations is a specification; tests/sample_cubic_ref.py restates it): x first, a row's three or four nodes summed from the lowest
+ *   index up; then y over the rows of a plane; then z over the planes.  Gradient and Hessian entries use the same nest with w' or w'' in place of w on the
+ *   differentiated axes; the gradient is divided by cell once at the end, Hessian entries twice.  Hessian layout: xx, yy, zz, xy, xz, yz.
+ * Box: shm_grid_sample's closed box, no tolerance band.  A point outside it, or with a NaN coordinate, gets NaN in every output asked for;
+ *   *n_answered counts the points in the box.
+ * Non-finite nodes: no special case.  IEEE arithmetic on exactly the nodes the rule above reads (27 to 64 of them): every output is non-finite where
+ *   one of those nodes is (a node of weight zero included), and finite elsewhere.
+ * Precision: the handle's nodes (fp32 or fp64) are read, points are promoted to fp64 first and everything after the load is fp64, so an SHM_F32
+ *   handle returns the exact cubic of its fp32 nodes, rounded once on the store.  Two calls give bit-identical outputs, whatever local_slabs is.
+ * State: valid whenever shm_grid_sample is; SHM_ERR_STATE before a solve, after a test entry point that overwrote phi, and with world > 1 (the stencil
+ *   would need two ghost planes; any local_slabs works: every plane is read from the slab that owns it).  Not collective.  phi, Y, the meshes, the brick
+ *   extrema and psi are left as they were.
+ * grad_out and hess_out are optional independently of each other; an output passed as NULL is not written.
+ * shm_grid_sample_cubic: host buffers, fp64; pts [3Q] xyz-interleaved, phi_out [Q], grad_out [3Q] or NULL, hess_out [6Q] or NULL.  The points stream
+ *   through the pair of pinned staging slots the handle's host query entries share (see shm_grid_sample), in chunks of 2^19 (104 bytes per query).
+ *   Q = 0 is valid; Q < 0, Q > 2^48 (both calls), or NULL pts / phi_out with Q > 0, is SHM_ERR_INVALID.
+ * shm_grid_sample_cubic_device: device buffers of the handle's precision on the handle's device, same layouts; synchronous.  Every pointer is checked
+ *   as shm_grid_sample_device checks its own before anything is launched. */
+shm_status shm_grid_sample_cubic(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out /* [3Q] or NULL */,
+                                 double* hess_out /* [6Q] or NULL */, int64_t* n_answered);
+shm_status shm_grid_sample_cubic_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, void* d_hess, int64_t* n_answered);
+
 /* --- indexed isosurface of the resident phi, built on the device in a canonical order ------------------------------------------------------------------
  * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the three entry points by their symbols (dlsym).
  * The same surface as shm_grid_isosurface (marching cubes: the case table, inside = phi < isovalue, one vertex per cut grid edge at

@@ -266,6 +266,12 @@ shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* 
 shm_status shm_grid_sample_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, int64_t* n_answered) {
     return guard(s, [&] { s->impl->sample_device(Q, d_pts, d_phi, d_grad, n_answered); });
 }
+shm_status shm_grid_sample_cubic(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, double* hess_out, int64_t* n_answered) {
+    return guard(s, [&] { s->impl->sample_cubic(Q, pts, phi_out, grad_out, hess_out, n_answered); });
+}
+shm_status shm_grid_sample_cubic_device(shm_solver* s, int64_t Q, const void* d_pts, void* d_phi, void* d_grad, void* d_hess, int64_t* n_answered) {
+    return guard(s, [&] { s->impl->sample_cubic_device(Q, d_pts, d_phi, d_grad, d_hess, n_answered); });
+}
 
 shm_status shm_grid_raycast(shm_solver* s, int64_t Q, const double* origins, const double* dirs, double isovalue, double t_min, double t_max, double* t_out,
                             double* grad_out, int64_t* n_hits) {

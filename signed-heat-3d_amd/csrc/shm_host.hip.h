@@ -565,6 +565,8 @@ struct SolverBase {
     virtual void get_isosurface(double*, int64_t*) = 0;
     virtual void sample(int64_t, const double*, double*, double*, int64_t*) = 0;
     virtual void sample_device(int64_t, const void*, void*, void*, int64_t*) = 0;
+    virtual void sample_cubic(int64_t, const double*, double*, double*, double*, int64_t*) = 0;
+    virtual void sample_cubic_device(int64_t, const void*, void*, void*, void*, int64_t*) = 0;
     virtual void field_at_points(int64_t, const double*, double, int32_t, double, double*, double*, shm_field_stats*) = 0;
     virtual void field_at_points_device(int64_t, const void*, double, int32_t, double, void*, void*, shm_field_stats*) = 0;
     virtual void isosurface_indexed(double, int64_t*, int64_t*) = 0;

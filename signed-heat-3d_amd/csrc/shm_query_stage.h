@@ -11,6 +11,7 @@
 //   closest_point  points 24 | distance 8 | foot points 24 | triangles 8 (int64)               64
 //   mesh_raycast   origins 24 | directions 24 | t 8 | triangles 8 (int64) | barycentrics 16 | counts 4 (int32)    84
 //   field_at_points  points 24 | Y 24 | ratio 8                                                56
+//   sample_cubic   points 24 | phi 8 | gradient 24 | hessian 48                                104  (in chunks of 2^19, so that a slot stays within the 84 MiB)
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -19,6 +20,7 @@
 namespace shm {
 
 constexpr int64_t kQueryChunk = (int64_t)1 << 20;   // queries per chunk of a host entry: at most 84 MiB of pinned staging and as much device memory per slot, two slots
+constexpr int64_t kCubicQueryChunk = (int64_t)1 << 19;   // sample_cubic's chunk: 104 bytes per query, 52 MiB per slot
 constexpr int64_t kQueryMaxQ = (int64_t)1 << 48;    // the largest Q an entry accepts: Q times the bytes of a query must not wrap
 constexpr int kQueryMaxCols = 8;
 

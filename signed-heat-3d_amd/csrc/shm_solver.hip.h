@@ -26,6 +26,7 @@
 #include "shm_iso_indexed.hip.h"
 #include "shm_iso_components.hip.h"
 #include "shm_raycast.hip.h"
+#include "shm_sample_cubic.hip.h"
 #include "shm_redistance.hip.h"
 #include "shm_redistance_exact.hip.h"
 #include "shm_closest.hip.h"
@@ -3191,10 +3192,10 @@ struct Solver final : SolverBase {
         }
         stage.cap = bytes;
     }
-    // The host entries: Q queries in chunks of 2^20 through the two slots, so that the host copies of one chunk overlap the device work of the other.
+    // The host entries: Q queries in chunks of 2^20 (2^19 for sample_cubic, whose queries are the widest) through the two slots, so that the host copies of one chunk overlap the device work of the other.
     // launch(m, d) enqueues the kernels of one chunk of m queries; d[i] is the device address of column i, null for an absent one.
-    template <size_t NC, typename Launch> void query_stream(int64_t Q, const std::array<QueryCol, NC>& cols, Launch&& launch) {
-        const QueryChunks ch = query_chunks(Q);
+    template <size_t NC, typename Launch> void query_stream(int64_t Q, const std::array<QueryCol, NC>& cols, Launch&& launch, int64_t chunk = kQueryChunk) {
+        const QueryChunks ch = query_chunks(Q, chunk);
         if (ch.n == 0) return;
         const QueryLayout L = query_layout(cols.data(), (int)NC, ch.C);
         stage_reserve(L.slot_bytes);
@@ -3825,6 +3826,72 @@ struct Solver final : SolverBase {
         launch_raycast<T>(P, Q, (const T*)org, (const T*)dir, (T*)t_out, (T*)grad);
         const int64_t a = raycast_end();
         if (n_hits) *n_hits = a;
+    }
+
+    // ---- C1 cubic reads of the resident phi (shm_sample_cubic.hip.h) --------------------------------------------------------------------------------------------
+    // Working memory: the slab table (written again by every call, like d_rd_slabs) and the counter.  Every plane is read from the slab that owns it, so no
+    // ghost plane is read and nothing is exchanged: the call writes nothing of the handle but these two.
+    DevArray<RaySlab<T>> d_cubic_slabs;
+    DevArray<unsigned long long> d_cubic_count;
+
+    static std::array<QueryCol, 4> cubic_cols(const void* pts, const void* out, const void* grad, const void* hess) {
+        return {{query_in(pts, 24, "the point buffer"), query_out(out, 8, "the phi buffer"), query_out(grad, 24, "the gradient buffer", true),
+                 query_out(hess, 48, "the Hessian buffer", true)}};
+    }
+    void cubic_check(const char* who, int64_t Q, const std::array<QueryCol, 4>& cols) {
+        query_check(who, "points", "points or output", Q, cols);
+        need_phi();
+        if (cfg.world != 1)
+            throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: the 4^3 stencil would need two ghost planes (gather phi, or sample on a single-process handle)", who));
+        if (n < 4) throw Error(SHM_ERR_STATE, fmt("%s: the cubic needs n >= 4", who));
+    }
+    CubicParams cubic_begin() {
+        HIPCHK(hipSetDevice(cfg.device));
+        CubicParams P;
+        P.n = n;
+        P.nslabs = (int)slabs.size();
+        P.cell = cell;
+        for (int a = 0; a < 3; a++) {
+            P.bbox_min[a] = bbox_min[a];
+            P.hi[a] = (n - 1) * cell + bbox_min[a];
+        }
+        upload_ray_slabs(d_cubic_slabs);
+        d_cubic_count.alloc(1);
+        HIPCHK(hipMemsetAsync(d_cubic_count.p, 0, sizeof(unsigned long long), stream));
+        return P;
+    }
+    int64_t cubic_end() {
+        unsigned long long c = 0;
+        HIPCHK(hipMemcpyAsync(&c, d_cubic_count.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        return (int64_t)c;
+    }
+    template <typename TIO> void launch_cubic(const CubicParams& P, int64_t Q, const TIO* pts, TIO* out, TIO* grad, TIO* hess) {
+        if (Q <= 0) return;
+        const int grid = grid_for((size_t)Q, 16384);
+        if (hess) hipLaunchKernelGGL((sample_cubic_kernel<T, TIO, kCubicHess>), dim3(grid), dim3(kBlock), 0, stream, P, Q, pts, d_cubic_slabs.p, out, grad, hess, d_cubic_count.p);
+        else if (grad) hipLaunchKernelGGL((sample_cubic_kernel<T, TIO, kCubicGrad>), dim3(grid), dim3(kBlock), 0, stream, P, Q, pts, d_cubic_slabs.p, out, grad, hess, d_cubic_count.p);
+        else hipLaunchKernelGGL((sample_cubic_kernel<T, TIO, kCubicValue>), dim3(grid), dim3(kBlock), 0, stream, P, Q, pts, d_cubic_slabs.p, out, grad, hess, d_cubic_count.p);
+        HIPCHK(hipGetLastError());
+    }
+    void sample_cubic(int64_t Q, const double* pts, double* out, double* grad, double* hess, int64_t* n_answered) override {
+        const auto cols = cubic_cols(pts, out, grad, hess);
+        cubic_check("sample_cubic", Q, cols);
+        const CubicParams P = cubic_begin();
+        query_stream(Q, cols, [&](int64_t m, void* const* d) { launch_cubic<double>(P, m, (const double*)d[0], (double*)d[1], (double*)d[2], (double*)d[3]); }, kCubicQueryChunk);
+        const int64_t a = cubic_end();
+        if (n_answered) *n_answered = a;
+    }
+    void sample_cubic_device(int64_t Q, const void* pts, void* out, void* grad, void* hess, int64_t* n_answered) override {
+        const char* who = "sample_cubic_device";
+        const auto cols = cubic_cols(pts, out, grad, hess);
+        cubic_check(who, Q, cols);
+        HIPCHK(hipSetDevice(cfg.device));
+        check_device_columns(who, "points", Q, cols);
+        const CubicParams P = cubic_begin();
+        launch_cubic<T>(P, Q, (const T*)pts, (T*)out, (T*)grad, (T*)hess);
+        const int64_t a = cubic_end();
+        if (n_answered) *n_answered = a;
     }
 
     // ---- redistancing of the resident phi (shm_redistance.hip.h) ----------------------------------------------------------------------------------------------

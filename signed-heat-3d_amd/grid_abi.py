@@ -22,7 +22,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_apply_kplus_sparse", "shm_grid_apply_schur_grid", "shm_grid_isosurface","shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
-               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_raycast", "shm_grid_raycast_device",
+               "shm_grid_sample", "shm_grid_sample_device", "shm_grid_sample_cubic", "shm_grid_sample_cubic_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
                "shm_grid_closest_point", "shm_grid_closest_point_device", "shm_grid_mesh_raycast", "shm_grid_mesh_raycast_device",
                "shm_grid_field_at_points", "shm_grid_field_at_points_device",
@@ -179,6 +179,9 @@ def load_library():
     lib.shm_grid_get_isosurface.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shm_grid_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shm_grid_sample_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "shm_grid_sample_cubic"):   # added within ABI 5: found by symbol
+        lib.shm_grid_sample_cubic.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        lib.shm_grid_sample_cubic_device.argtypes = lib.shm_grid_sample_cubic.argtypes
     if hasattr(lib, "shm_grid_isosurface_indexed"):   # added within ABI 5: found by symbol
         lib.shm_grid_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         lib.shm_grid_get_isosurface_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -570,6 +573,40 @@ class GridSolver:
         self._chk(self._lib.shm_grid_sample_device(self._h, Q, points.data_ptr() if Q else None, phi.data_ptr() if Q else None,
                                                    g.data_ptr() if grad and Q else None, C.byref(na)))
         return (phi, g, na.value) if grad else (phi, na.value)
+
+    def sample_cubic(self, points, grad=False, hess=False):
+        """The C1 cubic read of the resident phi at points [Q, 3] (shm_grid_sample_cubic: Keys cubic convolution over 4^3 nodes, Keys' boundary rule at
+        the faces): returns (phi [Q][, grad [Q, 3]][, hess [Q, 6]], n_answered), float64; the Hessian as xx, yy, zz, xy, xz, yz.  NaN outside the box."""
+        pts = _f64(points).reshape(-1, 3)
+        Q = pts.shape[0]
+        phi = np.empty(Q, dtype=np.float64)
+        g = np.empty((Q, 3), dtype=np.float64) if grad else None
+        H = np.empty((Q, 6), dtype=np.float64) if hess else None
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_sample_cubic(self._h, Q, pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None,
+                                                  H.ctypes.data if hess else None, C.byref(na)))
+        return tuple([phi] + ([g] if grad else []) + ([H] if hess else []) + [na.value])
+
+    def sample_cubic_device(self, points, grad=False, hess=False):
+        """The same on device memory (shm_grid_sample_cubic_device), with sample_device's conventions: points is a contiguous [Q, 3] torch tensor on this
+        handle's device with its dtype; returns torch tensors (phi [Q][, grad [Q, 3]][, hess [Q, 6]], n_answered) of that dtype on that device.  The
+        vertex buffer of get_isosurface_indexed_device is such a tensor: its gradients are the mesh's vertex normals, unnormalised."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("sample_cubic_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if points.dtype != dt or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise ValueError("sample_cubic_device: points must be a contiguous [Q, 3] %s tensor" % dt)
+        Q = points.shape[0]
+        phi = torch.empty(Q, dtype=dt, device=points.device)
+        g = torch.empty((Q, 3), dtype=dt, device=points.device) if grad else None
+        H = torch.empty((Q, 6), dtype=dt, device=points.device) if hess else None
+        if points.is_cuda:
+            torch.cuda.current_stream(points.device).synchronize()   # the points may still be in flight on torch's stream
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_sample_cubic_device(self._h, Q, points.data_ptr() if Q else None, phi.data_ptr() if Q else None,
+                                                         g.data_ptr() if grad and Q else None, H.data_ptr() if hess and Q else None, C.byref(na)))
+        return tuple([phi] + ([g] if grad else []) + ([H] if hess else []) + [na.value])
 
     def raycast(self, origins, dirs, isovalue=0.0, t_min=0.0, t_max=float("inf"), grad=False):
         """Where each ray origins[q] + t dirs[q] first meets the level set phi = isovalue of the resident phi (shm_grid_raycast): returns (t [Q], n_hits)

@@ -190,6 +190,25 @@ int shmh_sample(void* hv, int64_t Q, const double* pts, double* phi_out, double*
     });
 }
 
+// evaluateFunctionCubic through the C++ class: the C1 cubic read at pts [3Q] -> phi_out [Q], grad_out [3Q] or NULL, hess_out [6Q] or NULL.
+int shmh_sample_cubic(void* hv, int64_t Q, const double* pts, double* phi_out, double* grad_out, double* hess_out) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> q((size_t)Q);
+        for (int64_t a = 0; a < Q; a++) q[(size_t)a] = Vector3{pts[3 * a], pts[3 * a + 1], pts[3 * a + 2]};
+        std::vector<Vector3> g;
+        std::vector<std::array<double, 6>> H;
+        const std::vector<double> phi = h->solver.evaluateFunctionCubic(q, grad_out ? &g : nullptr, hess_out ? &H : nullptr);
+        if (Q > 0) std::memcpy(phi_out, phi.data(), phi.size() * sizeof(double));
+        if (grad_out)
+            for (int64_t a = 0; a < Q; a++)
+                for (int b = 0; b < 3; b++) grad_out[3 * a + b] = g[(size_t)a][b];
+        if (hess_out)
+            for (int64_t a = 0; a < Q; a++)
+                for (int b = 0; b < 6; b++) hess_out[6 * a + b] = H[(size_t)a][b];
+    });
+}
+
 // vectorFieldAt through the C++ class: Y of Steps 1-2 at pts [3Q] over the sources of the last compute_distance -> Y_out [3Q], ratio_out [Q] or NULL, stats or NULL.
 int shmh_vector_field_at(void* hv, int64_t Q, const double* pts, double lambda, int32_t arith, double budget, double* Y_out, double* ratio_out, shm_field_stats* stats) {
     Host* h = (Host*)hv;

@@ -34,6 +34,7 @@ static void usage() {
                  "      --min-triangles <T> With --iso-indexed: drop the components with fewer than T triangles; either flag prints one line per component\n"
                  "      --query <file>    Points to evaluate phi at: raw little-endian float64 xyz triples\n"
                  "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n"
+                 "      --query-cubic     With --query: the C1 cubic read instead; ten values per point: phi, the gradient, the Hessian as xx yy zz xy xz yz\n"
                  "      --rays <file>     Rays to cast against a level set of phi: raw little-endian float64, six values per ray (origin xyz, direction xyz)\n"
                  "      --rays-out <file> Raw float64, four values per ray: t of the first hit in units of the direction (NaN: none), then the gradient there\n"
                  "      --rays-iso <v>    The level the rays are cast against (default 0; independent of --iso)\n"
@@ -65,7 +66,7 @@ int main(int argc, char** argv) {
     long long auditCount = -1, keepLargest = -1, minTriangles = -1;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
-    bool verbose = false, isoIndexed = false;
+    bool verbose = false, isoIndexed = false, queryCubic = false;
     for (int a = 1; a < argc; a++) {
         const std::string s = argv[a];
         auto need = [&](const char* what) -> const char* {
@@ -95,6 +96,7 @@ int main(int argc, char** argv) {
         else if (s == "--min-triangles") minTriangles = atoll(need("--min-triangles"));
         else if (s == "--query") queryPath = need("--query");
         else if (s == "--query-out") queryOut = need("--query-out");
+        else if (s == "--query-cubic") queryCubic = true;
         else if (s == "--rays") raysPath = need("--rays");
         else if (s == "--rays-out") raysOut = need("--rays-out");
         else if (s == "--rays-iso") raysIso = atof(need("--rays-iso"));
@@ -118,6 +120,10 @@ int main(int argc, char** argv) {
     }
     if (queryPath.empty() != queryOut.empty()) {
         std::cerr << "--query and --query-out go together." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (queryCubic && queryPath.empty()) {
+        std::cerr << "--query-cubic needs --query and --query-out." << std::endl;
         return EXIT_FAILURE;
     }
     if (raysPath.empty() != raysOut.empty()) {
@@ -303,15 +309,28 @@ int main(int argc, char** argv) {
             std::vector<Vector3> q(raw.size() / 3);
             for (size_t a = 0; a < q.size(); a++) q[a] = Vector3{raw[3 * a], raw[3 * a + 1], raw[3 * a + 2]};
             std::vector<Vector3> g;
-            const std::vector<double> v = solver.evaluateFunction(q, &g);
-            std::vector<double> res(4 * q.size());
-            for (size_t a = 0; a < q.size(); a++) {
-                res[4 * a] = v[a];
-                for (int b = 0; b < 3; b++) res[4 * a + 1 + b] = g[a][b];
+            std::vector<double> res;
+            if (queryCubic) {
+                std::vector<std::array<double, 6>> H;
+                const std::vector<double> v = solver.evaluateFunctionCubic(q, &g, &H);
+                res.resize(10 * q.size());
+                for (size_t a = 0; a < q.size(); a++) {
+                    res[10 * a] = v[a];
+                    for (int b = 0; b < 3; b++) res[10 * a + 1 + b] = g[a][b];
+                    for (int b = 0; b < 6; b++) res[10 * a + 4 + b] = H[a][b];
+                }
+            } else {
+                const std::vector<double> v = solver.evaluateFunction(q, &g);
+                res.resize(4 * q.size());
+                for (size_t a = 0; a < q.size(); a++) {
+                    res[4 * a] = v[a];
+                    for (int b = 0; b < 3; b++) res[4 * a + 1 + b] = g[a][b];
+                }
             }
             std::ofstream o(queryOut, std::ios::binary);
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
-            std::cerr << "phi and its gradient at " << q.size() << " points written to " << queryOut << std::endl;
+            std::cerr << (queryCubic ? "phi, its gradient and its Hessian (C1 cubic) at " : "phi and its gradient at ") << q.size() << " points written to " << queryOut
+                      << std::endl;
         }
         if (!fieldPath.empty()) {
             std::ifstream f(fieldPath, std::ios::binary | std::ios::ate);

@@ -194,6 +194,27 @@ std::vector<double> SignedHeatGridSolver::evaluateFunction(const std::vector<Vec
     return phi;
 }
 
+std::vector<double> SignedHeatGridSolver::evaluateFunctionCubic(const std::vector<Vector3>& q, std::vector<Vector3>* gradients,
+                                                                 std::vector<std::array<double, 6>>* hessians) {
+    if (!handle) throw std::runtime_error("evaluateFunctionCubic: computeDistance has not been called");
+    std::vector<double> pts(3 * q.size()), phi(q.size()), g(gradients ? 3 * q.size() : 0), H(hessians ? 6 * q.size() : 0);
+    for (size_t a = 0; a < q.size(); a++)
+        for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+    int64_t answered = 0;
+    if (shm_grid_sample_cubic(handle, (int64_t)q.size(), pts.data(), phi.data(), gradients ? g.data() : nullptr, hessians ? H.data() : nullptr, &answered) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_sample_cubic: ") + shm_grid_last_error(handle));
+    if (gradients) {
+        gradients->resize(q.size());
+        for (size_t a = 0; a < q.size(); a++) (*gradients)[a] = Vector3{g[3 * a], g[3 * a + 1], g[3 * a + 2]};
+    }
+    if (hessians) {
+        hessians->resize(q.size());
+        for (size_t a = 0; a < q.size(); a++)
+            for (int b = 0; b < 6; b++) (*hessians)[a][b] = H[6 * a + b];
+    }
+    return phi;
+}
+
 std::vector<Vector3> SignedHeatGridSolver::vectorFieldAt(const std::vector<Vector3>& q, double lam, std::vector<double>* ratio, shm_field_stats* st, int arith,
                                                          double budget) {
     if (!handle) throw std::runtime_error("vectorFieldAt: computeDistance has not been called");

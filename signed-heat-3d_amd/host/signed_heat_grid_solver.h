@@ -4,6 +4,7 @@
 // has no counterpart: the Laplacian is matrix-free on the device and the dead Cholesky factorisation
 // (signed_heat_grid_solver.cpp:30, never solved with) is not reproduced.
 #pragma once
+#include <array>
 #include <memory>
 #include <limits>
 #include <vector>
@@ -57,6 +58,12 @@ class SignedHeatGridSolver {
     // the LAST computeDistance() call at every point of q, evaluated on the device (shm_grid_sample; box, NaN and gradient rules in include/shm_grid.h).
     // With gradients != nullptr it is resized to q.size() and receives the gradient of the trilinear interpolant in each point's cell.
     std::vector<double> evaluateFunction(const std::vector<Vector3>& q, std::vector<Vector3>* gradients = nullptr);
+
+    // The smooth read beside evaluateFunction: the C1 cubic (Keys cubic convolution over 4 x 4 x 4 nodes, Keys' boundary rule at the faces) of the same phi
+    // at every point of q, evaluated on the device (shm_grid_sample_cubic; rules in include/shm_grid.h).  It interpolates the nodes and smooths nothing.
+    // gradients and hessians are optional independently; each is resized to q.size().  Hessian layout: xx, yy, zz, xy, xz, yz.
+    std::vector<double> evaluateFunctionCubic(const std::vector<Vector3>& q, std::vector<Vector3>* gradients = nullptr,
+                                              std::vector<std::array<double, 6>>* hessians = nullptr);
 
     // Where does each ray origins[q] + t dirs[q] first meet the level set phi = isoval of the LAST computeDistance() call?  Cast on the device against the
     // trilinear interpolant evaluateFunction evaluates (shm_grid_raycast; rules in include/shm_grid.h): t per ray in units of dirs[q] (not normalised), NaN

@@ -41,6 +41,7 @@ def load_host_library():
                                     C.POINTER(C.c_int64)]
     lib.shmh_compute_distance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.POINTER(ShmStats)]
     lib.shmh_sample.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.shmh_sample_cubic.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.shmh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     lib.shmh_redistance.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.POINTER(ShmRedistanceStats)]
     if hasattr(lib, "shmh_vector_field_at"):
@@ -139,6 +140,18 @@ class HostSolver:
         g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
         self._chk(self._lib.shmh_sample(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None))
         return (phi, g) if grad else phi
+
+    def sample_cubic(self, points, grad=False, hess=False):
+        """evaluateFunctionCubic of the C++ mirror at points [Q, 3]: the C1 cubic read of the phi of the last compute_distance (shm_grid_sample_cubic).
+        Returns phi [Q] or a tuple (phi[, grad [Q, 3]][, hess [Q, 6]]), float64; NaN outside the box."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        phi = np.empty(pts.shape[0], dtype=np.float64)
+        g = np.empty((pts.shape[0], 3), dtype=np.float64) if grad else None
+        H = np.empty((pts.shape[0], 6), dtype=np.float64) if hess else None
+        self._chk(self._lib.shmh_sample_cubic(self._h, pts.shape[0], pts.ctypes.data, phi.ctypes.data, g.ctypes.data if grad else None,
+                                              H.ctypes.data if hess else None))
+        res = [phi] + ([g] if grad else []) + ([H] if hess else [])
+        return res[0] if len(res) == 1 else tuple(res)
 
     def vector_field_at(self, points, lam=0.0, arith="auto", budget=0.0, ratio=False, stats=False):
         """vectorFieldAt of the C++ mirror at points [Q, 3]: Y of Steps 1-2 over the sources of the last compute_distance (shm_grid_field_at_points).
