@@ -234,6 +234,32 @@ shm_status shm_grid_get_field_planes(shm_solver* s, shm_field f, int32_t k_begin
 /* out = L*u with the reference's Laplacian (signed_heat_grid_solver.cpp:278-334); u,out: n^3 doubles
  * on the host (world==1). */
 shm_status shm_grid_apply_laplacian(shm_solver* s, const double* u, double* out);
+/* One step of the fused stencil CG (csrc/shm_cg_fused.hip.h) by the launches of the solve's own loop.  Test entry points, added within ABI 5 (no struct
+ * changed, SHM_GRID_ABI_VERSION stays 5; detect them by their symbols), world==1, any local_slabs, handles of both precisions.  Every vector holds n^3 doubles
+ * on the host in shm_grid_get_phi's node order and is rounded once to the handle's precision on the way in.  They need shm_grid_set_problem only -- no Step 1
+ * and no constraints.  SHM_ERR_STATE before it; SHM_ERR_INVALID for NULL, world != 1, and a grid the fused sweeps do not serve (a row of more than 512 lanes of
+ * 1, 2 (fp64) or 4 (fp32) nodes, or SHM_CG_CLASSIC set).  Both overwrite the residual, the iterate and both direction buffers, one of which holds phi: afterwards
+ * there is no phi, no divergence and nothing derived from phi (their getters return SHM_ERR_STATE), as after shm_grid_apply_laplacian; Y and the constraint
+ * set-up stay, and a later solve is not affected.
+ *   shm_grid_cg_sweeps: the DIR sweep of iteration `it` (only its parity matters: p is stored in direction buffer it & 1, rho_old in the rho slot of that parity)
+ *     followed by the RES sweep of iteration it + 1, with K = -L of shm_grid_apply_laplacian:
+ *       rho_new = red0 - (use_uw ? uw : 0);  beta = (init || rho_old == 0) ? 0 : rho_new / rho_old;  p' = -z + beta p  (init: p' = -z, p is not read);
+ *       alpha = rho_new == 0 ? 0 : rho_new / (p'.K p');  r' = r + alpha K p'.
+ *     z is stored where the preconditioned loop keeps it, so z and r are independent.  The ghost planes of p between slabs are filled as the previous DIR sweep
+ *     leaves them; those of z are filled by the loop's halo exchange, beside the interior z chunks where every slab has three or more chunks.  With init the
+ *     launches are the loop's first (DIR into buffer 0, RES of iteration 0) whatever `it`.
+ *     p_out, r_out: p' and r'.  out_sc[3]: rho_new as the DIR sweep stored it, alpha as the RES sweep stored it, ||r'||^2 summed over the sweep's block partials
+ *     and over the slabs in the order the loop's projection sums them.  p'.K p' is not returned: on one slab the RES sweep sums its partials itself and it is
+ *     never stored; alpha carries it.  out_shape[8]: the kernel instance and grid of the first slab -- nodes per lane, rows per lane RY, waves along x WX and
+ *     along y WY of a workgroup, planes per z chunk, z chunks, workgroups along y -- and 1 if the halo exchange ran beside the interior chunks.
+ *   shm_grid_cg_x_update: x' = x + (use_a ? alpha_a p_a : 0) + (use_b ? alpha_b p_b : 0), p_a / p_b in the direction buffers of even / odd iterations (a
+ *     switched-off direction is not read).  half -1: every node; 0 / 1: the lower / upper half of the nodes in node order, split at floor(N / vec / 2) * vec
+ *     with vec the nodes per lane, the other half is returned unchanged -- one slab only (SHM_ERR_INVALID on several, as for any other value of half). */
+shm_status shm_grid_cg_sweeps(shm_solver* s, const double* z, const double* p, const double* r, double rho_old, double red0, double uw, int32_t use_uw,
+                              int32_t init, int32_t it, double* p_out /* [n^3] */, double* r_out /* [n^3] */, double* out_sc /* [3] */,
+                              int32_t* out_shape /* [8] */);
+shm_status shm_grid_cg_x_update(shm_solver* s, const double* x, const double* p_a, const double* p_b, double alpha_a, double alpha_b, int32_t use_a,
+                                int32_t use_b, int32_t half, double* x_out /* [n^3] */);
 /* Make the caller's field the resident phi: phi holds n^3 doubles on the host in shm_grid_get_phi's node order (world==1), each rounded once to the handle's
  * precision on the way in, so shm_grid_get_phi returns exactly those rounded values.  Test and tooling entry point, added within ABI 5 (no struct changed,
  * SHM_GRID_ABI_VERSION stays 5; detect it by its symbol): the tests feed every reader of phi fields no solve produces (tests/test_injected_phi.py), and a caller

@@ -176,6 +176,20 @@ shm_status shm_grid_apply_laplacian(shm_solver* s, const double* u, double* out)
         s->impl->apply_laplacian(u, out);
     });
 }
+shm_status shm_grid_cg_sweeps(shm_solver* s, const double* z, const double* p, const double* r, double rho_old, double red0, double uw, int32_t use_uw,
+                              int32_t init, int32_t it, double* p_out, double* r_out, double* out_sc, int32_t* out_shape) {
+    return guard(s, [&] {
+        if (!z || !p || !r || !p_out || !r_out || !out_sc || !out_shape) throw shm::Error(SHM_ERR_INVALID, "null argument");
+        s->impl->cg_sweeps(z, p, r, rho_old, red0, uw, use_uw, init, it, p_out, r_out, out_sc, out_shape);
+    });
+}
+shm_status shm_grid_cg_x_update(shm_solver* s, const double* x, const double* p_a, const double* p_b, double alpha_a, double alpha_b, int32_t use_a,
+                                int32_t use_b, int32_t half, double* x_out) {
+    return guard(s, [&] {
+        if (!x || !p_a || !p_b || !x_out) throw shm::Error(SHM_ERR_INVALID, "null argument");
+        s->impl->cg_x_update(x, p_a, p_b, alpha_a, alpha_b, use_a, use_b, half, x_out);
+    });
+}
 shm_status shm_grid_set_phi(shm_solver* s, const double* phi) {
     return guard(s, [&] {
         if (!phi) throw shm::Error(SHM_ERR_INVALID, "null argument");

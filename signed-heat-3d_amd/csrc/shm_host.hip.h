@@ -553,6 +553,8 @@ struct SolverBase {
     virtual void get_field(shm_field, double*) = 0;
     virtual void get_field_planes(shm_field, int, int, double*) = 0;
     virtual void apply_laplacian(const double*, double*) = 0;
+    virtual void cg_sweeps(const double*, const double*, const double*, double, double, double, int32_t, int32_t, int32_t, double*, double*, double*, int32_t*) = 0;
+    virtual void cg_x_update(const double*, const double*, const double*, double, double, int32_t, int32_t, int32_t, double*) = 0;
     virtual void set_phi(const double*) = 0;
     virtual void get_constraints(int64_t*, double*, int32_t*) = 0;
     virtual void apply_projector(double*) = 0;

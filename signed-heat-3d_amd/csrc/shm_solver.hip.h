@@ -2581,18 +2581,20 @@ struct Solver final : SolverBase {
     }
 
     // ------------------------------------------------------------------------------------------
-    // Projected (preconditioned) CG with the fused sweeps of shm_cg_fused.hip.h -- same recurrence as the classic loop in solve():
-    //      x=0; r=P b; z=P M^-1 r; p0=-z;
-    //      loop k { a_k = rho_k / (p_k . K p_k);  r = P(r + a_k K p_k);  z = P M^-1 r;  rho_{k+1} = r.z;  p_{k+1} = -z + (rho_{k+1}/rho_k) p_k }
-    //      x = sum_k a_k p_k, accumulated two directions at a time (p_k lives in buffer k & 1: sl.p / sl.q)
-    // N-sized launches per iteration: RES (r += a K p, ||r||^2), DIR (p' = -z + b p, p'.K p'), and x_update2 on odd k: 8 N T bytes.
-    void solve_primal_fused(const shm_opts& o, shm_stats* st, bool pre, SolveClock& clk) {
-        std::vector<int> nparts(slabs.size()), zparts(slabs.size(), 0), kparts(slabs.size(), 0);
+    // The DIR sweep of the fused loop and the sum behind it, shared by solve_primal_fused and the test entry point cg_sweeps (p_k lives in buffer k & 1: sl.p / sl.q)
+    struct FusedSweeps {
+        int zsel = ARR_R, use_uw = 1;   // z = r with rho = red[0] - u.w (plain), or z = P M^-1 r with rho = red[0] (preconditioned)
+        bool overlap = false;           // the halo exchange of z runs beside the interior z chunks
+        std::vector<int> kparts;        // block partials of p'.Kp' per slab
+        Event e_ready, e_halo;
+    };
+    static T* dirbuf(Slab<T>& sl, int k) { return (k & 1) ? sl.q.p : sl.p.p; }
+    void begin_fused_sweeps(FusedSweeps& fs, int zsel, int use_uw) {
+        fs.zsel = zsel;
+        fs.use_uw = use_uw;
+        fs.kparts.assign(slabs.size(), 0);
         fold_pq = total_slabs == 1 && !comm;   // (otherwise finalize_sum_kernel after every DIR sweep, as until round 4)
         fold_pq_np = 0;
-        auto dirbuf = [&](Slab<T>& sl, int k) { return (k & 1) ? sl.q.p : sl.p.p; };
-        const int zsel = pre ? ARR_Z : ARR_R;
-        primal_prologue(pre, nparts, zparts);
         // Several slabs: the ghost planes of z travel on a second stream while the z chunks that do not touch them are swept (the first and the
         // last chunk of every slab follow once the planes have arrived).  One host thread issues everything in the same order on every rank; RCCL
         // orders the operations of one communicator across streams itself.  Otherwise: exchange first, then one sweep.
@@ -2600,42 +2602,61 @@ struct Solver final : SolverBase {
         // serialising the send/recv of stream_h against the all-reduces the same communicator issues on `stream`, which only the librccl double and the
         // loop-back transport (several slabs in one process: device copies) have exercised so far.  Read per solve: the tests flip it inside one process.
         const bool halo_serial = comm != nullptr && knob("SHM_HALO_OVERLAP") == nullptr;
-        bool overlap = total_slabs > 1 && !halo_serial;
-        for (Slab<T>& sl : slabs) overlap = overlap && fused_cfg(sl).zchunks >= 3;
-        if (overlap && !stream_h) HIPCHK(hipStreamCreateWithFlags(&stream_h, hipStreamNonBlocking));
-        Event e_ready, e_halo;
-        auto run_dir = [&](int k, int slot_old, int slot_new, int init) {  // p_{k+1} (init: p_0) from z and p_k; leaves p'.Kp' in pq
-            auto sweep = [&](int part) {
-                for (size_t s = 0; s < slabs.size(); s++) {
-                    Slab<T>& sl = slabs[s];
-                    const int out = init ? 0 : k + 1;
-                    kparts[s] = launch_fused<CGF_DIR>(sl, slot_old, slot_new, init, pre ? 0 : 1, 0, arr(sl, zsel), dirbuf(sl, k), dirbuf(sl, out), part);
-                }
-            };
-            if (!overlap) {
-                if (total_slabs > 1) halo_exchange(zsel);
-                sweep(FUSED_ALL);
-                return;
+        fs.overlap = total_slabs > 1 && !halo_serial;
+        for (Slab<T>& sl : slabs) fs.overlap = fs.overlap && fused_cfg(sl).zchunks >= 3;
+        if (fs.overlap && !stream_h) HIPCHK(hipStreamCreateWithFlags(&stream_h, hipStreamNonBlocking));
+    }
+    void run_dir(FusedSweeps& fs, int k, int slot_old, int slot_new, int init) {  // p_{k+1} (init: p_0) from z and p_k; leaves p'.Kp' in pq
+        auto sweep = [&](int part) {
+            for (size_t s = 0; s < slabs.size(); s++) {
+                Slab<T>& sl = slabs[s];
+                const int out = init ? 0 : k + 1;
+                fs.kparts[s] = launch_fused<CGF_DIR>(sl, slot_old, slot_new, init, fs.use_uw, 0, arr(sl, fs.zsel), dirbuf(sl, k), dirbuf(sl, out), part);
             }
-            e_ready.record(stream);                                   // z is final (projection done)
-            HIPCHK(hipStreamWaitEvent(stream_h, e_ready.e, 0));
-            sweep(FUSED_INTERIOR);
-            halo_exchange(zsel, stream_h);
-            e_halo.record(stream_h);
-            HIPCHK(hipStreamWaitEvent(stream, e_halo.e, 0));
-            sweep(FUSED_BOUNDARY);
         };
-        auto finalize_pq = [&]() {
-            if (fold_pq) {   // the RES sweep sums the partials itself (cg_fused_kernel)
-                fold_pq_np = kparts[0];
-                return;
-            }
-            for (size_t s = 0; s < slabs.size(); s++)
-                hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, stream, slabs[s].partials.p, kparts[s], slabs[s].pq.p);
-            allreduce(1, 1);
-        };
-        run_dir(0, SC_RHO_A, SC_RHO_A, 1);
-        finalize_pq();
+        if (!fs.overlap) {
+            if (total_slabs > 1) halo_exchange(fs.zsel);
+            sweep(FUSED_ALL);
+            return;
+        }
+        fs.e_ready.record(stream);                                   // z is final (projection done)
+        HIPCHK(hipStreamWaitEvent(stream_h, fs.e_ready.e, 0));
+        sweep(FUSED_INTERIOR);
+        halo_exchange(fs.zsel, stream_h);
+        fs.e_halo.record(stream_h);
+        HIPCHK(hipStreamWaitEvent(stream, fs.e_halo.e, 0));
+        sweep(FUSED_BOUNDARY);
+    }
+    void finalize_pq(FusedSweeps& fs) {
+        if (fold_pq) {   // the RES sweep sums the partials itself (cg_fused_kernel)
+            fold_pq_np = fs.kparts[0];
+            return;
+        }
+        for (size_t s = 0; s < slabs.size(); s++)
+            hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, stream, slabs[s].partials.p, fs.kparts[s], slabs[s].pq.p);
+        allreduce(1, 1);
+    }
+    // RES sweep of iteration `it` on every slab (r += a_it K p_it); nparts[s]: the block partials of ||r||^2 slab s leaves in its `partials`
+    void run_res(int it, std::vector<int>& nparts) {
+        const int slot_old = (it & 1) ? SC_RHO_B : SC_RHO_A, slot_new = (it & 1) ? SC_RHO_A : SC_RHO_B;
+        for (size_t s = 0; s < slabs.size(); s++)
+            nparts[s] = launch_fused<CGF_RES>(slabs[s], slot_old, slot_new, 0, 0, (it & 1) ? SC_ALPHA_B : SC_ALPHA_A, (const T*)nullptr, dirbuf(slabs[s], it),
+                                              (T*)nullptr);
+    }
+
+    // ------------------------------------------------------------------------------------------
+    // Projected (preconditioned) CG with the fused sweeps of shm_cg_fused.hip.h -- same recurrence as the classic loop in solve():
+    //      x=0; r=P b; z=P M^-1 r; p0=-z;
+    //      loop k { a_k = rho_k / (p_k . K p_k);  r = P(r + a_k K p_k);  z = P M^-1 r;  rho_{k+1} = r.z;  p_{k+1} = -z + (rho_{k+1}/rho_k) p_k }
+    //      x = sum_k a_k p_k, accumulated two directions at a time (p_k lives in buffer k & 1: sl.p / sl.q)
+    // N-sized launches per iteration: RES (r += a K p, ||r||^2), DIR (p' = -z + b p, p'.K p'), and x_update2 on odd k: 8 N T bytes.
+    void solve_primal_fused(const shm_opts& o, shm_stats* st, bool pre, SolveClock& clk) {
+        std::vector<int> nparts(slabs.size()), zparts(slabs.size(), 0);
+        primal_prologue(pre, nparts, zparts);
+        FusedSweeps fs;
+        begin_fused_sweeps(fs, pre ? ARR_Z : ARR_R, pre ? 0 : 1);
+        run_dir(fs, 0, SC_RHO_A, SC_RHO_A, 1);
+        finalize_pq(fs);
         HIPCHK(hipGetLastError());
 
         // Per-kernel durations are sampled on a few iterations only: a sampled iteration keeps everything on one stream (no projection beside the x update) and records
@@ -2667,9 +2688,7 @@ struct Solver final : SolverBase {
                 const bool sample = tm.begin(it % sample_stride == 1);
                 auto mark = [&](int k) { tm.mark(k, stream); };
                 mark(0);
-                for (size_t s = 0; s < slabs.size(); s++)
-                    nparts[s] = launch_fused<CGF_RES>(slabs[s], slot_old, slot_new, 0, 0, (it & 1) ? SC_ALPHA_B : SC_ALPHA_A, (const T*)nullptr,
-                                                      dirbuf(slabs[s], it), (T*)nullptr);
+                run_res(it, nparts);
                 mark(1);
                 // x += a_{k-1} p_{k-1} + a_k p_k (odd k) needs nothing of the projection, and the projection's kernels are m-sized and latency-bound: on one GPU the
                 // two run side by side (fork after RES, which fixes a_k; join before DIR, which needs the projected residual and overwrites p_{k-1}).  Sampled
@@ -2696,9 +2715,9 @@ struct Solver final : SolverBase {
                 else if (!fork_x && (it & 1))
                     for (Slab<T>& sl : slabs) launch_x_update2(sl, 1, 1);
                 mark(5);
-                run_dir(it, slot_old, slot_new, 0);
+                run_dir(fs, it, slot_old, slot_new, 0);
                 mark(6);
-                finalize_pq();
+                finalize_pq(fs);
                 mark(7);
                 tm.end();
             }
@@ -2968,15 +2987,16 @@ struct Solver final : SolverBase {
         copy_planes_to_host((int)f, ka, kb, out);
     }
 
-    void upload_owned(const double* in, int which) {
-        // host N-vector -> slab array `which` (0: p with ghosts filled from the host copy, 1: r, 2: q), each value rounded once to T
+    void upload_owned(const double* in, int which, bool ghosts = true) {
+        // host N-vector -> slab array `which` (0: p with ghosts filled from the host copy, 1: r, 2: q, 3: z, 4: x), each value rounded once to T.
+        // ghosts = false: the ghost planes hold NaN instead, so that a reader shows whether the halo exchange it relies on has run
         std::vector<T> tmp;
         for (Slab<T>& sl : slabs) {
-            tmp.assign(sl.ntot, (T)0);
-            const int klo = std::max(0, sl.k0 - 1), khi = std::min(n, sl.k1 + 1);
+            tmp.assign(sl.ntot, ghosts ? (T)0 : std::numeric_limits<T>::quiet_NaN());
+            const int klo = ghosts ? std::max(0, sl.k0 - 1) : sl.k0, khi = ghosts ? std::min(n, sl.k1 + 1) : sl.k1;
             for (int k = klo; k < khi; k++)
                 for (size_t a = 0; a < sl.plane; a++) tmp[(size_t)(k - sl.k0 + 1) * sl.plane + a] = (T)in[(size_t)k * sl.plane + a];
-            T* dst = which == 0 ? sl.p.p : which == 1 ? sl.r.p : sl.q.p;
+            T* dst = which == 0 ? sl.p.p : which == 1 ? sl.r.p : which == 2 ? sl.q.p : which == 3 ? sl.z.p : sl.x.p;
             HIPCHK(hipMemcpyAsync(dst, tmp.data(), sl.ntot * sizeof(T), hipMemcpyHostToDevice, stream));
             HIPCHK(hipStreamSynchronize(stream));
         }
@@ -2993,6 +3013,108 @@ struct Solver final : SolverBase {
         copy_owned_to_host(SHM_FIELD_PHI, out);
         have_phi = false;  // q now holds L u, not phi
         drop_phi_derived();
+    }
+
+    // owned planes of a solver array (ARR_*) -> host doubles
+    void copy_arr_to_host(int sel, double* out) {
+        size_t off = 0;
+        for (Slab<T>& sl : slabs) {
+            const T* srcp = arr(sl, sel) + sl.plane;
+            if (sizeof(T) == 8) {
+                HIPCHK(hipMemcpyAsync(out + off, srcp, sl.nown * sizeof(double), hipMemcpyDeviceToHost, stream));
+            } else {
+                DevArray<double> tmp;
+                tmp.alloc(sl.nown);
+                hipLaunchKernelGGL((convert_kernel<T, double>), dim3(grid_for(sl.nown, 4096)), dim3(kBlock), 0, stream, sl.nown, srcp, tmp.p);
+                HIPCHK(hipMemcpyAsync(out + off, tmp.p, sl.nown * sizeof(double), hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+            }
+            off += sl.nown;
+        }
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    void set_scalar(double* dst, double v) {   // (synchronous: v is a stack value)
+        HIPCHK(hipMemcpyAsync(dst, &v, sizeof(double), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    // r, z, x and both direction buffers are about to hold the caller's vectors: no phi (q), no divergence (r), nothing derived from phi; Y and the constraints stay
+    void begin_cg_entry(const char* name) {
+        need_problem();
+        if (cfg.world != 1) throw Error(SHM_ERR_INVALID, fmt("%s is a single-process test entry point", name));
+        if (!fused_available()) throw Error(SHM_ERR_INVALID, fmt("%s: the fused sweeps do not serve this grid (a row of more than 512 lanes, or SHM_CG_CLASSIC)", name));
+        HIPCHK(hipSetDevice(cfg.device));
+        have_phi = have_div = false;
+        drop_phi_derived();
+    }
+
+    // Test entry point: the DIR sweep of iteration `it` and the RES sweep of iteration `it + 1` of solve_primal_fused, by its own launches (run_dir, finalize_pq,
+    // run_res), on the caller's z, p_it and r.  init: the loop's first DIR sweep (p' = -z into buffer 0, both rho slots SC_RHO_A) and the RES sweep of iteration 0.
+    void cg_sweeps(const double* z, const double* p, const double* r, double rho_old, double red0, double uw, int32_t use_uw, int32_t init, int32_t it, double* p_out,
+                   double* r_out, double* out_sc, int32_t* out_shape) override {
+        begin_cg_entry("cg_sweeps");
+        const int k = init ? 0 : (it & 1);
+        const int slot_old = k ? SC_RHO_B : SC_RHO_A, slot_new = init ? SC_RHO_A : (k ? SC_RHO_A : SC_RHO_B);
+        const int kres = init ? 0 : k + 1;   // the iteration whose RES sweep follows: it reads rho from slot_new and p' from buffer kres & 1
+        bool new_red = false;
+        for (Slab<T>& sl : slabs) {
+            if (!sl.z.p) {
+                sl.z.alloc(sl.ntot);
+                HIPCHK(hipMemsetAsync(sl.z.p, 0, sl.ntot * sizeof(T), stream));
+            }
+            if (!sl.red.p) {
+                sl.red.alloc(1);
+                new_red = true;
+            }
+        }
+        if (new_red || !d_redptrs.p) upload_red_tables(stream);
+        upload_owned(z, 3, false);           // the ghost planes of z are the halo exchange's to fill
+        upload_owned(r, 1, false);
+        upload_owned(p, k ? 2 : 0);          // ... those of p the previous DIR sweep's: here from the host copy
+        for (Slab<T>& sl : slabs) {
+            set_scalar(sl.sc.p + slot_old, rho_old);
+            set_scalar(sl.sc.p + SC_UW, uw);
+            set_scalar(sl.red.p, red0);
+        }
+        FusedSweeps fs;
+        begin_fused_sweeps(fs, ARR_Z, use_uw ? 1 : 0);
+        run_dir(fs, k, slot_old, slot_new, init ? 1 : 0);
+        finalize_pq(fs);
+        std::vector<int> nparts(slabs.size(), 0);
+        run_res(kres, nparts);
+        // ||r'||^2 as the loop's next consumer forms it: block 0 of gather_rows_kernel sums the block partials as finalize_sum_kernel does, the slabs follow in allreduce
+        for (size_t s = 0; s < slabs.size(); s++)
+            hipLaunchKernelGGL(finalize_sum_kernel, dim3(1), dim3(kBlock), 0, stream, slabs[s].partials.p, nparts[s], slabs[s].red.p);
+        allreduce(0, 1);
+        HIPCHK(hipGetLastError());
+        copy_arr_to_host((kres & 1) ? ARR_Q : ARR_P, p_out);
+        copy_arr_to_host(ARR_R, r_out);
+        double sc[SC_COUNT];
+        HIPCHK(hipMemcpyAsync(sc, slabs[0].sc.p, SC_COUNT * sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(out_sc + 2, slabs[0].red.p, sizeof(double), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        out_sc[0] = sc[slot_new];
+        out_sc[1] = sc[(kres & 1) ? SC_ALPHA_B : SC_ALPHA_A];
+        const FusedCfg c = fused_cfg(slabs[0]);
+        const int shape[8] = {vec, c.ry, c.wx, c.nw / c.wx, c.zc, c.zchunks, c.yblocks, fs.overlap ? 1 : 0};
+        for (int a = 0; a < 8; a++) out_shape[a] = shape[a];
+    }
+
+    // Test entry point: x += alpha_a p_a + alpha_b p_b by launch_x_update2 (p_a / p_b: the direction buffers of even / odd iterations)
+    void cg_x_update(const double* x, const double* pa, const double* pb, double alpha_a, double alpha_b, int32_t use_a, int32_t use_b, int32_t half,
+                     double* x_out) override {
+        begin_cg_entry("cg_x_update");
+        if (half < -1 || half > 1) throw Error(SHM_ERR_INVALID, "cg_x_update: half is -1 (all), 0 (lower) or 1 (upper)");
+        if (half >= 0 && total_slabs > 1) throw Error(SHM_ERR_INVALID, "cg_x_update: the loop updates half a grid on one slab only");
+        upload_owned(x, 4);
+        upload_owned(pa, 0);
+        upload_owned(pb, 2);
+        for (Slab<T>& sl : slabs) {
+            set_scalar(sl.sc.p + SC_ALPHA_A, alpha_a);
+            set_scalar(sl.sc.p + SC_ALPHA_B, alpha_b);
+            launch_x_update2(sl, use_a ? 1 : 0, use_b ? 1 : 0, nullptr, half);
+        }
+        HIPCHK(hipGetLastError());
+        copy_arr_to_host(ARR_X, x_out);
     }
 
     // Test and tooling entry point: the caller's field becomes the resident phi (q of every slab), as if a solve had produced it.  Y, the divergence, the

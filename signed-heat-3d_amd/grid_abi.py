@@ -19,7 +19,7 @@ STATUS_NAMES = {0: "SHM_OK", 1: "SHM_ERR_INVALID", 2: "SHM_ERR_HIP", 3: "SHM_ERR
 # every symbol include/shm_grid.h declares (tests check the library exports all of them)
 ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "shm_grid_last_error", "shm_grid_abi_version", "shm_grid_set_problem",
                "shm_grid_solve", "shm_grid_get_phi", "shm_grid_compute_distance", "shm_grid_run_conv", "shm_grid_run_conv_arith", "shm_grid_run_divergence",
-               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_apply_kplus_sparse", "shm_grid_apply_schur_grid", "shm_grid_isosurface","shm_grid_isosurface_ex", "shm_grid_get_isosurface",
+               "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_cg_sweeps", "shm_grid_cg_x_update", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_apply_kplus_sparse", "shm_grid_apply_schur_grid", "shm_grid_isosurface","shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_sample_cubic", "shm_grid_sample_cubic_device", "shm_grid_raycast", "shm_grid_raycast_device",
@@ -164,6 +164,10 @@ def load_library():
     lib.shm_grid_get_field.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     lib.shm_grid_get_field_planes.argtypes = [C.c_void_p, C.c_int, C.c_int32, C.c_int32, C.c_void_p]
     lib.shm_grid_apply_laplacian.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(lib, "shm_grid_cg_sweeps"):   # added within ABI 5: found by symbol
+        lib.shm_grid_cg_sweeps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.shm_grid_cg_x_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     lib.shm_grid_set_phi.argtypes = [C.c_void_p, C.c_void_p]
     lib.shm_grid_get_constraints.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
     lib.shm_grid_get_schur.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
@@ -378,6 +382,37 @@ class GridSolver:
         u = _f64(u).reshape(-1)
         out = np.empty_like(u)
         self._chk(self._lib.shm_grid_apply_laplacian(self._h, u.ctypes.data, out.ctypes.data))
+        return out
+
+    CG_SHAPE = ("vec", "ry", "wx", "wy", "zc", "zchunks", "yblocks", "overlap")
+
+    def _n3(self, name, *vs):
+        out = []
+        for v in vs:
+            v = _f64(v).reshape(-1)
+            if self.n and v.size != self.n ** 3:
+                raise ValueError("%s: every vector must hold n^3 = %d values, got %d" % (name, self.n ** 3, v.size))
+            out.append(v)
+        return out
+
+    def cg_sweeps(self, z, p, r, rho_old, red0, uw=0.0, use_uw=False, init=False, it=0):
+        """One step of the fused stencil CG by the loop's own launches (shm_grid_cg_sweeps): the DIR sweep of iteration `it` (p' = -z + beta p, p'.Kp') and the RES
+        sweep of iteration it + 1 (r' = r + alpha K p', ||r'||^2) on z, p, r [n^3].  Returns (p', r', (rho_new, alpha, ||r'||^2), shape) with shape a dict of
+        CG_SHAPE: the kernel instance and grid the device chose.  Afterwards the handle holds no phi and no divergence.  Test entry point."""
+        z, p, r = self._n3("cg_sweeps", z, p, r)
+        p_out, r_out = np.empty_like(z), np.empty_like(z)
+        sc, shape = np.zeros(3, dtype=np.float64), np.zeros(8, dtype=np.int32)
+        self._chk(self._lib.shm_grid_cg_sweeps(self._h, z.ctypes.data, p.ctypes.data, r.ctypes.data, float(rho_old), float(red0), float(uw), int(bool(use_uw)),
+                                               int(bool(init)), int(it), p_out.ctypes.data, r_out.ctypes.data, sc.ctypes.data, shape.ctypes.data))
+        return p_out, r_out, tuple(float(v) for v in sc), dict(zip(self.CG_SHAPE, (int(v) for v in shape)))
+
+    def cg_x_update(self, x, p_a, p_b, alpha_a, alpha_b, use_a=True, use_b=True, half=-1):
+        """x + alpha_a p_a + alpha_b p_b by the fused loop's x update (shm_grid_cg_x_update); use_a / use_b switch a direction off (it is then not read), half 0 / 1
+        updates the lower / upper half of the nodes only (one slab).  Afterwards the handle holds no phi and no divergence.  Test entry point."""
+        x, p_a, p_b = self._n3("cg_x_update", x, p_a, p_b)
+        out = np.empty_like(x)
+        self._chk(self._lib.shm_grid_cg_x_update(self._h, x.ctypes.data, p_a.ctypes.data, p_b.ctypes.data, float(alpha_a), float(alpha_b), int(bool(use_a)),
+                                                 int(bool(use_b)), int(half), out.ctypes.data))
         return out
 
     def set_phi(self, phi):
