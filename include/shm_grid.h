@@ -456,6 +456,59 @@ shm_status shm_grid_get_isosurface_components(shm_solver* s, shm_iso_component* 
                                               int64_t* vertex_component /* [nv] or NULL */);
 shm_status shm_grid_isosurface_keep_components(shm_solver* s, const uint8_t* keep /* [nc] */, int64_t* n_vertices, int64_t* n_triangles);
 
+/* --- Taubin smoothing and vertex normals of an indexed mesh ----------------------------------------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the three entry points by their symbols (dlsym).
+ * phi is kinked at cell scale around the constraint cells, the samplers smooth nothing and marching cubes adds its staircase: these entry points fair an
+ *   indexed mesh on the device with Taubin's lambda | mu passes (cell-scale roughness goes, the enclosed volume stays; plain Laplacian passes, mu = 0, shrink
+ *   the shape) and give the result normals of its own.  Like every mesh stage here the result is a function of the mesh alone, two calls bit-identical, and
+ *   here also independent of the order of the triangle list and of the rotation of a triangle's corners: every neighbour sum is a fixed-point int64 sum, as
+ *   area / volume above.  All other arithmetic is fp64 and unfused, in the order written below (kernels in csrc/shm_mesh_smooth.hip.h, the per-vertex
+ *   arithmetic in csrc/shm_mesh_smooth.h).
+ * Frame, once per call from the input positions: a vertex is finite if its three coordinates are; lo[a], hi[a] = min, max over the finite vertices (on the
+ *   order-preserving integer image of the components); E = max_a (hi[a] - lo[a]) = m 2^e with m in [0.5, 1): q = 2^(e-40); q = 1 without a finite vertex or with
+ *   E = 0 (and e - 40 is held at -1074).  Q_a(x) = llrint((x_a - lo[a]) / q): the division is exact, the rounding to nearest, ties to even; the quotient is held
+ *   to [-2^62, 2^62] first, which changes nothing on a mesh that stays within 2^22 extents of its frame.
+ * One pass with factor f, from the current positions X to X' (Jacobi: every read is from X):
+ *   1. a triangle (a, b, c) contributes iff its three indices are pairwise distinct and its three current positions are finite;
+ *   2. it adds to corner a the int64 triple Q(X_b) + Q(X_c) and the count 2, and the same, cyclically, to b and c;
+ *   3. a vertex with count c > 0:  mean_a = ((double)S_a / (double)c) * q + lo[a];  L_a = mean_a - x_a;  x'_a = x_a + f * L_a;
+ *   4. an axis whose bit is set in fixed[v] keeps x_a bitwise;
+ *   5. a vertex with c = 0 (in no contributing triangle, not finite, or only in triangles with a non-finite corner) keeps its position;
+ *   6. with max_displacement > 0 the move is capped after the pass: X0 the call's input, D = X' - X0, len = sqrt((D_0^2 + D_1^2) + D_2^2); where
+ *      len > max_displacement, x'_a = x0_a + D_a * (max_displacement / len) on the axes that are not fixed.
+ *   A neighbour across an interior manifold edge counts twice, one across a border edge once: on a closed manifold mesh this is the uniform umbrella operator.
+ * Smoothing: `iterations` times a pass with lambda and then, if mu != 0, a pass with mu.  iterations = 0 returns the input positions (normals alone).
+ * Normals of the final positions (optional): per contributing triangle u = B - A, w = C - A, N = (u1 w2 - u2 w1, u2 w0 - u0 w2, u0 w1 - u1 w0); Cmax = the
+ *   largest finite |N_a| over them, an integer-image maximum, = m 2^e: qn = 2^(e-41) (1 with Cmax = 0); every corner receives llrint(N_a / qn) in int64; the
+ *   vertex normal is s / sqrt((s_0^2 + s_1^2) + s_2^2), s the sums converted to fp64, and (0, 0, 0) where the sum is zero or the vertex not finite.
+ *   Marching-cubes triangles here are wound so that it points towards increasing phi.
+ * Limits: at most 2^20 incidences per vertex (triangles with pairwise distinct corners, finite or not; the sums then stay inside int64); nv, nt < 2^31; iterations in [0, 1000];
+ *   0 < lambda <= 1; -1 <= mu <= 0; max_displacement finite and >= 0; an extent hi[a] - lo[a] that overflows fp64 is refused.  Anything else is SHM_ERR_INVALID
+ *   with no output written.  nv = 0 and nt = 0 are valid; repeated corners and duplicate triangles are valid.
+ * shm_grid_smooth_mesh_device: any indexed mesh in device buffers; needs only a handle (no problem, no phi) and works at any `world`.  d_vertices and both
+ *   outputs are in the handle's precision: fp32 positions are promoted to fp64 first and every fp64 result is rounded once on the store.  d_vertices_out may
+ *   alias d_vertices.  d_fixed: one byte per vertex, bit a = axis a frozen, or NULL.  All pointers are checked as shm_grid_sample_device checks its own, and
+ *   a pass over the triangles checks every index BEFORE any is used: an index outside [0, nv) is SHM_ERR_INVALID with nothing written.  Synchronous.
+ *   Per call the vertex -> incidence lists are built once (a count, a scan, a fill through an atomic cursor: 8 bytes per incidence); the passes are then
+ *   gathers, one lane per vertex, without atomics, between two fp64 buffers of the handle; the order inside a list is arbitrary and cannot show in an integer sum.
+ * shm_grid_get_isosurface_smoothed[_device]: the mesh of the resident indexed-mesh slot -- the phi contour, the psi offset mesh, either after the component
+ *   filter -- read from its fp64 vertices, with the triangles of shm_grid_get_isosurface_indexed.  They NEVER write the slot: the closest-point and mesh-raycast
+ *   indexes rely on every resident triangle lying inside one grid cell, so the smoothed positions only ever go to the caller (host: fp64; device: the handle's
+ *   precision, checked pointers).  slide_on_box = 1 builds `fixed` from touches_box's per-axis test with the same exact comparisons: a rim vertex slides inside
+ *   its box face and never leaves it; 0 freezes nothing; another value is SHM_ERR_INVALID.  SHM_ERR_STATE under the conditions of the indexed getters and with
+ *   world > 1 (seam vertices are duplicated between ranks); an empty mesh is SHM_OK and NULL is accepted for it.  phi, Y, psi, the resident mesh, its
+ *   labelling, the closest-point and ray indexes and every other flag are left as they were. */
+typedef struct {
+    int32_t iterations, reserved;
+    double  lambda, mu, max_displacement;
+} shm_smooth_opts;                 /* 32 bytes */
+shm_status shm_grid_smooth_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_vertices /* [3*nv], handle precision */,
+                                       const void* d_triangles /* [3*nt] int64 */, const void* d_fixed /* [nv] uint8, bit a = axis a frozen; or NULL */,
+                                       const shm_smooth_opts* o, void* d_vertices_out /* [3*nv]; may alias d_vertices */, void* d_normals_out /* [3*nv] or NULL */);
+shm_status shm_grid_get_isosurface_smoothed(shm_solver* s, const shm_smooth_opts* o, int32_t slide_on_box, double* vertices_out /* [3*nv] */,
+                                            double* normals_out /* [3*nv] or NULL */);
+shm_status shm_grid_get_isosurface_smoothed_device(shm_solver* s, const shm_smooth_opts* o, int32_t slide_on_box, void* d_vertices_out, void* d_normals_out /* or NULL */);
+
 /* --- audit of Step 1 at sampled grid nodes ---------------------------------------------------------------------------------------------------------------
  * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
  * What it answers: what did the Step 1 that produced the resident Y cost in accuracy, at these nodes?  For every node of the list the device re-evaluates

@@ -12,4 +12,4 @@ Layout:
 """
 from .grid_abi import (GridSolver, ShmError, ShmStats, lib_path, load_library, SHM_F32, SHM_F64,  # noqa: F401
                        plan_slab, comm_unique_id, step1_plane_weights, plan_slab_weighted, audit_sample_nodes, ShmStep1Audit, ShmFieldStats, ShmRedistanceStats,
-                       ShmIsoComponent, ISO_COMPONENT_DTYPE, largest_components_mask)
+                       ShmIsoComponent, ShmSmoothOpts, ISO_COMPONENT_DTYPE, largest_components_mask)

@@ -274,6 +274,17 @@ shm_status shm_grid_isosurface_keep_components(shm_solver* s, const uint8_t* kee
     return guard(s, [&] { s->impl->isosurface_keep_components(keep, n_vertices, n_triangles); });
 }
 
+shm_status shm_grid_smooth_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_vertices, const void* d_triangles, const void* d_fixed, const shm_smooth_opts* o,
+                                       void* d_vertices_out, void* d_normals_out) {
+    return guard(s, [&] { s->impl->smooth_mesh_device(nv, nt, d_vertices, d_triangles, d_fixed, o, d_vertices_out, d_normals_out); });
+}
+shm_status shm_grid_get_isosurface_smoothed(shm_solver* s, const shm_smooth_opts* o, int32_t slide_on_box, double* vertices_out, double* normals_out) {
+    return guard(s, [&] { s->impl->get_isosurface_smoothed(o, slide_on_box, vertices_out, normals_out); });
+}
+shm_status shm_grid_get_isosurface_smoothed_device(shm_solver* s, const shm_smooth_opts* o, int32_t slide_on_box, void* d_vertices_out, void* d_normals_out) {
+    return guard(s, [&] { s->impl->get_isosurface_smoothed_device(o, slide_on_box, d_vertices_out, d_normals_out); });
+}
+
 shm_status shm_grid_sample(shm_solver* s, int64_t Q, const double* pts, double* phi_out, double* grad_out, int64_t* n_answered) {
     return guard(s, [&] { s->impl->sample(Q, pts, phi_out, grad_out, n_answered); });
 }

@@ -578,6 +578,9 @@ struct SolverBase {
     virtual void isosurface_components(int64_t*) = 0;
     virtual void get_isosurface_components(shm_iso_component*, int64_t*, int64_t*) = 0;
     virtual void isosurface_keep_components(const uint8_t*, int64_t*, int64_t*) = 0;
+    virtual void smooth_mesh_device(int64_t, int64_t, const void*, const void*, const void*, const shm_smooth_opts*, void*, void*) = 0;
+    virtual void get_isosurface_smoothed(const shm_smooth_opts*, int32_t, double*, double*) = 0;
+    virtual void get_isosurface_smoothed_device(const shm_smooth_opts*, int32_t, void*, void*) = 0;
     virtual void audit_step1(int64_t, const int64_t*, double*, double*, shm_step1_audit*) = 0;
     virtual void raycast(int64_t, const double*, const double*, double, double, double, double*, double*, int64_t*) = 0;
     virtual void raycast_device(int64_t, const void*, const void*, double, double, double, void*, void*, int64_t*) = 0;

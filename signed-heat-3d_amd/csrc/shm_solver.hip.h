@@ -25,6 +25,7 @@
 #include "shm_audit.hip.h"
 #include "shm_iso_indexed.hip.h"
 #include "shm_iso_components.hip.h"
+#include "shm_mesh_smooth.hip.h"
 #include "shm_raycast.hip.h"
 #include "shm_sample_cubic.hip.h"
 #include "shm_redistance.hip.h"
@@ -3856,6 +3857,175 @@ struct Solver final : SolverBase {
         cmp_nc = 0;
         if (nv_out) *nv_out = iso_idx_nv;
         if (nt_out) *nt_out = iso_idx_nt;
+    }
+
+    // ---- Taubin smoothing and vertex normals of an indexed mesh (shm_mesh_smooth.hip.h) ----------------------------------------------------------------------
+    // Working memory: two fp64 position buffers the passes ping-pong between, a third for the call's input when a cap is set, the fp64 normals, the vertex ->
+    // incidence lists (8 bytes per vertex each for the counts, the offsets and the cursor, 8 per incidence) and the tile totals of their scan.  Allocated on first use
+    // and freed with the handle; nothing of the solver is borrowed, and the resident mesh is only read.
+    DevArray<double> d_sm_X[3], d_sm_N;
+    DevArray<cmp_u64> d_sm_cnt, d_sm_start, d_sm_cursor, d_sm_off;
+    DevArray<unsigned> d_sm_tot;
+    DevArray<uint2> d_sm_nbr;
+    DevArray<SmoothAcc> d_sm_acc;
+    DevArray<uint8_t> d_sm_fixed;
+
+    static void smooth_check_opts(const char* who, const shm_smooth_opts* o) {
+        if (!o) throw Error(SHM_ERR_INVALID, fmt("%s: null options", who));
+        if (o->iterations < 0 || o->iterations > kSmoothMaxIterations) throw Error(SHM_ERR_INVALID, fmt("%s: iterations outside [0, %d]", who, kSmoothMaxIterations));
+        if (!(o->lambda > 0. && o->lambda <= 1.)) throw Error(SHM_ERR_INVALID, fmt("%s: lambda outside (0, 1]", who));
+        if (!(o->mu >= -1. && o->mu <= 0.)) throw Error(SHM_ERR_INVALID, fmt("%s: mu outside [-1, 0]", who));
+        if (!(o->max_displacement >= 0. && o->max_displacement - o->max_displacement == 0.)) throw Error(SHM_ERR_INVALID, fmt("%s: max_displacement is negative or not finite", who));
+    }
+    // Smooths nv > 0 vertices read from d_in (TI = T or double) over validated or still unvalidated triangles; returns the index of the buffer of d_sm_X that
+    // holds the result (the normals, if asked for, are in d_sm_N).  Throws before anything the caller owns is written.
+    template <typename TI>
+    int smooth_run(const char* who, int64_t nv, int64_t nt, const TI* d_in, const int64_t* d_F, bool validate, const uint8_t* d_fixed, const shm_smooth_opts& o, bool normals) {
+        const size_t cv = (size_t)nv * 3;
+        const bool cap = o.max_displacement > 0. && o.iterations > 0;
+        d_sm_acc.alloc(1);
+        d_sm_X[0].alloc(cv);
+        d_sm_X[1].alloc(cv);
+        if (cap) d_sm_X[2].alloc(cv);
+        d_sm_start.alloc((size_t)nv + 1);
+        d_sm_cnt.alloc((size_t)nv);
+        d_sm_cursor.alloc((size_t)nv);
+        SmoothAcc* acc = d_sm_acc.p;
+        double* X0 = cap ? d_sm_X[2].p : d_sm_X[0].p;   // the input lands here; without a cap it is the first pass's source and nothing more
+        hipLaunchKernelGGL((smooth_acc_init_kernel<kBlock>), dim3(1), dim3(kBlock), 0, stream, acc);
+        if (nt > 0 && validate)   // every index is looked at before any is used as an address
+            hipLaunchKernelGGL((cmp_validate_kernel<kBlock>), dim3(grid_for((size_t)nt * 3)), dim3(kBlock), 0, stream, (size_t)nt * 3, d_F, nv, &acc->bad);
+        hipLaunchKernelGGL((smooth_load_kernel<kBlock, TI>), dim3(grid_for((size_t)nv, 1024)), dim3(kBlock), 0, stream, (size_t)nv, d_in, X0, acc);
+        HIPCHK(hipGetLastError());
+        SmoothAcc h;
+        HIPCHK(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (h.bad) throw Error(SHM_ERR_INVALID, fmt("%s: a triangle holds an index outside [0, nv); nothing was written", who));
+        SmoothFrame Fr;
+        double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
+        if (h.nfinite)
+            for (int a = 0; a < 3; a++) { lo[a] = smooth_unkey(h.lo[a]); hi[a] = smooth_unkey(h.hi[a]); }
+        if (!smooth_frame_q(lo, hi, h.nfinite != 0, &Fr.q)) throw Error(SHM_ERR_INVALID, fmt("%s: the extent of the finite vertices overflows fp64", who));
+        for (int a = 0; a < 3; a++) Fr.lo[a] = lo[a];
+        // the vertex -> incidence lists
+        const size_t ntiles = ((size_t)nv + kSmoothTile - 1) / kSmoothTile;
+        d_sm_tot.alloc(ntiles);
+        d_sm_off.alloc(ntiles + 1);
+        d_sm_nbr.alloc(std::max<size_t>(1, (size_t)nt * 3));
+        HIPCHK(hipMemsetAsync(d_sm_cnt.p, 0, (size_t)nv * sizeof(cmp_u64), stream));
+        if (nt > 0) hipLaunchKernelGGL((smooth_count_kernel<kBlock>), dim3(grid_for((size_t)nt)), dim3(kBlock), 0, stream, (size_t)nt, d_F, d_sm_cnt.p);
+        hipLaunchKernelGGL((smooth_tile_total_kernel<kBlock>), dim3((unsigned)ntiles), dim3(kBlock), 0, stream, (size_t)nv, d_sm_cnt.p, d_sm_tot.p, acc);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (h.over) throw Error(SHM_ERR_INVALID, fmt("%s: a vertex lies in more than 2^20 triangles with distinct corners", who));
+        hipLaunchKernelGGL((cmp_scan_kernel<kCmpScanBlock>), dim3(1), dim3(kCmpScanBlock), 0, stream, ntiles, d_sm_tot.p, d_sm_off.p);
+        hipLaunchKernelGGL((smooth_offsets_kernel<kBlock>), dim3((unsigned)ntiles), dim3(kBlock), 0, stream, (size_t)nv, d_sm_cnt.p, d_sm_off.p, d_sm_start.p, d_sm_cursor.p);
+        if (nt > 0) hipLaunchKernelGGL((smooth_fill_kernel<kBlock>), dim3(grid_for((size_t)nt)), dim3(kBlock), 0, stream, (size_t)nt, d_F, d_sm_cursor.p, d_sm_nbr.p);
+        HIPCHK(hipGetLastError());
+        // the passes
+        int cur = cap ? 2 : 0;
+        auto pass = [&](double f) {
+            const int dst = cur == 0 ? 1 : 0;
+            hipLaunchKernelGGL((smooth_pass_kernel<kBlock>), dim3(grid_for((size_t)nv)), dim3(kBlock), 0, stream, Fr, f, cap ? o.max_displacement : 0., (size_t)nv, d_sm_start.p,
+                               d_sm_nbr.p, d_fixed, d_sm_X[cur].p, X0, d_sm_X[dst].p);
+            cur = dst;
+        };
+        for (int it = 0; it < o.iterations; it++) {
+            pass(o.lambda);
+            if (o.mu != 0.) pass(o.mu);
+        }
+        HIPCHK(hipGetLastError());
+        if (normals) {
+            d_sm_N.alloc(cv);
+            double qn = 1.;
+            if (nt > 0) {
+                hipLaunchKernelGGL((smooth_normal_max_kernel<kBlock>), dim3(grid_for((size_t)nt, 1024)), dim3(kBlock), 0, stream, (size_t)nt, d_F, d_sm_X[cur].p, acc);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(&h, acc, sizeof h, hipMemcpyDeviceToHost, stream));
+                HIPCHK(hipStreamSynchronize(stream));
+                qn = smooth_quantum(smooth_unkey(h.nmax), kSmoothNormalBits);
+            }
+            hipLaunchKernelGGL((smooth_normal_kernel<kBlock>), dim3(grid_for((size_t)nv)), dim3(kBlock), 0, stream, qn, (size_t)nv, d_sm_start.p, d_sm_nbr.p, d_sm_X[cur].p,
+                               d_sm_N.p);
+            HIPCHK(hipGetLastError());
+        }
+        return cur;
+    }
+    template <typename TO> void smooth_store(size_t count, const double* src, TO* dst) {
+        hipLaunchKernelGGL((smooth_store_kernel<kBlock, TO>), dim3(grid_for(count, 4096)), dim3(kBlock), 0, stream, count, src, dst);
+    }
+
+    void smooth_mesh_device(int64_t nv, int64_t nt, const void* d_vertices, const void* d_triangles, const void* d_fixed, const shm_smooth_opts* o, void* d_vertices_out,
+                            void* d_normals_out) override {
+        const char* who = "smooth_mesh_device";
+        if (nv < 0 || nt < 0) throw Error(SHM_ERR_INVALID, fmt("%s: a negative count", who));
+        if (nv >= ((int64_t)1 << 31) || nt >= ((int64_t)1 << 31)) throw Error(SHM_ERR_INVALID, fmt("%s: 2^31 or more vertices or triangles", who));
+        smooth_check_opts(who, o);
+        if ((nv > 0 && (!d_vertices || !d_vertices_out)) || (nt > 0 && !d_triangles)) throw Error(SHM_ERR_INVALID, fmt("%s: null buffer with a positive count", who));
+        HIPCHK(hipSetDevice(cfg.device));
+        const size_t cv = (size_t)nv * 3;
+        if (nv > 0) {
+            check_device_buffer(d_vertices, cv * sizeof(T), "the vertex buffer", who, "the 3 nv positions of the mesh");
+            check_device_buffer(d_vertices_out, cv * sizeof(T), "the output vertex buffer", who, "the 3 nv positions of the mesh");
+            if (d_fixed) check_device_buffer(d_fixed, (size_t)nv, "the mask of fixed axes", who, "the nv bytes of the mesh");
+            if (d_normals_out) check_device_buffer(d_normals_out, cv * sizeof(T), "the normal buffer", who, "the 3 nv components of the mesh");
+        }
+        if (nt > 0) check_device_buffer(d_triangles, (size_t)nt * 3 * sizeof(int64_t), "the triangle buffer", who, "the 3 nt indices of the mesh");
+        if (nv == 0) {   // no vertex: an index, if there is one, is out of range
+            if (nt > 0) throw Error(SHM_ERR_INVALID, fmt("%s: a triangle holds an index outside [0, nv); nothing was written", who));
+            return;
+        }
+        const int cur = smooth_run<T>(who, nv, nt, (const T*)d_vertices, (const int64_t*)d_triangles, true, (const uint8_t*)d_fixed, *o, d_normals_out != nullptr);
+        smooth_store<T>(cv, d_sm_X[cur].p, (T*)d_vertices_out);
+        if (d_normals_out) smooth_store<T>(cv, d_sm_N.p, (T*)d_normals_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    // what the two resident entries refuse before they look at their buffers
+    void smooth_resident_check(const char* who, const shm_smooth_opts* o, int32_t slide_on_box) {
+        smooth_check_opts(who, o);
+        if (slide_on_box != 0 && slide_on_box != 1) throw Error(SHM_ERR_INVALID, fmt("%s: slide_on_box is 0 or 1", who));
+        need_iso_indexed(who);
+        if (cfg.world != 1) throw Error(SHM_ERR_STATE, fmt("%s: world > 1 is not supported: seam vertices are duplicated between ranks", who));
+        if (iso_idx_nv >= ((int64_t)1 << 31) || iso_idx_nt >= ((int64_t)1 << 31)) throw Error(SHM_ERR_INVALID, fmt("%s: 2^31 or more vertices or triangles", who));
+        HIPCHK(hipSetDevice(cfg.device));
+    }
+    // the resident indexed mesh (not empty) smoothed into d_sm_X[returned]
+    int smooth_resident(const char* who, const shm_smooth_opts& o, int32_t slide_on_box, bool normals) {
+        const int64_t nv = iso_idx_nv, nt = iso_idx_nt;
+        const uint8_t* fixed = nullptr;
+        if (slide_on_box) {
+            d_sm_fixed.alloc((size_t)nv);
+            hipLaunchKernelGGL((smooth_box_mask_kernel<kBlock>), dim3(grid_for((size_t)nv)), dim3(kBlock), 0, stream, cmp_geom(), (size_t)nv, d_iso_V.p, d_sm_fixed.p);
+            fixed = d_sm_fixed.p;
+        }
+        return smooth_run<double>(who, nv, nt, d_iso_V.p, d_iso_F.p, false, fixed, o, normals);
+    }
+    void get_isosurface_smoothed(const shm_smooth_opts* o, int32_t slide_on_box, double* vertices_out, double* normals_out) override {
+        const char* who = "get_isosurface_smoothed";
+        smooth_resident_check(who, o, slide_on_box);
+        if (iso_idx_nv == 0) return;
+        if (!vertices_out) throw Error(SHM_ERR_INVALID, fmt("%s: null buffer for a non-empty mesh", who));
+        const int cur = smooth_resident(who, *o, slide_on_box, normals_out != nullptr);
+        const size_t bytes = (size_t)iso_idx_nv * 3 * sizeof(double);
+        HIPCHK(hipMemcpyAsync(vertices_out, d_sm_X[cur].p, bytes, hipMemcpyDeviceToHost, stream));
+        if (normals_out) HIPCHK(hipMemcpyAsync(normals_out, d_sm_N.p, bytes, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+    }
+    void get_isosurface_smoothed_device(const shm_smooth_opts* o, int32_t slide_on_box, void* d_vertices_out, void* d_normals_out) override {
+        const char* who = "get_isosurface_smoothed_device";
+        smooth_resident_check(who, o, slide_on_box);
+        if (iso_idx_nv == 0) return;
+        if (!d_vertices_out) throw Error(SHM_ERR_INVALID, fmt("%s: null buffer for a non-empty mesh", who));
+        const size_t cv = (size_t)iso_idx_nv * 3;
+        check_device_buffer(d_vertices_out, cv * sizeof(T), "the output vertex buffer", who, "the 3 nv positions of the mesh");
+        if (d_normals_out) check_device_buffer(d_normals_out, cv * sizeof(T), "the normal buffer", who, "the 3 nv components of the mesh");
+        const int cur = smooth_resident(who, *o, slide_on_box, d_normals_out != nullptr);
+        smooth_store<T>(cv, d_sm_X[cur].p, (T*)d_vertices_out);
+        if (d_normals_out) smooth_store<T>(cv, d_sm_N.p, (T*)d_normals_out);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
     }
 
     // ---- ray casts against a level set of the resident phi (shm_raycast.hip.h) ----------------------------------------------------------------------------

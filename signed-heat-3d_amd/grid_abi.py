@@ -22,6 +22,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_get_field", "shm_grid_get_field_planes", "shm_grid_apply_laplacian", "shm_grid_cg_sweeps", "shm_grid_cg_x_update", "shm_grid_set_phi", "shm_grid_get_constraints", "shm_grid_get_schur", "shm_grid_spd_solve", "shm_grid_apply_projector", "shm_grid_apply_preconditioner", "shm_grid_apply_kplus_sparse", "shm_grid_apply_schur_grid", "shm_grid_isosurface","shm_grid_isosurface_ex", "shm_grid_get_isosurface",
                "shm_grid_isosurface_indexed", "shm_grid_get_isosurface_indexed", "shm_grid_get_isosurface_indexed_device",
                "shm_grid_label_mesh_device", "shm_grid_isosurface_components", "shm_grid_get_isosurface_components", "shm_grid_isosurface_keep_components",
+               "shm_grid_smooth_mesh_device", "shm_grid_get_isosurface_smoothed", "shm_grid_get_isosurface_smoothed_device",
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_sample_cubic", "shm_grid_sample_cubic_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
                "shm_grid_closest_point", "shm_grid_closest_point_device", "shm_grid_mesh_raycast", "shm_grid_mesh_raycast_device",
@@ -110,6 +111,11 @@ class ShmIsoComponent(C.Structure):
                 ("lo", C.c_double * 3), ("hi", C.c_double * 3), ("touches_box", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ShmSmoothOpts(C.Structure):
+    """shm_smooth_opts of include/shm_grid.h (shm_grid_smooth_mesh_device): 32 bytes."""
+    _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("lambda_", C.c_double), ("mu", C.c_double), ("max_displacement", C.c_double)]
+
+
 # the same record as a numpy structured dtype: what GridSolver.isosurface_components returns an array of
 ISO_COMPONENT_DTYPE = np.dtype([("first_vertex", "<i8"), ("n_vertices", "<i8"), ("n_triangles", "<i8"), ("area", "<f8"), ("volume", "<f8"),
                                 ("lo", "<f8", (3,)), ("hi", "<f8", (3,)), ("touches_box", "<i4"), ("reserved", "<i4")])
@@ -195,6 +201,10 @@ def load_library():
         lib.shm_grid_isosurface_components.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         lib.shm_grid_get_isosurface_components.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.shm_grid_isosurface_keep_components.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    if hasattr(lib, "shm_grid_smooth_mesh_device"):
+        lib.shm_grid_smooth_mesh_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(ShmSmoothOpts), C.c_void_p, C.c_void_p]
+        lib.shm_grid_get_isosurface_smoothed.argtypes = [C.c_void_p, C.POINTER(ShmSmoothOpts), C.c_int32, C.c_void_p, C.c_void_p]
+        lib.shm_grid_get_isosurface_smoothed_device.argtypes = lib.shm_grid_get_isosurface_smoothed.argtypes
     if hasattr(lib, "shm_grid_field_at_points"):   # added within ABI 5: found by symbol
         lib.shm_grid_field_at_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                                                  C.POINTER(ShmFieldStats)]
@@ -299,6 +309,7 @@ class GridSolver:
         self.world, self.rank, self.local_slabs = world, rank, local_slabs
         self.device, self.precision = device, precision
         self._keep = None
+        self._iso_counts = None   # (nv, nt) of the resident indexed mesh as this object last saw them
 
     def close(self):
         if getattr(self, "_h", None):
@@ -519,6 +530,7 @@ class GridSolver:
 
     def get_isosurface_indexed(self, nv, nt, device=False):
         """The resident indexed mesh of nv vertices and nt triangles (the counts the last build or isosurface_keep returned), as isosurface_indexed returns it."""
+        self._iso_counts = (int(nv), int(nt))
         if not device:
             V = np.empty((nv, 3), dtype=np.float64)
             F = np.empty((nt, 3), dtype=np.int64)
@@ -575,7 +587,68 @@ class GridSolver:
         mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8).reshape(-1)
         nv, nt = C.c_int64(), C.c_int64()
         self._chk(self._lib.shm_grid_isosurface_keep_components(self._h, mask.ctypes.data if mask.size else None, C.byref(nv), C.byref(nt)))
+        self._iso_counts = (nv.value, nt.value)
         return nv.value, nt.value
+
+    def smooth_mesh_device(self, vertices, triangles, iterations, lam=0.5, mu=-0.53, fixed=None, max_displacement=0.0, normals=False, out=None):
+        """Taubin smoothing and vertex normals of any indexed mesh in device memory (shm_grid_smooth_mesh_device): `iterations` times a pass with lam and,
+        if mu != 0, one with mu; every neighbour sum is a fixed-point integer sum, so the result is a function of the mesh alone, whatever the order of the
+        triangles.  vertices: contiguous [nv, 3] torch tensor on this handle's device in its dtype (float64 for SHM_F64, float32 for SHM_F32); triangles:
+        contiguous int64 tensor of 3 nt indices; fixed: [nv] uint8 tensor, bit a = axis a frozen, or None; max_displacement > 0 caps the move since the
+        input.  Returns the smoothed positions or, with normals=True, (positions, normals) as new tensors; out=vertices smooths in place.  iterations=0
+        gives the normals of the input.  An index outside [0, nv) raises ShmError (SHM_ERR_INVALID)."""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("smooth_mesh_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if vertices.dtype != dt or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+            raise ValueError("smooth_mesh_device: vertices must be a contiguous [nv, 3] %s tensor" % dt)
+        if triangles.dtype != torch.int64 or not triangles.is_contiguous() or triangles.numel() % 3:
+            raise ValueError("smooth_mesh_device: triangles must be a contiguous int64 tensor of 3 nt indices")
+        nv, nt = vertices.shape[0], triangles.numel() // 3
+        if fixed is not None and (fixed.dtype != torch.uint8 or not fixed.is_contiguous() or fixed.numel() != nv):
+            raise ValueError("smooth_mesh_device: fixed must be a contiguous uint8 tensor of nv bytes")
+        if out is None:
+            out = torch.empty_like(vertices)
+        elif out.dtype != dt or out.shape != vertices.shape or not out.is_contiguous():
+            raise ValueError("smooth_mesh_device: out must be a contiguous tensor like vertices")
+        N = torch.empty_like(vertices) if normals else None
+        if vertices.is_cuda:
+            torch.cuda.current_stream(vertices.device).synchronize()   # the mesh may still be in flight on torch's stream
+        o = ShmSmoothOpts(int(iterations), 0, float(lam), float(mu), float(max_displacement))
+        self._chk(self._lib.shm_grid_smooth_mesh_device(self._h, nv, nt, vertices.data_ptr() if nv else None, triangles.data_ptr() if nt else None,
+                                                        fixed.data_ptr() if fixed is not None and nv else None, C.byref(o), out.data_ptr() if nv else None,
+                                                        N.data_ptr() if normals and nv else None))
+        return (out, N) if normals else out
+
+    def isosurface_smoothed(self, iterations, lam=0.5, mu=-0.53, max_displacement=0.0, slide_on_box=True, normals=False, device=False, nv=None):
+        """The resident indexed mesh (isosurface_indexed, isosurface_indexed_psi, either after isosurface_keep) smoothed as smooth_mesh_device smooths,
+        from its fp64 vertices (shm_grid_get_isosurface_smoothed[_device]); its triangles are get_isosurface_indexed's.  The resident mesh is never
+        written: closest_point and mesh_raycast go on answering against the contour.  slide_on_box freezes, per axis, the coordinates that lie in a face
+        of the box, so the rim of a surface that runs into the box slides inside its face.  Returns positions [nv, 3] or (positions, normals): numpy
+        float64, or with device=True torch tensors in the handle's dtype.  nv: the vertex count of the resident mesh; None takes the count this object
+        saw at its last build, filter or redistance_exact (a caller who built the mesh through the raw library passes nv)."""
+        if nv is None:
+            if self._iso_counts is None:
+                raise ValueError("isosurface_smoothed: this object has built no indexed mesh; pass nv")
+            nv = self._iso_counts[0]
+        o = ShmSmoothOpts(int(iterations), 0, float(lam), float(mu), float(max_displacement))
+        if not device:
+            V = np.empty((nv, 3), dtype=np.float64)
+            N = np.empty((nv, 3), dtype=np.float64) if normals else None
+            self._chk(self._lib.shm_grid_get_isosurface_smoothed(self._h, C.byref(o), int(bool(slide_on_box)), V.ctypes.data if nv else None,
+                                                                 N.ctypes.data if normals and nv else None))
+            return (V, N) if normals else V
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("isosurface_smoothed: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dev = torch.device("cuda", self.device)
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        V = torch.empty((nv, 3), dtype=dt, device=dev)
+        N = torch.empty((nv, 3), dtype=dt, device=dev) if normals else None
+        self._chk(self._lib.shm_grid_get_isosurface_smoothed_device(self._h, C.byref(o), int(bool(slide_on_box)), V.data_ptr() if nv else None,
+                                                                    N.data_ptr() if normals and nv else None))
+        return (V, N) if normals else V
 
     def sample(self, points, grad=False):
         """phi of the resident (shifted) phi at points [Q, 3] by the reference's trilinear evaluateFunction (shm_grid_sample): returns (phi [Q],
@@ -699,6 +772,7 @@ class GridSolver:
         if band is None:
             band = 4.0 * self.cell
         self._chk(self._lib.shm_grid_redistance_exact(self._h, float(isovalue), float(band), C.byref(st)))
+        self._iso_counts = (st.n_vertices, st.n_triangles)
         return st.as_dict()
 
     def isosurface_indexed_psi(self, distance, device=False, keep_largest=None, min_triangles=None):

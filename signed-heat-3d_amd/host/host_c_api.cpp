@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <stdexcept>
 #include <string>
 
 #include "mesh_io.h"
@@ -383,6 +384,23 @@ int shmh_isosurface_indexed_filtered(void* hv, double isoval, int64_t keep_large
         if (triangles)
             for (size_t a = 0; a < f.size(); a++)
                 for (int b = 0; b < 3; b++) triangles[3 * a + b] = (int64_t)f[a][(size_t)b];
+    });
+}
+
+// isosurfaceSmoothed through the C++ class, on the mesh the last shmh_isosurface_indexed* call left on the device: positions [3 nv] and, if not NULL,
+// normals [3 nv], nv that call's vertex count (refused if the device's mesh has another count: something rebuilt it in between).
+int shmh_isosurface_smoothed(void* hv, int32_t iterations, double lambda, double mu, double max_displacement, int32_t slide_on_box, int64_t nv, double* positions,
+                             double* normals) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> x, nrm;
+        h->solver.isosurfaceSmoothed(iterations, x, normals ? &nrm : nullptr, lambda, mu, max_displacement, slide_on_box != 0);
+        if ((int64_t)x.size() != nv) throw std::runtime_error("shmh_isosurface_smoothed: the resident mesh does not have nv vertices");
+        for (size_t a = 0; a < x.size(); a++)
+            for (int b = 0; b < 3; b++) {
+                positions[3 * a + b] = x[a][b];
+                if (normals) normals[3 * a + b] = nrm[a][b];
+            }
     });
 }
 

@@ -32,6 +32,10 @@ static void usage() {
                  "      --iso-indexed     Build the exported isosurface on the device in the canonical order (vertices by grid edge, triangles by cell)\n"
                  "      --keep-largest <K> With --iso-indexed: keep the K connected components with the most triangles (filtered on the device)\n"
                  "      --min-triangles <T> With --iso-indexed: drop the components with fewer than T triangles; either flag prints one line per component\n"
+                 "      --smooth <it>     With --iso-indexed: export the mesh after <it> Taubin iterations on the device, with one vn line per vertex (0: normals only)\n"
+                 "      --smooth-lambda <L> The shrinking pass's factor, in (0, 1] (default 0.5)\n"
+                 "      --smooth-mu <M>   The inflating pass's factor, in [-1, 0] (default -0.53; 0: plain Laplacian passes, which shrink the shape)\n"
+                 "      --smooth-cap <D>  Largest move of a vertex from the contour, a length (default 0: none)\n"
                  "      --query <file>    Points to evaluate phi at: raw little-endian float64 xyz triples\n"
                  "      --query-out <file> Raw float64, four values per query point: phi, dphi/dx, dphi/dy, dphi/dz (trilinear; NaN outside the box)\n"
                  "      --query-cubic     With --query: the C1 cubic read instead; ten values per point: phi, the gradient, the Hessian as xx yy zz xy xz yz\n"
@@ -64,6 +68,8 @@ int main(int argc, char** argv) {
     bool redistance = false, redistanceExact = false, haveOffset = false;
     double offset = 0.;
     long long auditCount = -1, keepLargest = -1, minTriangles = -1;
+    int smoothIterations = -1;
+    double smoothLambda = 0.5, smoothMu = -0.53, smoothCap = 0.;
     SignedHeat3DOptions opts;
     GridBackendOptions backend;
     bool verbose = false, isoIndexed = false, queryCubic = false;
@@ -94,6 +100,10 @@ int main(int argc, char** argv) {
         else if (s == "--iso-indexed") isoIndexed = true;
         else if (s == "--keep-largest") keepLargest = atoll(need("--keep-largest"));
         else if (s == "--min-triangles") minTriangles = atoll(need("--min-triangles"));
+        else if (s == "--smooth") smoothIterations = atoi(need("--smooth"));
+        else if (s == "--smooth-lambda") smoothLambda = atof(need("--smooth-lambda"));
+        else if (s == "--smooth-mu") smoothMu = atof(need("--smooth-mu"));
+        else if (s == "--smooth-cap") smoothCap = atof(need("--smooth-cap"));
         else if (s == "--query") queryPath = need("--query");
         else if (s == "--query-out") queryOut = need("--query-out");
         else if (s == "--query-cubic") queryCubic = true;
@@ -164,6 +174,10 @@ int main(int argc, char** argv) {
     }
     if ((keepLargest >= 0 || minTriangles >= 0) && !isoIndexed) {
         std::cerr << "--keep-largest and --min-triangles filter the mesh of --iso-indexed." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (smoothIterations >= 0 && (!isoIndexed || exportPath.empty())) {
+        std::cerr << "--smooth fairs the mesh of --iso-indexed on its way to --export." << std::endl;
         return EXIT_FAILURE;
     }
     if (path.empty()) {
@@ -237,8 +251,13 @@ int main(int argc, char** argv) {
                 }
             } else if (isoIndexed) solver.isosurfaceIndexed(isoval, iv, jf);
             else solver.isosurface(isoval, iv, jf);
+            if (!exportPath.empty() && smoothIterations >= 0) {   // the device's mesh stays the contour: --closest and --mesh-rays below measure against it
+                std::vector<Vector3> sx, sn;
+                solver.isosurfaceSmoothed(smoothIterations, sx, &sn, smoothLambda, smoothMu, smoothCap);
+                writeSurfaceMesh(sx, sn, jf, exportPath);
+                std::cerr << "Smoothed by " << smoothIterations << " Taubin iterations (lambda " << smoothLambda << ", mu " << smoothMu << ", cap " << smoothCap << "): ";
+            } else if (!exportPath.empty()) writeSurfaceMesh(iv, jf, exportPath);
             if (!exportPath.empty()) {
-                writeSurfaceMesh(iv, jf, exportPath);
                 std::cerr << (haveOffset ? "Offset surface written to " : "Isosurface written to ") << exportPath << " (" << iv.size() << " vertices, " << jf.size() << " triangles)" << std::endl;
             }
         }

@@ -13,4 +13,6 @@ VertexPositionGeometry readSurfaceMesh(const std::string& path);
 PointPositionNormalGeometry readPointCloud(const std::string& path);
 // Triangle mesh -> Wavefront OBJ (the demo writes ../export/isosurface.obj through geometry-central, src/main.cpp:188-190).
 void writeSurfaceMesh(const std::vector<Vector3>& vertices, const std::vector<std::array<size_t, 3>>& faces, const std::string& path);
+// The same with one `vn` line per vertex, referenced by the faces as v//vn.
+void writeSurfaceMesh(const std::vector<Vector3>& vertices, const std::vector<Vector3>& normals, const std::vector<std::array<size_t, 3>>& faces, const std::string& path);
 }  // namespace shm_host

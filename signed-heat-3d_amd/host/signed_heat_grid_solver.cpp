@@ -93,16 +93,32 @@ void SignedHeatGridSolver::isosurfaceIndexed(double isoval, std::vector<Vector3>
     int64_t nv = 0, nt = 0;
     if (shm_grid_isosurface_indexed(handle, isoval, &nv, &nt) != SHM_OK)
         throw std::runtime_error(std::string("shm_grid_isosurface_indexed: ") + shm_grid_last_error(handle));
-    std::vector<double> v((size_t)3 * nv);
-    std::vector<int64_t> f((size_t)3 * nt);
-    if (shm_grid_get_isosurface_indexed(handle, nv ? v.data() : nullptr, nt ? f.data() : nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
-    vertices.resize((size_t)nv);
-    faces.resize((size_t)nt);
-    for (int64_t a = 0; a < nv; a++) vertices[(size_t)a] = Vector3{v[3 * a], v[3 * a + 1], v[3 * a + 2]};
-    for (int64_t a = 0; a < nt; a++) faces[(size_t)a] = {(size_t)f[3 * a], (size_t)f[3 * a + 1], (size_t)f[3 * a + 2]};
+    fetchIndexed(nv, nt, vertices, faces);
+}
+
+void SignedHeatGridSolver::isosurfaceSmoothed(int iterations, std::vector<Vector3>& positions, std::vector<Vector3>* normals, double lambda, double mu,
+                                              double maxDisplacement, bool slideOnBox) {
+    if (!handle) throw std::runtime_error("isosurfaceSmoothed: computeDistance has not been called");
+    if (indexedVertices < 0) throw std::runtime_error("isosurfaceSmoothed: no indexed isosurface (isosurfaceIndexed has not been called)");
+    const int64_t nv = indexedVertices;
+    shm_smooth_opts o{};
+    o.iterations = iterations;
+    o.lambda = lambda;
+    o.mu = mu;
+    o.max_displacement = maxDisplacement;
+    std::vector<double> x((size_t)3 * nv), nrm(normals ? (size_t)3 * nv : 0);
+    if (shm_grid_get_isosurface_smoothed(handle, &o, slideOnBox ? 1 : 0, nv ? x.data() : nullptr, normals && nv ? nrm.data() : nullptr) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_get_isosurface_smoothed: ") + shm_grid_last_error(handle));
+    positions.resize((size_t)nv);
+    for (int64_t a = 0; a < nv; a++) positions[(size_t)a] = Vector3{x[3 * a], x[3 * a + 1], x[3 * a + 2]};
+    if (normals) {
+        normals->resize((size_t)nv);
+        for (int64_t a = 0; a < nv; a++) (*normals)[(size_t)a] = Vector3{nrm[3 * a], nrm[3 * a + 1], nrm[3 * a + 2]};
+    }
 }
 
 void SignedHeatGridSolver::fetchIndexed(int64_t nv, int64_t nt, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces) {
+    indexedVertices = nv;
     std::vector<double> v((size_t)3 * nv);
     std::vector<int64_t> f((size_t)3 * nt);
     if (shm_grid_get_isosurface_indexed(handle, nv ? v.data() : nullptr, nt ? f.data() : nullptr) != SHM_OK) throw std::runtime_error(shm_grid_last_error(handle));
@@ -298,8 +314,11 @@ VectorXd SignedHeatGridSolver::redistance(double isoval, double band, shm_redist
 
 VectorXd SignedHeatGridSolver::redistanceExact(double isoval, double band, shm_redistance_exact_stats* stats) {
     if (!handle) throw std::runtime_error("redistanceExact: computeDistance has not been called");
+    shm_redistance_exact_stats own{};
+    if (!stats) stats = &own;
     if (shm_grid_redistance_exact(handle, isoval, band, stats) != SHM_OK)
         throw std::runtime_error(std::string("shm_grid_redistance_exact: ") + shm_grid_last_error(handle));
+    indexedVertices = stats->n_vertices;   // the device's indexed mesh is now that of isoval
     VectorXd psi(nx * ny * nz);
     if (shm_grid_get_redistanced(handle, psi.data()) != SHM_OK) throw std::runtime_error(std::string("shm_grid_get_redistanced: ") + shm_grid_last_error(handle));
     return psi;

@@ -54,6 +54,16 @@ class SignedHeatGridSolver {
     void isosurfaceIndexed(double isoval, std::vector<Vector3>& vertices, std::vector<std::array<size_t, 3>>& faces, int64_t keepLargest, int64_t minTriangles,
                            std::vector<shm_iso_component>* components = nullptr);
 
+    // The mesh of the LAST isosurfaceIndexed() / isosurfaceIndexedOffset() call (filtered if that call filtered it), or the one redistanceExact() left behind,
+    // faired on the device (shm_grid_get_isosurface_smoothed; the contract, bit for bit, in include/shm_grid.h): `iterations` Taubin iterations -- a pass
+    // with lambda, then, if mu != 0, one with mu -- whose neighbour sums are fixed-point integer sums, so the result is a function of the mesh alone.
+    // positions receives the smoothed vertices, in that call's order and with that call's `faces`; normals (optional) the unit vertex normals of the
+    // smoothed mesh, towards increasing phi ((0, 0, 0) at a vertex in no triangle).  maxDisplacement > 0 caps every vertex's move (a length); slideOnBox
+    // keeps, per axis, the coordinates that lie in a face of the box.  iterations = 0: the contour's own positions, and its normals.  The device's
+    // resident mesh is left as it was: closestPoints and castRaysMesh go on answering against the contour.
+    void isosurfaceSmoothed(int iterations, std::vector<Vector3>& positions, std::vector<Vector3>* normals = nullptr, double lambda = 0.5, double mu = -0.53,
+                            double maxDisplacement = 0., bool slideOnBox = true);
+
     // Stands for the reference's private evaluateFunction(u, q) (signed_heat_grid_solver.cpp:405-431), here public and batched: the trilinear value of the phi of
     // the LAST computeDistance() call at every point of q, evaluated on the device (shm_grid_sample; box, NaN and gradient rules in include/shm_grid.h).
     // With gradients != nullptr it is resized to q.size() and receives the gradient of the trilinear interpolant in each point's cell.
@@ -137,6 +147,7 @@ class SignedHeatGridSolver {
     double shortTime = 0., cellSize = 0., lambda = 0.;
     std::vector<double> srcPos, srcWn, srcArea;
     shm_stats stats{};
+    int64_t indexedVertices = -1;   // vertices of the device's resident indexed mesh; -1: none built by this object
 
     void ensureHandle();
     void keepLargestComponents(int64_t keepLargest, int64_t minTriangles, int64_t& nv, int64_t& nt, std::vector<shm_iso_component>* components);

@@ -57,6 +57,8 @@ def load_host_library():
     lib.shmh_isosurface_indexed.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
     lib.shmh_isosurface_components.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int64), C.c_void_p]
     lib.shmh_isosurface_indexed_filtered.argtypes = [C.c_void_p, C.c_double, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p, C.c_void_p]
+    if hasattr(lib, "shmh_isosurface_smoothed"):
+        lib.shmh_isosurface_smoothed.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.argtypes = [C.c_void_p, C.c_void_p]
     lib.shmh_grid_info.restype = None
     _LIB = lib
@@ -226,6 +228,7 @@ class HostSolver:
         V = np.empty((nv.value, 3), dtype=np.float64)
         F = np.empty((nt.value, 3), dtype=np.int64)
         self._chk(call(None, None, V.ctypes.data, F.ctypes.data))
+        self._indexed_nv = nv.value
         return V, F
 
     def isosurface_indexed(self, isovalue=0.0, keep_largest=None, min_triangles=None):
@@ -242,7 +245,20 @@ class HostSolver:
         V = np.empty((nv.value, 3), dtype=np.float64)
         F = np.empty((nt.value, 3), dtype=np.int64)
         self._chk(call(None, None, V.ctypes.data, F.ctypes.data))
+        self._indexed_nv = nv.value
         return V, F
+
+    def isosurface_smoothed(self, iterations, lam=0.5, mu=-0.53, max_displacement=0.0, slide_on_box=True, normals=False):
+        """isosurfaceSmoothed of the C++ mirror (shm_grid_get_isosurface_smoothed): the mesh of the last isosurface_indexed / isosurface_indexed_offset
+        call after `iterations` Taubin iterations on the device.  Returns positions [nv, 3] float64 or, with normals=True, (positions, normals)."""
+        nv = getattr(self, "_indexed_nv", None)
+        if nv is None:
+            raise ValueError("isosurface_smoothed: isosurface_indexed has not been called")
+        X = np.empty((nv, 3), dtype=np.float64)
+        N = np.empty((nv, 3), dtype=np.float64) if normals else None
+        self._chk(self._lib.shmh_isosurface_smoothed(self._h, int(iterations), float(lam), float(mu), float(max_displacement), int(bool(slide_on_box)),
+                                                     nv, X.ctypes.data, N.ctypes.data if normals else None))
+        return (X, N) if normals else X
 
     def isosurface_components(self, isovalue=0.0):
         """isosurfaceComponents of the C++ mirror on the indexed mesh at `isovalue`: a numpy structured array of shm_iso_component records
