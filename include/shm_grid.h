@@ -737,6 +737,74 @@ shm_status shm_grid_closest_point(shm_solver* s, int64_t Q, const double* pts /*
 shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d_pts, double max_dist, void* d_dist, void* d_cp /* or NULL */,
                                          void* d_tri /* int64, or NULL */, int64_t* n_answered);
 
+/* --- closest-point queries against any indexed mesh in device buffers: the attached mesh --------------------------------------------------------------------
+ * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the six entry points by their symbols (dlsym).
+ * shm_grid_closest_point answers against the resident indexed mesh only, whose index needs every triangle inside one cell of the solve grid.  The attached
+ *   mesh is a second mesh, owned by the handle and independent of the resident one and of phi: the smoothed mesh, the input surface, any mesh.  Like
+ *   shm_grid_smooth_mesh_device these entries need only a handle (no problem, no phi) and work at any `world` (no collective: every rank answers its own
+ *   queries against its own attachment).  Rules in csrc/shm_mesh_index.h, kernels in csrc/shm_mesh_index.hip.h, numpy restatement tests/mesh_index_ref.py.
+ * shm_grid_attach_mesh_device: copies the mesh into device memory of the handle -- positions promoted to fp64, ids narrowed to 32 bits -- and builds its
+ *   index; synchronous; the caller's buffers are not referenced after it returns.  d_vertices [3 nv] of the handle's precision, d_triangles [3 nt] int64,
+ *   checked as shm_grid_sample_device checks its pointers.  Every index is looked at before any is used: one outside [0, nv) is SHM_ERR_INVALID.  nv = 0 and
+ *   nt = 0 are valid (an empty mesh answers nothing); repeated corners and duplicate triangles are valid; nv < 2^31, nt <= 2^25.
+ *   A TRIANGLE WITH A NON-FINITE CORNER IS NEVER A CANDIDATE: no query tests it, and the minimum below runs over the other triangles.
+ *   A second attach replaces the first.  A refused attach leaves the previous attachment as it was, answers bitwise unchanged.
+ *   opts (NULL: all zero): cells = c, the index has c cubic cells of size E / c per axis from the lower corner of the box of the finite vertices, E the box's
+ *   longest side; 1 <= c <= 512, else SHM_ERR_INVALID.  cells = 0 chooses c = the smallest integer with 8 c^2 >= nt (at most 512), about two triangles per
+ *   occupied cell on a surface of even triangles, and halves it while the big list below is too long.  c = 1 is brute force on the device.  The choice
+ *   cannot show in an answer.  info (optional) reports what was built.
+ * Answer: shm_grid_closest_point's contract, word for word, with M the attached mesh: d^2(q) = min over the candidate triangles of tri_dist2 (corners minus
+ *   q); tri(q) = the SMALLEST id attaining it, an index into the attached d_triangles; dist = sqrt(d^2); foot point q + c from tri_closest; answered iff
+ *   dist < max_dist; unanswered entries hold NaN, NaN x 3, -1; a query with a non-finite coordinate is unanswered, not an error; *n_answered counts the
+ *   answers.  The result is a function of (mesh, q, max_dist) alone -- not of c, of the order inside the index, of Q or of host against device entry: two
+ *   calls give bit-identical buffers.  The distance is unsigned.
+ * max_dist: positive, else SHM_ERR_INVALID (NaN included).  +inf is valid: the nearest triangle whatever its distance, which is what a deviation measurement
+ *   needs.  Cost: a query walks the Chebyshev shells of index cells around its own until the shell bound passes min(running distance, max_dist), so a query
+ *   with nothing within max_dist -- or, at +inf, far from every triangle -- walks up to the whole index, (2 s + 1)^2 rows per shell s.  A query further than
+ *   4096 index cells from the index's box walks nothing and tests every triangle: nt pair evaluations, whatever max_dist is.
+ * Index: a triangle is filed under every cell of the per-axis range [cell(min_a), cell(max_a)] of its extent (conservative: no triangle / box test), in the
+ *   layout of the resident index: a bitmask of the occupied cells, the prefix of its words' popcounts, the ids grouped by cell.  A triangle whose range
+ *   holds more than 64 cells, and a sliver (above; the threshold 2^-22 taken with the index's cell), is filed under no cell and offered to every query.  That
+ *   list holds at most 4096 triangles: with an explicit c a longer one is SHM_ERR_INVALID, and the message names a coarser `cells`; the automatic c is halved
+ *   instead, down to 1, where only slivers remain on it.  Memory: 24 bytes per vertex, 12 per triangle, 3 (c + 1)^3 / 16 bytes, 4 per occupied cell and per
+ *   (triangle, cell) reference.
+ * shm_grid_attached_closest_point: host buffers, fp64, through the shared pinned staging slots in chunks of 2^20, as shm_grid_closest_point.
+ * shm_grid_attached_closest_point_device: device buffers of the handle's precision, d_tri int64; layouts and pointer checks of shm_grid_closest_point_device.
+ * shm_grid_detach_mesh frees the slot (SHM_OK without one); it is freed with the handle as well.  A query without an attachment is SHM_ERR_STATE.
+ * Errors otherwise as shm_grid_closest_point: SHM_ERR_INVALID for Q < 0, Q > 2^48 or NULL pts / dist_out with Q > 0; Q = 0 is valid.
+ * Nothing else in the handle is touched: phi, psi, Y, the resident mesh, its labelling and its closest-point / ray index stay bitwise as they were. */
+typedef struct {
+    int32_t cells;      /* c; 0: automatic */
+    int32_t reserved;   /* 0 */
+} shm_mesh_index_opts;  /* 8 bytes */
+typedef struct {
+    int32_t cells;          /* the c in force */
+    int32_t automatic;      /* 1: chosen by the call */
+    double  cell;           /* E / c */
+    double  box_min[3];     /* the lower corner of the box of the finite vertices */
+    int64_t n_vertices, n_triangles;
+    int64_t n_occupied;     /* occupied cells */
+    int64_t n_references;   /* (triangle, cell) pairs */
+    int64_t n_big;          /* triangles offered to every query */
+    int64_t bytes;          /* device memory of the slot */
+    double  ms;             /* device time of the attach */
+} shm_mesh_index_info;      /* 96 bytes */
+shm_status shm_grid_attach_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_vertices /* [3*nv], handle precision */,
+                                       const void* d_triangles /* [3*nt] int64 */, const shm_mesh_index_opts* o /* or NULL */, shm_mesh_index_info* info /* or NULL */);
+/* The same attach from host buffers: fp64 positions on handles of both precisions (they are not rounded to the handle's type), staged through device memory
+ * of the call's own.  What the host mirror's attachMesh / attachInputMesh call: that layer holds no device memory. */
+shm_status shm_grid_attach_mesh(shm_solver* s, int64_t nv, int64_t nt, const double* vertices /* [3*nv] */, const int64_t* triangles /* [3*nt] */,
+                                const shm_mesh_index_opts* o /* or NULL */, shm_mesh_index_info* info /* or NULL */);
+/* The resident indexed mesh smoothed exactly as shm_grid_get_isosurface_smoothed smooths it (same options, same refusals: SHM_ERR_STATE without a valid indexed
+ * mesh and with world > 1), attached device to device in fp64 with the resident triangles: nothing is fetched, and the resident mesh stays the contour. */
+shm_status shm_grid_attach_isosurface_smoothed(shm_solver* s, const shm_smooth_opts* so, int32_t slide_on_box, const shm_mesh_index_opts* o /* or NULL */,
+                                               shm_mesh_index_info* info /* or NULL */);
+shm_status shm_grid_detach_mesh(shm_solver* s);
+shm_status shm_grid_attached_closest_point(shm_solver* s, int64_t Q, const double* pts /* [3Q] */, double max_dist, double* dist_out /* [Q] */,
+                                           double* cp_out /* [3Q] or NULL */, int64_t* tri_out /* [Q] or NULL */, int64_t* n_answered);
+shm_status shm_grid_attached_closest_point_device(shm_solver* s, int64_t Q, const void* d_pts, double max_dist, void* d_dist, void* d_cp /* or NULL */,
+                                                  void* d_tri /* int64, or NULL */, int64_t* n_answered);
+
 /* --- ray casts against the resident indexed mesh ----------------------------------------------------------------------------------------------------------
  * Added within ABI 5: no struct changed and SHM_GRID_ABI_VERSION stays 5; a caller detects the two entry points by their symbols (dlsym).
  * shm_grid_raycast intersects the trilinear level set of phi; this call intersects M, the mesh in the indexed slot (as shm_grid_closest_point reads it:

@@ -330,6 +330,27 @@ shm_status shm_grid_closest_point_device(shm_solver* s, int64_t Q, const void* d
     return guard(s, [&] { s->impl->closest_point_device(Q, d_pts, max_dist, d_dist, d_cp, d_tri, n_answered); });
 }
 
+shm_status shm_grid_attach_mesh_device(shm_solver* s, int64_t nv, int64_t nt, const void* d_vertices, const void* d_triangles, const shm_mesh_index_opts* o,
+                                       shm_mesh_index_info* info) {
+    return guard(s, [&] { s->impl->attach_mesh_device(nv, nt, d_vertices, d_triangles, o, info); });
+}
+shm_status shm_grid_attach_mesh(shm_solver* s, int64_t nv, int64_t nt, const double* vertices, const int64_t* triangles, const shm_mesh_index_opts* o,
+                                shm_mesh_index_info* info) {
+    return guard(s, [&] { s->impl->attach_mesh(nv, nt, vertices, triangles, o, info); });
+}
+shm_status shm_grid_attach_isosurface_smoothed(shm_solver* s, const shm_smooth_opts* so, int32_t slide_on_box, const shm_mesh_index_opts* o, shm_mesh_index_info* info) {
+    return guard(s, [&] { s->impl->attach_isosurface_smoothed(so, slide_on_box, o, info); });
+}
+shm_status shm_grid_detach_mesh(shm_solver* s) { return guard(s, [&] { s->impl->detach_mesh(); }); }
+shm_status shm_grid_attached_closest_point(shm_solver* s, int64_t Q, const double* pts, double max_dist, double* dist_out, double* cp_out, int64_t* tri_out,
+                                           int64_t* n_answered) {
+    return guard(s, [&] { s->impl->attached_closest_point(Q, pts, max_dist, dist_out, cp_out, tri_out, n_answered); });
+}
+shm_status shm_grid_attached_closest_point_device(shm_solver* s, int64_t Q, const void* d_pts, double max_dist, void* d_dist, void* d_cp, void* d_tri,
+                                                  int64_t* n_answered) {
+    return guard(s, [&] { s->impl->attached_closest_point_device(Q, d_pts, max_dist, d_dist, d_cp, d_tri, n_answered); });
+}
+
 shm_status shm_grid_mesh_raycast(shm_solver* s, int64_t Q, const double* origins, const double* dirs, double t_min, double t_max, double* t_out, int64_t* tri_out,
                                  double* bary_out, int32_t* count_out, int64_t* n_hits) {
     return guard(s, [&] { s->impl->mesh_raycast(Q, origins, dirs, t_min, t_max, t_out, tri_out, bary_out, count_out, n_hits); });

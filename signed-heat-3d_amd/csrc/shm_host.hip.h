@@ -591,6 +591,12 @@ struct SolverBase {
     virtual void isosurface_indexed_psi(double, int64_t*, int64_t*) = 0;
     virtual void closest_point(int64_t, const double*, double, double*, double*, int64_t*, int64_t*) = 0;
     virtual void closest_point_device(int64_t, const void*, double, void*, void*, void*, int64_t*) = 0;
+    virtual void attach_mesh_device(int64_t, int64_t, const void*, const void*, const shm_mesh_index_opts*, shm_mesh_index_info*) = 0;
+    virtual void attach_mesh(int64_t, int64_t, const double*, const int64_t*, const shm_mesh_index_opts*, shm_mesh_index_info*) = 0;
+    virtual void attach_isosurface_smoothed(const shm_smooth_opts*, int32_t, const shm_mesh_index_opts*, shm_mesh_index_info*) = 0;
+    virtual void detach_mesh() = 0;
+    virtual void attached_closest_point(int64_t, const double*, double, double*, double*, int64_t*, int64_t*) = 0;
+    virtual void attached_closest_point_device(int64_t, const void*, double, void*, void*, void*, int64_t*) = 0;
     virtual void mesh_raycast(int64_t, const double*, const double*, double, double, double*, int64_t*, double*, int32_t*, int64_t*) = 0;
     virtual void mesh_raycast_device(int64_t, const void*, const void*, double, double, void*, void*, void*, void*, int64_t*) = 0;
 };

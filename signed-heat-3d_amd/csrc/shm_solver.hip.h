@@ -31,6 +31,7 @@
 #include "shm_redistance.hip.h"
 #include "shm_redistance_exact.hip.h"
 #include "shm_closest.hip.h"
+#include "shm_mesh_index.hip.h"
 #include "shm_mesh_raycast.hip.h"
 #include "shm_field_points.hip.h"
 #include "shm_plan.h"
@@ -4498,6 +4499,212 @@ struct Solver final : SolverBase {
         closest_begin();
         launch_closest<T>(Q, max_dist, (const T*)pts, (T*)dist, (T*)cpo, (int64_t*)tri);
         const int64_t a = closest_end(Q);
+        if (n_answered) *n_answered = a;
+    }
+
+    // ---- the attached mesh and closest-point queries against it (shm_mesh_index.hip.h) ----------------------------------------------------------------------------
+    // A slot of its own: the mesh (24 bytes per vertex, 12 per triangle), the mask and its rank ((c + 1)^3 / 8 and / 16 bytes), 4 bytes per occupied cell and
+    // per reference, 16 KB of big list.  An attach builds a fresh slot and swaps it in when it is complete, so a refused attach leaves the previous one as it
+    // was.  The scans borrow the tile scratch of the resident index (d_cp_tile: work memory, not part of that index); nothing else of the handle is read or
+    // written, and the queries need no problem and no phi.
+    struct MeshSlot {
+        DevArray<double> V;
+        DevArray<uint32_t> F, rank, first, list, big, count;
+        DevArray<unsigned long long> mask;
+        CpGrid G;
+        int64_t nv = 0, nt = 0;
+        int32_t n_big = 0;
+        bool have = false;   // there is a candidate triangle
+    };
+    std::unique_ptr<MeshSlot> mi_slot;
+    DevArray<unsigned long long> d_mi_acc, d_mi_cnt;
+    DevArray<SmoothAcc> d_mi_box;
+    std::unique_ptr<Event> mi_ev[2];
+
+    // what every attach refuses before it looks at a buffer; returns c (0: automatic)
+    static int attach_check(const char* who, int64_t nv, int64_t nt, const void* vertices, const void* triangles, const shm_mesh_index_opts* o) {
+        if (nv < 0 || nt < 0) throw Error(SHM_ERR_INVALID, fmt("%s: a negative count", who));
+        if (nv >= ((int64_t)1 << 31) || nt > kMiMaxTriangles) throw Error(SHM_ERR_INVALID, fmt("%s: 2^31 or more vertices, or more than 2^25 triangles", who));
+        const int cells = o ? o->cells : 0;
+        if (cells < 0 || cells > kMiMaxCells) throw Error(SHM_ERR_INVALID, fmt("%s: cells outside [0, %d] (0: automatic)", who, kMiMaxCells));
+        if ((nv > 0 && !vertices) || (nt > 0 && !triangles)) throw Error(SHM_ERR_INVALID, fmt("%s: null buffer with a positive count", who));
+        if (nv == 0 && nt > 0) throw Error(SHM_ERR_INVALID, fmt("%s: a triangle holds an index outside [0, nv); the previous attachment stays", who));
+        return cells;
+    }
+    void attach_mesh_device(int64_t nv, int64_t nt, const void* d_vertices, const void* d_triangles, const shm_mesh_index_opts* o, shm_mesh_index_info* info) override {
+        const char* who = "attach_mesh_device";
+        const int cells = attach_check(who, nv, nt, d_vertices, d_triangles, o);
+        HIPCHK(hipSetDevice(cfg.device));
+        if (nv > 0) check_device_buffer(d_vertices, (size_t)nv * 3 * sizeof(T), "the vertex buffer", who, "the 3 nv positions of the mesh");
+        if (nt > 0) check_device_buffer(d_triangles, (size_t)nt * 3 * sizeof(int64_t), "the triangle buffer", who, "the 3 nt indices of the mesh");
+        attach_run<T>(who, nv, nt, (const T*)d_vertices, (const int64_t*)d_triangles, cells, info);
+    }
+    // host buffers, fp64 on handles of both precisions: staged through device memory of the call's own
+    void attach_mesh(int64_t nv, int64_t nt, const double* vertices, const int64_t* triangles, const shm_mesh_index_opts* o, shm_mesh_index_info* info) override {
+        const char* who = "attach_mesh";
+        const int cells = attach_check(who, nv, nt, vertices, triangles, o);
+        HIPCHK(hipSetDevice(cfg.device));
+        DevArray<double> dV;
+        DevArray<int64_t> dF;
+        dV.alloc((size_t)nv * 3);
+        dF.alloc((size_t)nt * 3);
+        if (nv > 0) HIPCHK(hipMemcpyAsync(dV.p, vertices, (size_t)nv * 3 * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (nt > 0) HIPCHK(hipMemcpyAsync(dF.p, triangles, (size_t)nt * 3 * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        attach_run<double>(who, nv, nt, dV.p, dF.p, cells, info);
+    }
+    // the resident indexed mesh smoothed as shm_grid_get_isosurface_smoothed smooths it, attached device to device in fp64: nothing is fetched
+    void attach_isosurface_smoothed(const shm_smooth_opts* so, int32_t slide_on_box, const shm_mesh_index_opts* o, shm_mesh_index_info* info) override {
+        const char* who = "attach_isosurface_smoothed";
+        smooth_resident_check(who, so, slide_on_box);
+        const int cells = attach_check(who, iso_idx_nv, iso_idx_nt, d_iso_V.p, d_iso_F.p, o);
+        const double* X = d_iso_V.p;
+        if (iso_idx_nv > 0) X = d_sm_X[smooth_resident(who, *so, slide_on_box, false)].p;
+        attach_run<double>(who, iso_idx_nv, iso_idx_nt, X, d_iso_F.p, cells, info);
+    }
+    // d_vertices [3 nv] of type TI and d_triangles [3 nt] are device memory the handle may read; the checks above have passed
+    template <typename TI>
+    void attach_run(const char* who, int64_t nv, int64_t nt, const TI* d_vertices, const int64_t* d_triangles, int cells, shm_mesh_index_info* info) {
+        for (auto& e : mi_ev)
+            if (!e) e.reset(new Event());
+        mi_ev[0]->record(stream);
+        std::unique_ptr<MeshSlot> S(new MeshSlot());
+        S->nv = nv;
+        S->nt = nt;
+        d_mi_acc.alloc(kMiAccCounters);
+        d_mi_box.alloc(1);
+        unsigned long long* acc = d_mi_acc.p;
+        unsigned long long h[kMiAccCounters] = {};
+        SmoothAcc box;
+        memset(&box, 0, sizeof box);
+        // load: every index is looked at before any is used as an address
+        HIPCHK(hipMemsetAsync(acc, 0, kMiAccCounters * sizeof(unsigned long long), stream));
+        hipLaunchKernelGGL((smooth_acc_init_kernel<kBlock>), dim3(1), dim3(kBlock), 0, stream, d_mi_box.p);
+        S->V.alloc((size_t)nv * 3);
+        S->F.alloc((size_t)nt * 3);
+        if (nv > 0) hipLaunchKernelGGL((smooth_load_kernel<kBlock, TI>), dim3(grid_for((size_t)nv, 1024)), dim3(kBlock), 0, stream, (size_t)nv, d_vertices, S->V.p, d_mi_box.p);
+        if (nt > 0) hipLaunchKernelGGL((mi_load_tris_kernel<kBlock>), dim3(grid_for((size_t)nt * 3)), dim3(kBlock), 0, stream, (size_t)nt * 3, d_triangles, nv, S->F.p, acc);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(&box, d_mi_box.p, sizeof box, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (h[kMiBad]) throw Error(SHM_ERR_INVALID, fmt("%s: a triangle holds an index outside [0, nv); the previous attachment stays", who));
+        double lo[3] = {0., 0., 0.}, hi[3] = {0., 0., 0.};
+        const bool any = box.nfinite != 0;
+        if (any)
+            for (int a = 0; a < 3; a++) { lo[a] = mi_unkey(box.lo[a]); hi[a] = mi_unkey(box.hi[a]); }
+        int c = cells ? cells : mi_auto_cells(nt);
+        const dim3 tgrid(grid_for((size_t)std::max<int64_t>(nt, 1), 16384));
+        S->big.alloc(kMiMaxBig);
+        size_t nwords = 0;
+        for (;;) {   // (more than once only while the automatic c is halved)
+            if (!mi_grid(c, lo, hi, any, &S->G)) throw Error(SHM_ERR_INVALID, fmt("%s: the extent of the finite vertices overflows fp64 (or underflows a cell)", who));
+            const size_t n1 = (size_t)S->G.n;
+            nwords = (n1 * n1 * n1 + 63) / 64;
+            S->mask.alloc(nwords);
+            HIPCHK(hipMemsetAsync(S->mask.p, 0, nwords * sizeof(unsigned long long), stream));
+            HIPCHK(hipMemsetAsync(acc, 0, kMiAccCounters * sizeof(unsigned long long), stream));
+            if (nt > 0) hipLaunchKernelGGL((mi_mark_kernel<kBlock>), tgrid, dim3(kBlock), 0, stream, S->G, nt, S->V.p, S->F.p, S->mask.p, S->big.p, acc);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(h, acc, sizeof h, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            if (h[kMiNBig] <= (unsigned long long)kMiMaxBig) break;
+            if (cells || c == 1)
+                throw Error(SHM_ERR_INVALID, fmt("%s: %llu triangles are slivers or span more than %d cells at cells = %d, and the list offered to every query holds at most %d: "
+                                                 "attach with a coarser `cells`; the previous attachment stays", who, h[kMiNBig], kMiBigCells, c, kMiMaxBig));
+            c /= 2;
+        }
+        S->n_big = (int32_t)h[kMiNBig];
+        const size_t nrefs = (size_t)h[kMiNRefs];
+        S->have = S->n_big > 0 || nrefs > 0;
+        S->rank.alloc(nwords + 1);
+        cp_scan<true>(nwords, S->mask.p, S->rank.p);
+        uint32_t nocc = 0;
+        HIPCHK(hipMemcpyAsync(&nocc, S->rank.p + nwords, sizeof nocc, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        S->count.alloc((size_t)nocc + 1);
+        S->first.alloc((size_t)nocc + 2);
+        S->list.alloc(nrefs);
+        HIPCHK(hipMemsetAsync(S->count.p, 0, ((size_t)nocc + 1) * sizeof(uint32_t), stream));
+        if (nrefs > 0)
+            hipLaunchKernelGGL((mi_file_kernel<kBlock, false>), tgrid, dim3(kBlock), 0, stream, S->G, nt, S->V.p, S->F.p, S->mask.p, S->rank.p, (const uint32_t*)nullptr, S->count.p,
+                               (uint32_t*)nullptr);
+        cp_scan<false>((size_t)nocc, S->count.p, S->first.p);
+        HIPCHK(hipMemsetAsync(S->count.p, 0, ((size_t)nocc + 1) * sizeof(uint32_t), stream));   // the counts become the fill cursors
+        if (nrefs > 0)
+            hipLaunchKernelGGL((mi_file_kernel<kBlock, true>), tgrid, dim3(kBlock), 0, stream, S->G, nt, S->V.p, S->F.p, S->mask.p, S->rank.p, S->first.p, S->count.p, S->list.p);
+        HIPCHK(hipGetLastError());
+        mi_ev[1]->record(stream);
+        HIPCHK(hipStreamSynchronize(stream));
+        S->count.release();
+        const float ms = elapsed(*mi_ev[0], *mi_ev[1]);
+        const int64_t bytes = (int64_t)((size_t)nv * 24 + (size_t)nt * 12 + nwords * 8 + (nwords + 1) * 4 + ((size_t)nocc + 2) * 4 + std::max<size_t>(nrefs, 1) * 4 + (size_t)kMiMaxBig * 4);
+        if (info) {
+            memset(info, 0, sizeof *info);
+            info->cells = c;
+            info->automatic = cells == 0;
+            info->cell = S->G.cell;
+            for (int a = 0; a < 3; a++) info->box_min[a] = S->G.bbox_min[a];
+            info->n_vertices = nv;
+            info->n_triangles = nt;
+            info->n_occupied = (int64_t)nocc;
+            info->n_references = (int64_t)nrefs;
+            info->n_big = S->n_big;
+            info->bytes = bytes;
+            info->ms = ms;
+        }
+        log("[shm] attach_mesh: %lld vertices, %lld triangles, c = %d%s, %u occupied cells, %zu references, %d big, %lld bytes, %.3f ms", (long long)nv, (long long)nt, c,
+            cells ? "" : " (automatic)", nocc, nrefs, S->n_big, (long long)bytes, ms);
+        mi_slot = std::move(S);
+    }
+    void detach_mesh() override {
+        HIPCHK(hipSetDevice(cfg.device));
+        HIPCHK(hipStreamSynchronize(stream));
+        mi_slot.reset();
+    }
+    void attached_check(const char* who, int64_t Q, const std::array<QueryCol, 4>& cols, double max_dist) {
+        query_check(who, "queries", "points or distance output", Q, cols);
+        if (!(max_dist > 0.)) throw Error(SHM_ERR_INVALID, fmt("%s: max_dist must be positive (+inf: the nearest triangle whatever its distance)", who));
+        if (!mi_slot) throw Error(SHM_ERR_STATE, fmt("%s: no mesh is attached (shm_grid_attach_mesh_device)", who));
+    }
+    void attached_begin() {
+        d_mi_cnt.alloc(kCpCounters);
+        HIPCHK(hipMemsetAsync(d_mi_cnt.p, 0, kCpCounters * sizeof(unsigned long long), stream));
+    }
+    int64_t attached_end(int64_t Q) {
+        unsigned long long c[kCpCounters] = {};
+        HIPCHK(hipMemcpyAsync(c, d_mi_cnt.p, sizeof c, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        log("[shm] attached_closest_point: %lld queries, %llu answered, %llu triangle tests", (long long)Q, c[kCpAnswered], c[kCpTriTests]);
+        return (int64_t)c[kCpAnswered];
+    }
+    template <typename TIO> void launch_attached(int64_t Q, double max_dist, const TIO* pts, TIO* dist, TIO* cpo, int64_t* tri) {
+        if (Q <= 0) return;
+        const MeshSlot& S = *mi_slot;
+        const MiIndex X{S.mask.p, S.rank.p, S.first.p, S.list.p, S.big.p, S.V.p, S.F.p, S.nt, S.n_big};
+        const int grid = grid_for((size_t)Q, 16384);
+        if (S.have) hipLaunchKernelGGL((mesh_index_query_kernel<TIO, true>), dim3(grid), dim3(kBlock), 0, stream, S.G, X, Q, max_dist, pts, dist, cpo, tri, d_mi_cnt.p);
+        else hipLaunchKernelGGL((mesh_index_query_kernel<TIO, false>), dim3(grid), dim3(kBlock), 0, stream, S.G, X, Q, max_dist, pts, dist, cpo, tri, d_mi_cnt.p);
+        HIPCHK(hipGetLastError());
+    }
+    void attached_closest_point(int64_t Q, const double* pts, double max_dist, double* dist, double* cpo, int64_t* tri, int64_t* n_answered) override {
+        const auto cols = closest_cols(pts, dist, cpo, tri);
+        attached_check("attached_closest_point", Q, cols, max_dist);
+        HIPCHK(hipSetDevice(cfg.device));
+        attached_begin();
+        query_stream(Q, cols, [&](int64_t m, void* const* d) { launch_attached<double>(m, max_dist, (const double*)d[0], (double*)d[1], (double*)d[2], (int64_t*)d[3]); });
+        const int64_t a = attached_end(Q);
+        if (n_answered) *n_answered = a;
+    }
+    void attached_closest_point_device(int64_t Q, const void* pts, double max_dist, void* dist, void* cpo, void* tri, int64_t* n_answered) override {
+        const char* who = "attached_closest_point_device";
+        const auto cols = closest_cols(pts, dist, cpo, tri);
+        attached_check(who, Q, cols, max_dist);
+        HIPCHK(hipSetDevice(cfg.device));
+        check_device_columns(who, "queries", Q, cols);
+        attached_begin();
+        launch_attached<T>(Q, max_dist, (const T*)pts, (T*)dist, (T*)cpo, (int64_t*)tri);
+        const int64_t a = attached_end(Q);
         if (n_answered) *n_answered = a;
     }
 

@@ -26,6 +26,7 @@ ABI_SYMBOLS = ["shm_grid_owned_planes", "shm_grid_create", "shm_grid_destroy", "
                "shm_grid_sample", "shm_grid_sample_device", "shm_grid_sample_cubic", "shm_grid_sample_cubic_device", "shm_grid_raycast", "shm_grid_raycast_device",
                "shm_grid_redistance", "shm_grid_get_redistanced", "shm_grid_get_redistanced_device", "shm_grid_redistance_exact", "shm_grid_isosurface_indexed_psi",
                "shm_grid_closest_point", "shm_grid_closest_point_device", "shm_grid_mesh_raycast", "shm_grid_mesh_raycast_device",
+               "shm_grid_attach_mesh_device", "shm_grid_attach_mesh", "shm_grid_attach_isosurface_smoothed", "shm_grid_detach_mesh", "shm_grid_attached_closest_point", "shm_grid_attached_closest_point_device",
                "shm_grid_field_at_points", "shm_grid_field_at_points_device",
                "shm_grid_audit_step1", "shm_comm_unique_id", "shm_plan_slab", "shm_step1_plane_weights", "shm_plan_slab_weighted"]
 
@@ -114,6 +115,23 @@ class ShmIsoComponent(C.Structure):
 class ShmSmoothOpts(C.Structure):
     """shm_smooth_opts of include/shm_grid.h (shm_grid_smooth_mesh_device): 32 bytes."""
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("lambda_", C.c_double), ("mu", C.c_double), ("max_displacement", C.c_double)]
+
+
+class ShmMeshIndexOpts(C.Structure):
+    """shm_mesh_index_opts of include/shm_grid.h (shm_grid_attach_mesh_device): 8 bytes."""
+    _fields_ = [("cells", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ShmMeshIndexInfo(C.Structure):
+    """shm_mesh_index_info of include/shm_grid.h (shm_grid_attach_mesh_device): 96 bytes."""
+    _fields_ = [("cells", C.c_int32), ("automatic", C.c_int32), ("cell", C.c_double), ("box_min", C.c_double * 3), ("n_vertices", C.c_int64),
+                ("n_triangles", C.c_int64), ("n_occupied", C.c_int64), ("n_references", C.c_int64), ("n_big", C.c_int64), ("bytes", C.c_int64), ("ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "box_min" else getattr(self, k)) for k, _ in self._fields_}
+
+
+assert C.sizeof(ShmMeshIndexOpts) == 8 and C.sizeof(ShmMeshIndexInfo) == 96
 
 
 # the same record as a numpy structured dtype: what GridSolver.isosurface_components returns an array of
@@ -226,6 +244,13 @@ def load_library():
     if hasattr(lib, "shm_grid_closest_point"):   # added within ABI 5: found by symbol
         lib.shm_grid_closest_point.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         lib.shm_grid_closest_point_device.argtypes = lib.shm_grid_closest_point.argtypes
+    if hasattr(lib, "shm_grid_attach_mesh_device"):   # added within ABI 5: found by symbol
+        lib.shm_grid_attach_mesh_device.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(ShmMeshIndexOpts), C.POINTER(ShmMeshIndexInfo)]
+        lib.shm_grid_attach_mesh.argtypes = lib.shm_grid_attach_mesh_device.argtypes
+        lib.shm_grid_attach_isosurface_smoothed.argtypes = [C.c_void_p, C.POINTER(ShmSmoothOpts), C.c_int32, C.POINTER(ShmMeshIndexOpts), C.POINTER(ShmMeshIndexInfo)]
+        lib.shm_grid_detach_mesh.argtypes = [C.c_void_p]
+        lib.shm_grid_attached_closest_point.argtypes = lib.shm_grid_closest_point.argtypes
+        lib.shm_grid_attached_closest_point_device.argtypes = lib.shm_grid_closest_point.argtypes
     if hasattr(lib, "shm_grid_mesh_raycast"):   # added within ABI 5: found by symbol
         lib.shm_grid_mesh_raycast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.POINTER(C.c_int64)]
@@ -932,6 +957,87 @@ class GridSolver:
         self._chk(self._lib.shm_grid_closest_point_device(self._h, Q, points.data_ptr() if Q else None, float(max_dist), dist.data_ptr() if Q else None,
                                                           c.data_ptr() if cp and Q else None, t.data_ptr() if tri and Q else None, C.byref(na)))
         return self._closest_result(dist, c, t, na.value, label)
+
+    def attach_mesh_device(self, vertices, triangles, cells=0):
+        """Attaches any indexed mesh in device memory to this handle and builds its closest-point index (shm_grid_attach_mesh_device): vertices a contiguous
+        [nv, 3] torch tensor on this handle's device in its dtype, triangles a contiguous int64 tensor of 3 nt indices.  The mesh is copied: the tensors
+        may be freed afterwards.  Independent of the resident mesh and of phi; needs no problem.  cells: index cells per axis, 1 to 512, 0 = automatic; it
+        cannot show in an answer.  Returns the info as a dict: cells, automatic, cell, box_min, n_vertices, n_triangles, n_occupied, n_references, n_big,
+        bytes, ms.  An index outside [0, nv) or a refused index raises ShmError (SHM_ERR_INVALID) and leaves the previous attachment as it was."""
+        if not hasattr(self._lib, "shm_grid_attach_mesh_device"):
+            raise RuntimeError("attach_mesh_device: this build of libshm_grid.so does not export shm_grid_attach_mesh_device")
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("attach_mesh_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if vertices.dtype != dt or vertices.dim() != 2 or vertices.shape[1] != 3 or not vertices.is_contiguous():
+            raise ValueError("attach_mesh_device: vertices must be a contiguous [nv, 3] %s tensor" % dt)
+        if triangles.dtype != torch.int64 or not triangles.is_contiguous() or triangles.numel() % 3:
+            raise ValueError("attach_mesh_device: triangles must be a contiguous int64 tensor of 3 nt indices")
+        nv, nt = vertices.shape[0], triangles.numel() // 3
+        if vertices.is_cuda:
+            torch.cuda.current_stream(vertices.device).synchronize()   # the mesh may still be in flight on torch's stream
+        o, info = ShmMeshIndexOpts(int(cells), 0), ShmMeshIndexInfo()
+        self._chk(self._lib.shm_grid_attach_mesh_device(self._h, nv, nt, vertices.data_ptr() if nv else None, triangles.data_ptr() if nt else None, C.byref(o),
+                                                        C.byref(info)))
+        return info.as_dict()
+
+    def attach_mesh(self, vertices, triangles, cells=0):
+        """attach_mesh_device from host arrays (shm_grid_attach_mesh): vertices [nv, 3] float64 -- kept as fp64 on handles of both precisions -- and
+        triangles [nt, 3] int64.  Returns the info dict."""
+        V = _f64(vertices).reshape(-1, 3)
+        F = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+        o, info = ShmMeshIndexOpts(int(cells), 0), ShmMeshIndexInfo()
+        self._chk(self._lib.shm_grid_attach_mesh(self._h, len(V), len(F), V.ctypes.data if len(V) else None, F.ctypes.data if len(F) else None, C.byref(o), C.byref(info)))
+        return info.as_dict()
+
+    def attach_isosurface_smoothed(self, iterations, lam=0.5, mu=-0.53, max_displacement=0.0, slide_on_box=True, cells=0):
+        """The resident indexed mesh smoothed as isosurface_smoothed smooths it, attached device to device in fp64 (shm_grid_attach_isosurface_smoothed):
+        nothing is fetched and the resident mesh stays the contour.  Returns the info dict."""
+        so = ShmSmoothOpts(int(iterations), 0, float(lam), float(mu), float(max_displacement))
+        o, info = ShmMeshIndexOpts(int(cells), 0), ShmMeshIndexInfo()
+        self._chk(self._lib.shm_grid_attach_isosurface_smoothed(self._h, C.byref(so), int(bool(slide_on_box)), C.byref(o), C.byref(info)))
+        return info.as_dict()
+
+    def detach_mesh(self):
+        """Frees the attached mesh and its index (shm_grid_detach_mesh); a query afterwards raises ShmError (SHM_ERR_STATE)."""
+        self._chk(self._lib.shm_grid_detach_mesh(self._h))
+
+    def attached_closest_point(self, points, max_dist=float("inf"), cp=True, tri=True):
+        """closest_point against the attached mesh (shm_grid_attached_closest_point): returns (dist [Q], [cp [Q, 3],] [tri [Q] int64,] n_answered), float64.
+        max_dist is positive and may be +inf (the default): the nearest triangle whatever its distance.  tri indexes the attached triangles."""
+        if not hasattr(self._lib, "shm_grid_attached_closest_point"):
+            raise RuntimeError("attached_closest_point: this build of libshm_grid.so does not export shm_grid_attached_closest_point")
+        pts = _f64(points).reshape(-1, 3)
+        Q = pts.shape[0]
+        dist = np.empty(Q, dtype=np.float64)
+        c = np.empty((Q, 3), dtype=np.float64) if cp else None
+        t = np.empty(Q, dtype=np.int64) if tri else None
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_attached_closest_point(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, c.ctypes.data if cp else None,
+                                                            t.ctypes.data if tri else None, C.byref(na)))
+        return (dist,) + tuple(x for x in (c, t) if x is not None) + (na.value,)
+
+    def attached_closest_point_device(self, points, max_dist=float("inf"), cp=True, tri=True):
+        """The same on device memory (shm_grid_attached_closest_point_device), with closest_point_device's conventions."""
+        if not hasattr(self._lib, "shm_grid_attached_closest_point_device"):
+            raise RuntimeError("attached_closest_point_device: this build of libshm_grid.so does not export shm_grid_attached_closest_point_device")
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("attached_closest_point_device: torch sees no HIP device (was torch imported after libshm_grid.so was loaded? import it first)")
+        dt = torch.float64 if self.precision == SHM_F64 else torch.float32
+        if points.dtype != dt or points.dim() != 2 or points.shape[1] != 3 or not points.is_contiguous():
+            raise ValueError("attached_closest_point_device: points must be a contiguous [Q, 3] %s tensor" % dt)
+        Q = points.shape[0]
+        dist = torch.empty(Q, dtype=dt, device=points.device)
+        c = torch.empty((Q, 3), dtype=dt, device=points.device) if cp else None
+        t = torch.empty(Q, dtype=torch.int64, device=points.device) if tri else None
+        if points.is_cuda:
+            torch.cuda.current_stream(points.device).synchronize()   # the points may still be in flight on torch's stream
+        na = C.c_int64()
+        self._chk(self._lib.shm_grid_attached_closest_point_device(self._h, Q, points.data_ptr() if Q else None, float(max_dist), dist.data_ptr() if Q else None,
+                                                                   c.data_ptr() if cp and Q else None, t.data_ptr() if tri and Q else None, C.byref(na)))
+        return (dist,) + tuple(x for x in (c, t) if x is not None) + (na.value,)
 
     def get_redistanced(self, device=False):
         """psi of the last redistance(): [n^3] float64 in get_phi's node order, or with device=True a torch tensor of the handle's dtype on its device,

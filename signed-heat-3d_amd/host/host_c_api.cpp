@@ -268,6 +268,71 @@ int shmh_closest_points(void* hv, int64_t Q, const double* pts, double max_dist,
     });
 }
 
+// attachMesh / attachInputMesh / attachSmoothed / detachMesh / closestPointsAttached through the C++ class.  info (optional) receives the shm_mesh_index_info.
+// shmh_input_fan: the fan-triangulated input surface attachInputMesh attaches; counts[0] = vertices, counts[1] = triangles; V [3 nv] and F [3 nt] or NULL.
+int shmh_attach_mesh(void* hv, int64_t nv, int64_t nt, const double* V, const int64_t* F, int32_t cells, shm_mesh_index_info* info) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> v((size_t)nv);
+        std::vector<std::array<size_t, 3>> f((size_t)nt);
+        for (int64_t a = 0; a < nv; a++) v[(size_t)a] = Vector3{V[3 * a], V[3 * a + 1], V[3 * a + 2]};
+        for (int64_t a = 0; a < nt; a++) f[(size_t)a] = {(size_t)F[3 * a], (size_t)F[3 * a + 1], (size_t)F[3 * a + 2]};
+        const shm_mesh_index_info i = h->solver.attachMesh(v, f, cells);
+        if (info) *info = i;
+    });
+}
+int shmh_attach_input_mesh(void* hv, int32_t cells, shm_mesh_index_info* info) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        const shm_mesh_index_info i = h->solver.attachInputMesh(cells);
+        if (info) *info = i;
+    });
+}
+int shmh_attach_smoothed(void* hv, int32_t iterations, double lambda, double mu, double max_displacement, int32_t slide_on_box, int32_t cells, shm_mesh_index_info* info) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        const shm_mesh_index_info i = h->solver.attachSmoothed(iterations, lambda, mu, max_displacement, slide_on_box != 0, cells);
+        if (info) *info = i;
+    });
+}
+int shmh_detach_mesh(void* hv) {
+    Host* h = (Host*)hv;
+    return guard([&] { h->solver.detachMesh(); });
+}
+int shmh_input_fan(void* hv, int64_t* counts, double* V, int64_t* F) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        const auto& v = h->solver.inputVertices();
+        const auto& f = h->solver.inputFanFaces();
+        counts[0] = (int64_t)v.size();
+        counts[1] = (int64_t)f.size();
+        if (V)
+            for (size_t a = 0; a < v.size(); a++)
+                for (int b = 0; b < 3; b++) V[3 * a + b] = v[a][b];
+        if (F)
+            for (size_t a = 0; a < f.size(); a++)
+                for (int b = 0; b < 3; b++) F[3 * a + b] = (int64_t)f[a][b];
+    });
+}
+int shmh_closest_points_attached(void* hv, int64_t Q, const double* pts, double max_dist, double* dist_out, double* cp_out, int64_t* tri_out, int64_t* n_answered) {
+    Host* h = (Host*)hv;
+    return guard([&] {
+        std::vector<Vector3> q((size_t)Q), c;
+        for (int64_t a = 0; a < Q; a++) q[(size_t)a] = Vector3{pts[3 * a], pts[3 * a + 1], pts[3 * a + 2]};
+        std::vector<int64_t> t;
+        const std::vector<double> d = h->solver.closestPointsAttached(q, max_dist, cp_out ? &c : nullptr, tri_out ? &t : nullptr);
+        int64_t answered = 0;
+        for (int64_t a = 0; a < Q; a++) {
+            dist_out[a] = d[(size_t)a];
+            answered += d[(size_t)a] == d[(size_t)a] ? 1 : 0;
+            if (cp_out)
+                for (int b = 0; b < 3; b++) cp_out[3 * a + b] = c[(size_t)a][b];
+            if (tri_out) tri_out[a] = t[(size_t)a];
+        }
+        if (n_answered) *n_answered = answered;
+    });
+}
+
 // castRaysMesh through the C++ class: rays against the device's resident indexed mesh -> t_out [Q], tri_out [Q], bary_out [2Q], count_out [Q] (each or NULL),
 // *n_hits finite answers.
 int shmh_cast_rays_mesh(void* hv, int64_t Q, const double* origins, const double* dirs, double t_min, double t_max, double* t_out, int64_t* tri_out, double* bary_out,

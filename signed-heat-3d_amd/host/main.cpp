@@ -50,6 +50,9 @@ static void usage() {
                  "      --closest <file>  With --iso-indexed: points to measure against the indexed mesh (filtered / offset as exported), in --query's format\n"
                  "      --closest-out <file> Raw float64, five values per point: distance (unsigned; NaN beyond --closest-max), nearest point xyz, triangle index (-1: none)\n"
                  "      --closest-max <D> How far the mesh may be from a point, in cells (default 4, at most 16)\n"
+                 "      --closest-mesh <contour|smoothed|input> What --closest measures against: the exported contour (default), the mesh --smooth made of it (attached on\n"
+                 "                        the device, not fetched), or the input surface (polygons as fans from their first vertex; the triangle index is into that list).\n"
+                 "                        For smoothed and input --closest-max may exceed 16 cells and may be inf\n"
                  "      --mesh-rays <file> With --iso-indexed: rays to cast against the indexed mesh (filtered / offset as exported), in --rays' format, t in [0, inf)\n"
                  "      --mesh-rays-out <file> Raw float64, five values per ray: t (NaN: no hit), triangle index (-1), barycentrics u v, number of triangles crossed\n"
                  "      --field-at <file> Points to evaluate the diffused normal field Y of Steps 1-2 at, anywhere in space, in --query's format\n"
@@ -61,7 +64,7 @@ static void usage() {
 
 int main(int argc, char** argv) {
     std::string path, out, exportPath, queryPath, queryOut, raysPath, raysOut, psiOut, closestPath, closestOut, meshRaysPath, meshRaysOut;
-    std::string fieldPath, fieldOut, fieldArith = "auto";
+    std::string fieldPath, fieldOut, fieldArith = "auto", closestMesh = "contour";
     double fieldLambda = 0., fieldBudget = 0.;
     double closestMax = 4.;
     double isoval = 0., raysIso = 0., band = std::numeric_limits<double>::infinity();
@@ -118,6 +121,7 @@ int main(int argc, char** argv) {
         else if (s == "--closest") closestPath = need("--closest");
         else if (s == "--closest-out") closestOut = need("--closest-out");
         else if (s == "--closest-max") closestMax = atof(need("--closest-max"));
+        else if (s == "--closest-mesh") closestMesh = need("--closest-mesh");
         else if (s == "--mesh-rays") meshRaysPath = need("--mesh-rays");
         else if (s == "--mesh-rays-out") meshRaysOut = need("--mesh-rays-out");
         else if (s == "--field-at") fieldPath = need("--field-at");
@@ -142,6 +146,18 @@ int main(int argc, char** argv) {
     }
     if (closestPath.empty() != closestOut.empty() || (!closestPath.empty() && !isoIndexed)) {
         std::cerr << "--closest and --closest-out go together and measure against the mesh of --iso-indexed." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (closestMesh != "contour" && closestMesh != "smoothed" && closestMesh != "input") {
+        std::cerr << "--closest-mesh is contour, smoothed or input." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (closestMesh != "contour" && closestPath.empty()) {
+        std::cerr << "--closest-mesh chooses what --closest measures against and needs --closest and --closest-out." << std::endl;
+        return EXIT_FAILURE;
+    }
+    if (closestMesh == "smoothed" && smoothIterations < 0) {
+        std::cerr << "--closest-mesh smoothed measures against the mesh of --smooth <it>, which is missing." << std::endl;
         return EXIT_FAILURE;
     }
     if (meshRaysPath.empty() != meshRaysOut.empty() || (!meshRaysPath.empty() && !isoIndexed)) {
@@ -272,7 +288,15 @@ int main(int argc, char** argv) {
             std::vector<Vector3> q(raw.size() / 3), c;
             for (size_t a = 0; a < q.size(); a++) q[a] = Vector3{raw[3 * a], raw[3 * a + 1], raw[3 * a + 2]};
             std::vector<int64_t> t;
-            const std::vector<double> d = solver.closestPoints(q, closestMax * solver.gridCell(), &c, &t);
+            std::vector<double> d;
+            if (closestMesh == "contour") d = solver.closestPoints(q, closestMax * solver.gridCell(), &c, &t);
+            else {
+                const shm_mesh_index_info mi = closestMesh == "input" ? solver.attachInputMesh() : solver.attachSmoothed(smoothIterations, smoothLambda, smoothMu, smoothCap);
+                std::cerr << "Attached the " << closestMesh << " mesh: " << mi.n_vertices << " vertices, " << mi.n_triangles << " triangles, " << mi.cells
+                          << " index cells per axis, " << mi.n_references << " references, " << mi.n_big << " offered to every query" << std::endl;
+                d = solver.closestPointsAttached(q, closestMax * solver.gridCell(), &c, &t);
+                solver.detachMesh();
+            }
             std::vector<double> res(5 * q.size());
             size_t answered = 0;
             for (size_t a = 0; a < q.size(); a++) {
@@ -283,7 +307,7 @@ int main(int argc, char** argv) {
             }
             std::ofstream o(closestOut, std::ios::binary);
             o.write((const char*)res.data(), (std::streamsize)(res.size() * sizeof(double)));
-            std::cerr << q.size() << " points measured against the indexed mesh within " << closestMax << " cells: " << answered
+            std::cerr << q.size() << " points measured against the " << (closestMesh == "contour" ? "indexed" : closestMesh) << " mesh within " << closestMax << " cells: " << answered
                       << " answered; distance, nearest point and triangle written to " << closestOut << std::endl;
         }
         if (!meshRaysPath.empty()) {

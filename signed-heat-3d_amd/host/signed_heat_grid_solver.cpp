@@ -283,6 +283,65 @@ std::vector<double> SignedHeatGridSolver::closestPoints(const std::vector<Vector
     return dist;
 }
 
+shm_mesh_index_info SignedHeatGridSolver::attachMesh(const std::vector<Vector3>& vertices, const std::vector<std::array<size_t, 3>>& triangles, int cells) {
+    ensureHandle();
+    std::vector<double> v(3 * vertices.size());
+    std::vector<int64_t> f(3 * triangles.size());
+    for (size_t a = 0; a < vertices.size(); a++)
+        for (int b = 0; b < 3; b++) v[3 * a + b] = vertices[a][b];
+    for (size_t a = 0; a < triangles.size(); a++)
+        for (int b = 0; b < 3; b++) f[3 * a + b] = (int64_t)triangles[a][b];
+    shm_mesh_index_opts o{};
+    o.cells = cells;
+    shm_mesh_index_info info{};
+    if (shm_grid_attach_mesh(handle, (int64_t)vertices.size(), (int64_t)triangles.size(), v.empty() ? nullptr : v.data(), f.empty() ? nullptr : f.data(), &o, &info) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_attach_mesh: ") + shm_grid_last_error(handle));
+    return info;
+}
+
+shm_mesh_index_info SignedHeatGridSolver::attachInputMesh(int cells) {
+    if (!inputIsMesh)
+        throw std::runtime_error("attachInputMesh: the last computeDistance was given no surface mesh (a point cloud has no faces to measure against)");
+    return attachMesh(inputPositions, inputFaces, cells);
+}
+
+shm_mesh_index_info SignedHeatGridSolver::attachSmoothed(int iterations, double lambda, double mu, double maxDisplacement, bool slideOnBox, int cells) {
+    if (!handle) throw std::runtime_error("attachSmoothed: computeDistance has not been called");
+    shm_smooth_opts so{};
+    so.iterations = iterations;
+    so.lambda = lambda;
+    so.mu = mu;
+    so.max_displacement = maxDisplacement;
+    shm_mesh_index_opts o{};
+    o.cells = cells;
+    shm_mesh_index_info info{};
+    if (shm_grid_attach_isosurface_smoothed(handle, &so, slideOnBox ? 1 : 0, &o, &info) != SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_attach_isosurface_smoothed: ") + shm_grid_last_error(handle));
+    return info;
+}
+
+void SignedHeatGridSolver::detachMesh() {
+    if (handle && shm_grid_detach_mesh(handle) != SHM_OK) throw std::runtime_error(std::string("shm_grid_detach_mesh: ") + shm_grid_last_error(handle));
+}
+
+std::vector<double> SignedHeatGridSolver::closestPointsAttached(const std::vector<Vector3>& q, double maxDist, std::vector<Vector3>* points, std::vector<int64_t>* triangles) {
+    if (!handle) throw std::runtime_error("closestPointsAttached: no mesh is attached");
+    const size_t Q = q.size();
+    std::vector<double> pts(3 * Q), dist(Q), cp(points ? 3 * Q : 0);
+    for (size_t a = 0; a < Q; a++)
+        for (int b = 0; b < 3; b++) pts[3 * a + b] = q[a][b];
+    if (triangles) triangles->resize(Q);
+    int64_t answered = 0;
+    if (shm_grid_attached_closest_point(handle, (int64_t)Q, pts.data(), maxDist, dist.data(), points ? cp.data() : nullptr, triangles ? triangles->data() : nullptr, &answered) !=
+        SHM_OK)
+        throw std::runtime_error(std::string("shm_grid_attached_closest_point: ") + shm_grid_last_error(handle));
+    if (points) {
+        points->resize(Q);
+        for (size_t a = 0; a < Q; a++) (*points)[a] = Vector3{cp[3 * a], cp[3 * a + 1], cp[3 * a + 2]};
+    }
+    return dist;
+}
+
 std::vector<double> SignedHeatGridSolver::castRaysMesh(const std::vector<Vector3>& origins, const std::vector<Vector3>& dirs, double tMin, double tMax,
                                                        std::vector<int64_t>* triangles, std::vector<double>* bary, std::vector<int32_t>* counts) {
     if (!handle) throw std::runtime_error("castRaysMesh: computeDistance has not been called");
@@ -338,6 +397,12 @@ VectorXd SignedHeatGridSolver::computeDistance(VertexPositionGeometry& geometry,
     std::vector<Vector3> normals;
     setFaceVectorAreas(geometry, areas, normals);
     const size_t F = geometry.mesh.nFaces();
+    // the surface itself, for attachInputMesh: polygons as fans from their first vertex
+    inputPositions = geometry.vertexPositions;
+    inputFaces.clear();
+    for (const auto& face : geometry.mesh.faces)
+        for (size_t k = 1; k + 1 < face.size(); k++) inputFaces.push_back({face[0], face[k], face[k + 1]});
+    inputIsMesh = true;
     srcPos.resize(3 * F);
     srcWn.resize(3 * F);
     srcArea = areas;
@@ -359,6 +424,9 @@ VectorXd SignedHeatGridSolver::computeDistance(PointPositionNormalGeometry& poin
         buildGrid(c, radius(pointGeom, c), options);
     }
     const size_t P = pointGeom.positions.size();
+    inputIsMesh = false;
+    inputPositions.clear();
+    inputFaces.clear();
     if (pointGeom.dualAreas.size() != P || !(pointGeom.meanEdgeLength > 0.)) estimatePointAreas(pointGeom);
     const double h = pointGeom.meanEdgeLength;  // :151
     shortTime = options.tCoef * h * h;

@@ -104,6 +104,21 @@ class SignedHeatGridSolver {
     // unanswered; the smallest index among equally near faces).  Keep neighbouring points neighbours in q.
     std::vector<double> closestPoints(const std::vector<Vector3>& q, double maxDist, std::vector<Vector3>* points = nullptr, std::vector<int64_t>* triangles = nullptr);
 
+    // The attached mesh (shm_grid_attach_mesh; contract in include/shm_grid.h): a second mesh on the device, independent of the resident one and of phi, with a
+    // closest-point index of its own.  attachMesh copies any triangle mesh there (cells: index cells per axis, 0 = automatic; it cannot show in an answer) and
+    // needs no computeDistance.  attachInputMesh attaches the surface of the LAST computeDistance(VertexPositionGeometry&) call, polygons fan-triangulated from
+    // each face's first vertex: `triangles` of closestPointsAttached then index that fan list (inputFanFaces()); after a point-cloud call it throws.
+    // attachSmoothed attaches the resident indexed mesh smoothed as isosurfaceSmoothed smooths it, device to device: nothing is fetched.
+    // closestPointsAttached is closestPoints against the attached mesh; maxDist is positive and may be +inf (the nearest face whatever its distance).
+    shm_mesh_index_info attachMesh(const std::vector<Vector3>& vertices, const std::vector<std::array<size_t, 3>>& triangles, int cells = 0);
+    shm_mesh_index_info attachInputMesh(int cells = 0);
+    shm_mesh_index_info attachSmoothed(int iterations, double lambda = 0.5, double mu = -0.53, double maxDisplacement = 0., bool slideOnBox = true, int cells = 0);
+    void detachMesh();
+    std::vector<double> closestPointsAttached(const std::vector<Vector3>& q, double maxDist = std::numeric_limits<double>::infinity(), std::vector<Vector3>* points = nullptr,
+                                              std::vector<int64_t>* triangles = nullptr);
+    const std::vector<std::array<size_t, 3>>& inputFanFaces() const { return inputFaces; }
+    const std::vector<Vector3>& inputVertices() const { return inputPositions; }
+
     // For every ray origins[q] + t dirs[q], t in [tMin, tMax]: where it first meets the indexed mesh resident on the device (the mesh closestPoints reads),
     // computed on the device (shm_grid_mesh_raycast; the rule and the contract in include/shm_grid.h).  Returns t, NaN for a miss; dirs need not be normalised.
     // triangles (optional) receives the index of the face hit in that call's `faces` (-1 for a miss), bary (optional, 2 per ray) the barycentrics (u, v) of the
@@ -148,6 +163,9 @@ class SignedHeatGridSolver {
     std::vector<double> srcPos, srcWn, srcArea;
     shm_stats stats{};
     int64_t indexedVertices = -1;   // vertices of the device's resident indexed mesh; -1: none built by this object
+    std::vector<Vector3> inputPositions;                  // the surface of the last mesh computeDistance, fan-triangulated (attachInputMesh)
+    std::vector<std::array<size_t, 3>> inputFaces;
+    bool inputIsMesh = false;
 
     void ensureHandle();
     void keepLargestComponents(int64_t keepLargest, int64_t minTriangles, int64_t& nv, int64_t& nt, std::vector<shm_iso_component>* components);

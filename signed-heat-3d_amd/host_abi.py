@@ -10,7 +10,7 @@ import os
 
 import numpy as np
 
-from .grid_abi import ISO_COMPONENT_DTYPE, ShmFieldStats, ShmRedistanceExactStats, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
+from .grid_abi import ISO_COMPONENT_DTYPE, ShmFieldStats, ShmMeshIndexInfo, ShmRedistanceExactStats, ShmRedistanceStats, ShmStats, ShmStep1Audit, load_library
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -48,6 +48,13 @@ def load_host_library():
         lib.shmh_vector_field_at.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(ShmFieldStats)]
     if hasattr(lib, "shmh_closest_points"):
         lib.shmh_closest_points.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    if hasattr(lib, "shmh_attach_mesh"):
+        lib.shmh_attach_mesh.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(ShmMeshIndexInfo)]
+        lib.shmh_attach_input_mesh.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ShmMeshIndexInfo)]
+        lib.shmh_attach_smoothed.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, C.c_int32, C.POINTER(ShmMeshIndexInfo)]
+        lib.shmh_detach_mesh.argtypes = [C.c_void_p]
+        lib.shmh_input_fan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.shmh_closest_points_attached.argtypes = lib.shmh_closest_points.argtypes
     if hasattr(lib, "shmh_cast_rays_mesh"):
         lib.shmh_cast_rays_mesh.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.POINTER(C.c_int64)]
@@ -189,6 +196,49 @@ class HostSolver:
         dist, cp, tri = np.empty(Q, dtype=np.float64), np.empty((Q, 3), dtype=np.float64), np.empty(Q, dtype=np.int64)
         na = C.c_int64()
         self._chk(self._lib.shmh_closest_points(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, cp.ctypes.data, tri.ctypes.data, C.byref(na)))
+        return dist, cp, tri, na.value
+
+    def attach_mesh(self, vertices, triangles, cells=0):
+        """attachMesh of the C++ mirror (shm_grid_attach_mesh): any triangle mesh, host arrays; returns the index info as a dict."""
+        V = np.ascontiguousarray(vertices, dtype=np.float64).reshape(-1, 3)
+        F = np.ascontiguousarray(triangles, dtype=np.int64).reshape(-1, 3)
+        info = ShmMeshIndexInfo()
+        self._chk(self._lib.shmh_attach_mesh(self._h, len(V), len(F), V.ctypes.data, F.ctypes.data, int(cells), C.byref(info)))
+        return info.as_dict()
+
+    def attach_input_mesh(self, cells=0):
+        """attachInputMesh of the C++ mirror: the surface of the last compute_distance, polygons fan-triangulated from each face's first vertex
+        (input_fan() returns that list); raises after a point-cloud solve."""
+        info = ShmMeshIndexInfo()
+        self._chk(self._lib.shmh_attach_input_mesh(self._h, int(cells), C.byref(info)))
+        return info.as_dict()
+
+    def attach_smoothed(self, iterations, lam=0.5, mu=-0.53, max_displacement=0.0, slide_on_box=True, cells=0):
+        """attachSmoothed of the C++ mirror (shm_grid_attach_isosurface_smoothed): the resident indexed mesh smoothed as isosurface_smoothed smooths it,
+        attached device to device."""
+        info = ShmMeshIndexInfo()
+        self._chk(self._lib.shmh_attach_smoothed(self._h, int(iterations), float(lam), float(mu), float(max_displacement), int(bool(slide_on_box)), int(cells),
+                                                 C.byref(info)))
+        return info.as_dict()
+
+    def detach_mesh(self):
+        self._chk(self._lib.shmh_detach_mesh(self._h))
+
+    def input_fan(self):
+        """(V [nv, 3], F [nt, 3]) of the fan-triangulated input surface: what attach_input_mesh attaches."""
+        counts = np.zeros(2, dtype=np.int64)
+        self._chk(self._lib.shmh_input_fan(self._h, counts.ctypes.data, None, None))
+        V, F = np.empty((counts[0], 3), dtype=np.float64), np.empty((counts[1], 3), dtype=np.int64)
+        self._chk(self._lib.shmh_input_fan(self._h, counts.ctypes.data, V.ctypes.data, F.ctypes.data))
+        return V, F
+
+    def closest_points_attached(self, points, max_dist=float("inf")):
+        """closestPointsAttached of the C++ mirror (shm_grid_attached_closest_point): returns (dist [Q], cp [Q, 3], tri [Q] int64, n_answered)."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        Q = pts.shape[0]
+        dist, cp, tri = np.empty(Q, dtype=np.float64), np.empty((Q, 3), dtype=np.float64), np.empty(Q, dtype=np.int64)
+        na = C.c_int64()
+        self._chk(self._lib.shmh_closest_points_attached(self._h, Q, pts.ctypes.data, float(max_dist), dist.ctypes.data, cp.ctypes.data, tri.ctypes.data, C.byref(na)))
         return dist, cp, tri, na.value
 
     def cast_rays_mesh(self, origins, dirs, t_min=0.0, t_max=float("inf")):
