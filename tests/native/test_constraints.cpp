@@ -2,7 +2,8 @@
 // [n, S, cell, bbox_min[3], pos[3 S], area[S]] (tests/test_constraints_host.py writes it from a golden fixture or a synthetic point set).  The rows are written
 // back (<out>.nodes.i64, <out>.coeffs.f64) for the bit-exact comparison with the fixture; everything else is checked here against brute force: shift items per
 // slab against the one-slab items and the areas, G against A A^T, B against A K A^T, the slab lists against the rows, the two-level partition for box requests of
-// 4 and 8 against G and the kernels' conventions, the Schur row order, the active tiles, and the "does not fit" flag on two row sets built here.
+// 4 and 8 against G and the kernels' conventions, the Schur row order, the active tiles, and the "does not fit" flag on two row sets built here.  Each partition
+// that fits is also printed (counts, then colour, rows and separator columns per box): tests/test_ginv_edges.py holds its numpy restatement of the rules to it.
 // usage: test_constraints INPUT OUT_PREFIX MUST_FIT(0|1)        Prints OK last.
 // Build+run:  g++ -O2 -std=c++17 -Wall -Wextra tests/native/test_constraints.cpp -o /tmp/test_constraints && /tmp/test_constraints in.f64 /tmp/out 0
 #include <cmath>
@@ -291,6 +292,22 @@ static void check_partition(const std::vector<Row>& rows, const Csr& Gcsr, const
         }
     }
     CHECK(sBox == t.sBox && sRow == t.sRow && tBox == t.tBox && tRow == t.tRow && chunkBox == t.chunkBox && chunkCol == t.chunkCol, "chunk lists");
+    // the counts, for tests/test_ginv_edges.py to hold its restatement of these rules to: one line per partition, one per box in the library's box order
+    // (colour, rows, separator columns, first row, first separator slot or -1)
+    printf("partition: request %d box %d P %d nI %d nS %d nSp %d maxs %d maxc %d\n", box, b, P, t.nI, nS, t.nSp, t.maxs, t.maxc);
+    std::vector<int> colour_of((size_t)P, -1);
+    for (int col = 0; col < 8; col++)
+        for (int q = t.colour_ptr[col]; q < t.colour_ptr[col + 1]; q++) colour_of[(size_t)t.colour_list[(size_t)q]] = col;
+    for (int a = 0; a < P; a++) {
+        const int ca = t.ptrS[(size_t)a + 1] - t.ptrS[(size_t)a];
+        printf("  box %d: colour %d s %d c %d row0 %d col0 %d\n", a, colour_of[(size_t)a], t.ptrI[(size_t)a + 1] - t.ptrI[(size_t)a], ca, t.rowsI[(size_t)t.ptrI[(size_t)a]],
+               ca > 0 ? t.colsS[(size_t)t.ptrS[(size_t)a]] : -1);
+        printf("    rows");
+        for (int u = t.ptrI[(size_t)a]; u < t.ptrI[(size_t)a + 1]; u++) printf(" %d", t.rowsI[(size_t)u]);
+        printf("\n    cols");
+        for (int l = t.ptrS[(size_t)a]; l < t.ptrS[(size_t)a + 1]; l++) printf(" %d", t.colsS[(size_t)l]);
+        printf("\n");
+    }
 }
 
 // rows of one point per listed cell on a unit grid

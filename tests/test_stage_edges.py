@@ -351,10 +351,12 @@ def _projector_errors(P, precision, tol, v, got):
     return float((err / bound).max()), float(err.max())
 
 
-def _projector_case(s, d_n, precision, tol, with_properties):
+def _projector_case(s, d_n, precision, tol, with_properties, P=None):
+    """P: the host projector to hold the handle to (test_ginv_edges.py passes its refined one); by default the dense one of this file."""
     n = d_n
     nodes, coeffs = s.get_constraints()
-    P = _HostProjector(nodes, coeffs, n ** 3)
+    if P is None:
+        P = _HostProjector(nodes, coeffs, n ** 3)
     rng = np.random.default_rng(1)
     v = _round_to(rng.standard_normal(n ** 3), precision)
     Pv = s.apply_projector(v)
